@@ -8,7 +8,15 @@ fine-tune default keeps): synthetic latents [B,13,16,60,90] + text [B,226,4096]
 already resident in HBM -> add_noise -> DiT forward -> loss -> backward (LoRA grads) -> [DDP all-reduce] -> fused AdamW.
 Random-init weights of the 2B architecture (no checkpoints offline), nothing skipped inside the timed region.
 
+A plain run sets up, warms up, times --steps optimizer steps and prints one JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall milliseconds of one timed step).  --full adds what takes extra work: HIP-event times of the attention / GEMM /
+convolution launches inside the timed steps (`kernels`, `roofline`, `roofline_more`), the CPU-oracle baseline (`cpu_baseline`) and,
+for --model hunyuan --fp8, the same batch's loss in bf16.  --dump-outputs DIR writes, after the timed steps, what the last timed
+step computed (loss, the denoiser's prediction, the trained parameters after the update and their gradients) as float32 .npy files.
+
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full                  # + per-kernel times, roofline, CPU baseline
+  python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR      # + the last timed step's outputs as DIR/*.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -110,6 +118,33 @@ if __name__ == "__main__" and _wants_launch(sys.argv[1:]):
 import torch
 import torch.distributed as dist
 
+DUMP_CAP = 5_000_000        # elements per dumped array (20 MB of float32); a larger array is written as a fixed, seeded sample
+DUMP_LIMIT = 64_000_000     # bytes of all dumped arrays together (64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> tensor, written as path/<name>.npy in float32.  An array of more than DUMP_CAP elements is replaced by
+    DUMP_CAP of its (flattened) elements at sorted indices drawn from a fixed seed, so two runs of the same arguments sample the same
+    elements.  Returns name -> {"shape", "sampled"} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out, total = {}, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        sampled = flat.numel() > DUMP_CAP
+        if sampled:
+            idx = torch.randint(0, flat.numel(), (DUMP_CAP,), generator=torch.Generator().manual_seed(0)).sort().values
+            flat = flat[idx.to(flat.device)]
+        a = flat.to(torch.float32).cpu().numpy()
+        if not sampled:
+            a = a.reshape(tuple(t.shape))
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT} bytes"
+        np.save(os.path.join(path, name + ".npy"), a)
+        out[name] = {"shape": list(t.shape), "sampled": DUMP_CAP if sampled else None}
+    return out
+
 
 def cpu_baseline(seconds_budget=40.0):
     """The oracle (CPU restatement of the reference path) timed on the host cores: ONE full-size CogVideoX-2B block,
@@ -205,7 +240,7 @@ def bench_vc2(args):
     for _ in range(args.warmup):
         step()
     barrier()
-    ops.profile_reset(True)
+    ops.profile_reset(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -240,11 +275,12 @@ def bench_vc2(args):
                           "weights": "seeded random init (no checkpoints offline)", "latents": "pre-encoded latents (synthetic)",
                           "text": "pre-encoded OpenCLIP embeddings (synthetic)"},
                "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
-               "step_tflops_algorithmic": step_tflop * args.steps / elapsed,
-               "roofline": {"bound": "mfma", "kernel": "convnd_cl_kernel / convnd320_kernel", "achieved": ach, "peak": 2500.0, "unit": "TFLOP/s",
-                            "frac": (ach / 2500.0) if ach else None, "traffic": None,
-                            "note": "all forward / input-gradient convolutions of the step, 2*M*Cout*taps*Cin FLOPs each, HIP events on the launch stream"},
-               "kernels": kern, "loss_first": lv[0], "loss_last": lv[-1]}
+               "step_tflops_algorithmic": step_tflop * args.steps / elapsed, "loss_first": lv[0], "loss_last": lv[-1]}
+        if args.full:
+            res["roofline"] = {"bound": "mfma", "kernel": "convnd_cl_kernel / convnd320_kernel", "achieved": ach, "peak": 2500.0, "unit": "TFLOP/s",
+                               "frac": (ach / 2500.0) if ach else None, "traffic": None,
+                               "note": "all forward / input-gradient convolutions of the step, 2*M*Cout*taps*Cin FLOPs each, HIP events on the launch stream"}
+            res["kernels"] = kern
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()
@@ -341,7 +377,7 @@ def bench_hunyuan(args):
     g = torch.Generator(device=dev).manual_seed(20230211 + dp_idx)          # the ranks of a sequence-parallel group see the same batch
     tv = torch.tensor([Lt - 37 * (b % 5) for b in range(B)], device=dev)
     losses = []
-    ops.profile_reset(True)
+    ops.profile_reset(args.full)
     if lora:
         # the WHOLE denoiser (patch embed, token refiner, modulation vector, 20 + 40 blocks, final layer) through the workflow's training_step:
         # latents [B, 16, T, H, W] (default 5 x 68 x 120 = 544x960x17f after the 4x8x8 VAE -> 10 200 tokens; 33,90,160 = 720p x 129f -> 118 800),
@@ -407,7 +443,7 @@ def bench_hunyuan(args):
         torch.cuda.synchronize()
 
     fp8_cmp = None
-    if args.fp8 and world == 1:      # the same batch through the E4M3 weights and through the bf16 weights they were rounded from
+    if args.fp8 and world == 1 and args.full:      # the same batch through the E4M3 weights and through the bf16 weights they were rounded from
         def repack(mode):
             model.fp8 = mode; model._packed = None
             if model.lora is not None:
@@ -417,13 +453,14 @@ def bench_hunyuan(args):
     for _ in range(args.warmup):
         step()
     barrier()
-    ops.profile_reset(True)
+    ops.profile_reset(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
     prof, work = ops.profile_collect(), ops.profile_work()
+    ops.profile_reset(False)
     if world > 1:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -458,7 +495,7 @@ def bench_hunyuan(args):
                                  "mode": "lora" if lora else "fullft", "parallelism": f"dp{n_dp} x sp{sp_deg} (Ulysses)" if sp_deg > 1 else f"dp{n_dp}",
                                  "micro_batch": B, "double_blocks": nd, "single_blocks": ns, "weights": "seeded random init"},
                       "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1), "step_tflops_algorithmic": step_tf * args.steps / elapsed,
-                      "kernels": kern, "loss_first": lv[0], "loss_last": lv[-1],
+                      **({"kernels": kern} if args.full else {}), "loss_first": lv[0], "loss_last": lv[-1],
                       **({"fp8": {"mode": "every Linear of the double / single blocks holds its weight as E4M3 with a per-tensor scale and multiplies the "
                                           "de-quantised copy in bf16 (the reference's fp8_optimization.py:55-101); activations, gradients and the product stay bf16",
                                   **(fp8_cmp or {})}} if args.fp8 else {})}), flush=True)
@@ -474,7 +511,13 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=None, help="default: 4 (2B LoRA), 2 otherwise; vc2 / stdit: 4")
     ap.add_argument("--accum", type=int, default=None, help="default: 1 (2B LoRA), 2 otherwise; vc2 / stdit: 1")
     ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 is not the benchmark")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU-oracle baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: HIP-event times of the attention / GEMM / convolution launches "
+                         "in the timed steps (kernels, roofline, roofline_more), the CPU-oracle baseline, the --fp8 line's bf16 loss")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB; an "
+                         "array of more than 5 M elements as a fixed, seeded sample of its elements); CogVideoX lines (--model 2b / 5b)")
     ap.add_argument("--model", choices=["2b", "5b", "vc2", "stdit", "hunyuan"], default="2b",
                     help="2b = the benchmark (BASELINE configs[1]); 5b = CogVideoX-5B dimensions (48 heads, 42 layers, rotary q/k) -- "
                          "extra data point, labelled as such, never the headline line; vc2 = BASELINE configs[3], the VideoCrafter2 "
@@ -510,6 +553,11 @@ def main():
             args.micro_batch = 4 if lora_2b else 2
         if args.accum is None:
             args.accum = (4 // args.micro_batch if args.micro_batch in (1, 2, 4) and lora_2b else 2)
+
+    if args.dump_outputs and args.model not in ("2b", "5b"):
+        ap.error("--dump-outputs is implemented for the CogVideoX lines (--model 2b / 5b)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.rehearse:
         from vt355.ddp import init_from_env
@@ -708,6 +756,7 @@ def main():
 
     batches = [make_batch() for _ in range(args.accum)]
     losses = []
+    last = {} if args.dump_outputs else None       # --dump-outputs: the prediction of the step's last micro-batch
 
     def step():
         nonlocal batches
@@ -732,6 +781,8 @@ def main():
             out = peft(hidden_states=noisy, encoder_hidden_states=text, timestep=t, image_rotary_emb=rope, return_dict=False)[0]
             sa, sb, w = sched.coefficients(t)
             loss = _LossFn.apply(out, noisy, x0, sa, sb, w)
+            if last is not None:
+                last["prediction"] = out.detach()
             if args.mode == "fullft":             # DDP no_sync: slices are all-reduced only on the last micro-batch,
                 st.on_grads_ready = red.hook if mb == args.accum - 1 else None      # as the backward finishes them
             (loss / args.accum).backward()
@@ -754,7 +805,7 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    ops.profile_reset(True)
+    ops.profile_reset(args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -800,7 +851,7 @@ def main():
             src = hashlib.sha256(open(os.path.join(ROOT, "videotuna-dev_amd", "csrc", "attn_bwd.hip"), "rb").read()).hexdigest()[:16]
             import glob as _glob
             alg_gb = 8 * args.micro_batch * S * 30 * 64 * 2 / 1e9       # q, k, v, o, dO read + dQ, dK, dV written, bf16
-            for path in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_bench_summary.json")), reverse=True):
+            for path in (sorted(_glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_bench_summary.json")), reverse=True) if args.full else []):
                 with open(path) as f:
                     summ = json.load(f)
                 rel = os.path.relpath(path, ROOT)
@@ -845,24 +896,28 @@ def main():
                                    "on a side stream" if args.vae_encoder else "pre-encoded latents (synthetic)"),
                        **({"encoder_cache": {"dataset": args.encoder_cache, "hits": dict(ecache.hits), "misses": dict(ecache.misses)}} if ecache is not None else {})},
             "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1),
-            "roofline": {"bound": "mfma", "kernel": "attn_bwd_hd64_kernel", "achieved": ach, "peak": 2500.0,
-                         "unit": "TFLOP/s", "frac": (ach / 2500.0) if ach else None, "traffic": traffic,
-                         "traffic_unit": traffic_note,
-                         "note": "algorithmic FLOPs per launch 8*S^2*d*B (dQ,dK,dV products; P recompute not counted)"},
-            "roofline_more": [
-                {"bound": "mfma", "kernel": "attn_fwd_hd64_kernel", "achieved": kern.get("attn_fwd", {}).get("tflops_algorithmic"), "peak": 2500.0,
-                 "unit": "TFLOP/s", "frac": (kern["attn_fwd"]["tflops_algorithmic"] / 2500.0) if "attn_fwd" in kern else None},
-                {"bound": "mfma", "kernel": "gemm_tn_* (every Linear with >= 4096 rows, forward and dX)", "achieved": kern.get("gemm", {}).get("tflops_algorithmic"),
-                 "peak": 2500.0, "unit": "TFLOP/s", "frac": (kern["gemm"]["tflops_algorithmic"] / 2500.0) if kern.get("gemm", {}).get("tflops_algorithmic") else None}] + hbm_lines,
-            "kernels": kern,
             "ddp": {"backend": (dist.get_backend() if world > 1 else None), "world_size_seen": (dist.get_world_size() if world > 1 else 1),
                     "allreduce_bytes_per_step": (int(st.grad.numel() * (2 if (args.mode == "fullft" and args.allreduce_dtype == "bf16") else 4)) if world > 1 else 0),
                     "allreduce_dtype": (args.allreduce_dtype if args.mode == "fullft" else "fp32"),
                     "dq_chains": bool(ops.attn_bwd_chain_workspace(args.micro_batch, model.config.num_attention_heads, S, dev) is not None)},
             "loss_last": loss_vals[-1], "loss_first": loss_vals[0],
         }
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline()
+        if args.dump_outputs:        # rank 0's last timed step: its losses, the last micro-batch's prediction, the updated weights, the gradient
+            res["outputs"] = dump_outputs(args.dump_outputs, {"loss": torch.stack(losses[-args.accum:]), "prediction": last["prediction"],
+                                                              "params": st.flat, "grads": st.grad})
+        if args.full:
+            res["roofline"] = {"bound": "mfma", "kernel": "attn_bwd_hd64_kernel", "achieved": ach, "peak": 2500.0,
+                               "unit": "TFLOP/s", "frac": (ach / 2500.0) if ach else None, "traffic": traffic,
+                               "traffic_unit": traffic_note,
+                               "note": "algorithmic FLOPs per launch 8*S^2*d*B (dQ,dK,dV products; P recompute not counted)"}
+            res["roofline_more"] = [
+                {"bound": "mfma", "kernel": "attn_fwd_hd64_kernel", "achieved": kern.get("attn_fwd", {}).get("tflops_algorithmic"), "peak": 2500.0,
+                 "unit": "TFLOP/s", "frac": (kern["attn_fwd"]["tflops_algorithmic"] / 2500.0) if "attn_fwd" in kern else None},
+                {"bound": "mfma", "kernel": "gemm_tn_* (every Linear with >= 4096 rows, forward and dX)", "achieved": kern.get("gemm", {}).get("tflops_algorithmic"),
+                 "peak": 2500.0, "unit": "TFLOP/s", "frac": (kern["gemm"]["tflops_algorithmic"] / 2500.0) if kern.get("gemm", {}).get("tflops_algorithmic") else None}] + hbm_lines
+            res["kernels"] = kern
+            if world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline()
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

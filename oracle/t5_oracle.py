@@ -14,7 +14,7 @@ What it follows:
                                            plus a bucketed relative position bias shared by all layers, gated-GELU MLP,
                                            final RMSNorm; no biases anywhere).
 
-PARITY STATUS: pinned.  tests/golden/t5_tiny.npz holds seeded weights, input ids and the output of transformers'
+PARITY STATUS: pinned.  tests/golden/t5_tiny.part*.npz holds seeded weights, input ids and the output of transformers'
 own ``T5EncoderModel`` (tests/golden/make_golden_t5.py; generated with the transformers 5.15.0 that is importable in the build
 container -- the encoder's arithmetic is unchanged since 4.46.2), and tests/test_oracle_golden.py checks this restatement
 against it.  Real T5-XXL weights are not available offline: the full-size check runs on seeded random weights.

@@ -15,7 +15,7 @@ What it follows: the reference's in-tree twin of diffusers' ``AutoencoderKLCogVi
 CogVideoX-2B/5B: ch 128, ch_mult (1,2,2,4), 3 ResNet blocks per level, z_channels 16 (double_z: 32 output channels = mean | logvar),
 temporal_compress_times 4.
 
-PARITY STATUS: pinned.  tests/golden/vae_encoder_tiny.npz holds seeded weights, an input clip and the output of the reference's own
+PARITY STATUS: pinned.  tests/golden/vae_encoder_tiny.part*.npz holds seeded weights, an input clip and the output of the reference's own
 ``ContextParallelEncoder3D`` imported in the build container (tests/golden/make_golden_vae.py; beartype / sgm.util / SafeConv3d
 stubbed, a 1-rank gloo group for the context-parallel helpers); tests/test_oracle_golden.py checks this restatement against it.
 Parameter names are the SAT twin's (``down.0.block.0.conv1.conv.weight`` ...); the diffusers checkpoint names

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/t5_tiny.npz: seeded weights + input ids + the output of transformers' own T5EncoderModel
+"""Generates tests/golden/t5_tiny.part*.npz (tests/golden_io.py): seeded weights + input ids + the output of transformers' own T5EncoderModel
 (the third-party module the reference calls at cogvideo_pl.py:254-286; pinned 4.46.2 in its poetry.lock, 5.15.0 importable
 here).  Run in the build container:  python tests/golden/make_golden_t5.py"""
 import os
@@ -10,6 +10,8 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
+sys.path.insert(0, os.path.join(HERE, ".."))
+import golden_io  # noqa: E402  (fixtures of more than 1 MiB are stored in parts)
 import t5_oracle as T                                               # only for the seeded weights / config
 import transformers
 from transformers import T5Config, T5EncoderModel
@@ -32,9 +34,9 @@ def main():
     with torch.no_grad():
         out = hf(input_ids=ids)[0]                                    # no attention mask, as the reference calls it
         bias = hf.encoder.block[0].layer[0].SelfAttention.compute_bias(150, 150)[0]
-    np.savez_compressed(os.path.join(HERE, "t5_tiny.npz"), ids=ids.numpy(), out=out.numpy().astype(np.float32),
-                        bias=bias.numpy().astype(np.float32), transformers_version=np.array(transformers.__version__),
-                        **{"P." + k: v.numpy() for k, v in P.items()})
+    golden_io.save(os.path.join(HERE, "t5_tiny.npz"), ids=ids.numpy(), out=out.numpy().astype(np.float32),
+                   bias=bias.numpy().astype(np.float32), transformers_version=np.array(transformers.__version__),
+                   **{"P." + k: v.numpy() for k, v in P.items()})
     print("wrote t5_tiny.npz", out.shape, float(out.abs().max()))
 
 

@@ -9,7 +9,7 @@ Non-arithmetic imports absent here are stubbed (colorama, omegaconf, loguru, cv2
 oracle/unet_oracle.init_params (seeded; zero-initialised reference layers get random weights so gradients flow), so the fixture
 holds only inputs, outputs and gradients.  Modules run in eval() mode: TemporalConvBlock's dropout(0.1) is then the identity.
 
-    python tests/golden/make_golden_unet.py   -> tests/golden/unet_tiny.npz, unet_blocks.npz
+    python tests/golden/make_golden_unet.py   -> tests/golden/unet_tiny.part*.npz, unet_blocks.part*.npz
 """
 import os
 import sys
@@ -20,6 +20,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
+sys.path.insert(0, os.path.join(HERE, ".."))
+import golden_io  # noqa: E402  (fixtures of more than 1 MiB are stored in parts)
 import make_golden as MG  # noqa: E402
 import unet_oracle as U   # noqa: E402
 
@@ -69,7 +71,7 @@ def main():
     for n in keep:
         assert n in names, n
         rec["grad." + n] = dict(net.named_parameters())[n].grad.detach().numpy()
-    np.savez_compressed(os.path.join(HERE, "unet_tiny.npz"), **rec)
+    golden_io.save(os.path.join(HERE, "unet_tiny.npz"), **rec)
     print("unet_tiny: out", tuple(out.shape), "loss", loss.item(), "params", len(names), sum(p.numel() for p in net.parameters()))
 
     # ---------------- each block alone: output, input gradient, parameter gradients ----------------
@@ -109,7 +111,7 @@ def main():
     assert isinstance(dn, om.Downsample) and isinstance(up, om.Upsample)
     run("down", dn, (torch.randn(4, 64, 8, 8, generator=g),), (0,))
     run("up", up, (torch.randn(4, 128, 4, 4, generator=g),), (0,))
-    np.savez_compressed(os.path.join(HERE, "unet_blocks.npz"), **blk)
+    golden_io.save(os.path.join(HERE, "unet_blocks.npz"), **blk)
     print("unet_blocks:", len(blk), "arrays")
 
     # ---------------- LDDPM q_sample / schedule / scale_arr for the loss path ----------------

@@ -10,7 +10,7 @@ container only; stubs as in make_golden_unet.py):
     modules the recipe targets (configs/001_videocrafter2/vc2_t2v_lora.yaml:7-12: to_q / to_k / to_v; videotuna/models/lvdm/ddpm3d.py:100-117,
     434-445) -- every CrossAttention of the reference UNetModel; base weights frozen; output, loss and every adapter gradient.
 
-    python tests/golden/make_golden_unet_train.py   -> tests/golden/unet_train.npz
+    python tests/golden/make_golden_unet_train.py   -> tests/golden/unet_train.part*.npz
 """
 import os
 import sys
@@ -22,6 +22,8 @@ import torch.nn as nn
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
+sys.path.insert(0, os.path.join(HERE, ".."))
+import golden_io  # noqa: E402  (fixtures of more than 1 MiB are stored in parts)
 import make_golden as MG  # noqa: E402
 import unet_oracle as U   # noqa: E402
 
@@ -145,8 +147,8 @@ def main():
     for n, p in lp.items():
         rec["lora.g." + n] = p.grad.detach().numpy()
     print("LoRA UNet: sites", len(sites), "adapter tensors", len(lp), "loss", loss.item())
-    np.savez_compressed(os.path.join(HERE, "unet_train.npz"), **rec)
-    print("unet_train.npz:", len(rec), "arrays,", os.path.getsize(os.path.join(HERE, "unet_train.npz")) // 1024, "KiB")
+    parts = golden_io.save(os.path.join(HERE, "unet_train.npz"), **rec)
+    print("unet_train.npz:", len(rec), "arrays,", sum(os.path.getsize(p) for p in parts) // 1024, "KiB")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/vae_encoder_tiny.npz by running the reference's own ContextParallelEncoder3D
+"""Generates tests/golden/vae_encoder_tiny.part*.npz (tests/golden_io.py) by running the reference's own ContextParallelEncoder3D
 (videotuna/models/cogvideo_sat/vae_modules/cp_enc_dec.py) on seeded weights in the build container.  Non-arithmetic imports are
 stubbed (beartype, sgm.util's context-parallel getters -> world 1 / rank 0, vae_modules.utils.SafeConv3d -> torch.nn.Conv3d, which
 it subclasses without changing the arithmetic below 2 GB); a 1-rank gloo group serves torch.distributed.get_rank().
@@ -17,6 +17,8 @@ import torch.distributed as dist
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = "/root/reference"
 sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
+sys.path.insert(0, os.path.join(HERE, ".."))
+import golden_io  # noqa: E402  (fixtures of more than 1 MiB are stored in parts)
 import vae_oracle as V
 
 
@@ -51,7 +53,7 @@ def main():
     x = torch.randn(1, 3, 9, 16, 24, generator=g)          # 9 frames -> 5 -> 3 latent frames; 16x24 -> 4x6
     with torch.no_grad():
         out = enc(x)
-    np.savez_compressed(os.path.join(HERE, "vae_encoder_tiny.npz"), x=x.numpy(), out=out.numpy(), **{"P." + k: v.numpy() for k, v in P.items()})
+    golden_io.save(os.path.join(HERE, "vae_encoder_tiny.npz"), x=x.numpy(), out=out.numpy(), **{"P." + k: v.numpy() for k, v in P.items()})
     print("wrote vae_encoder_tiny.npz", tuple(out.shape), float(out.abs().max()))
     # DownSample3D alone, both temporal branches (cp_enc_dec.py:640-676): rank-0 / fake_cp (first frame kept) and the plain
     # avg_pool1d branch (fake_cp=False), on an odd and an even frame count

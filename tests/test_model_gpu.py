@@ -252,7 +252,7 @@ def test_block_recompute_gives_the_same_gradients(dev, mode):
 @pytest.mark.parametrize("S", [150, 226])
 def test_t5_encoder_matches_oracle(dev, S):
     """The frozen text encoder on the vt355 kernels (rmsnorm, fused QKV / wi GEMMs, attention with the relative position
-    bias, gated GELU) against oracle/t5_oracle.py -- itself pinned to transformers' T5EncoderModel by tests/golden/t5_tiny.npz.
+    bias, gated GELU) against oracle/t5_oracle.py -- itself pinned to transformers' T5EncoderModel by tests/golden/t5_tiny.part*.npz.
     bf16 storage vs the fp64 oracle on the bf16-rounded weights."""
     import t5_oracle as T
     from vt355.t5 import T5EncoderModel

@@ -7,15 +7,27 @@ import torch
 import torch.nn.functional as F
 
 import cogvideox_oracle as O
+import golden_io
 
 G = os.path.join(os.path.dirname(__file__), "golden")
+
+
+def _sinusoid_bound(t, dim, max_period=10000.0):
+    """1e-6 plus what the fp32 frequency table admits: exp() in fp32 is faithful to 1-2 ulps, which ones depends on the CPU's vector-math
+    path (the golden holds one machine's), and an ulp of f moves the argument t*f, hence its sine and cosine, by up to |t f| 2^-23.  Any
+    formula error (period, shift, flip, order) is off by orders of magnitude more."""
+    half = dim // 2
+    f = np.exp(-np.log(max_period) * np.arange(half) / half)
+    tf = np.abs(np.asarray(t, np.float64)[:, None] * f[None])
+    return 1e-6 + 4.0 * 2.0 ** -24 * np.concatenate([tf, tf], axis=1)
 
 
 def test_timestep_sinusoid_matches_reference():
     g = np.load(os.path.join(G, "timestep_embedding.npz"))
     t = torch.from_numpy(g["t"])
-    assert np.abs(O.timestep_sinusoid(t, 1920).numpy() - g["emb1920"]).max() < 1e-6
-    assert np.abs(O.timestep_sinusoid(t, 64).numpy() - g["emb64"]).max() < 1e-6
+    for dim, key in ((1920, "emb1920"), (64, "emb64")):
+        dev = np.abs(O.timestep_sinusoid(t, dim).numpy().astype(np.float64) - g[key])
+        assert (dev <= _sinusoid_bound(g["t"], dim)).all(), (dim, dev.max())
 
 
 def test_pos_embed_matches_sat_twin():
@@ -151,7 +163,7 @@ def test_t5_oracle_matches_transformers_golden():
     (tests/golden/make_golden_t5.py): the whole encoder and the bucketed relative position bias (150 tokens > max_distance,
     so exact, log-spaced and clamped buckets all occur)."""
     import t5_oracle as T
-    g = np.load(os.path.join(G, "t5_tiny.npz"))
+    g = golden_io.load("t5_tiny")
     cfg = T.tiny_config()
     P = {k[2:]: torch.from_numpy(g[k]).double() for k in g.files if k.startswith("P.")}
     ids = torch.from_numpy(g["ids"])
@@ -170,7 +182,7 @@ def test_vae_encoder_oracle_matches_reference_twin_golden():
     cp_enc_dec.py:779-907) on seeded weights (tests/golden/make_golden_vae.py): causal padding, ResNet blocks, temporal + spatial
     downsampling, 9 frames -> 3 latent frames."""
     import vae_oracle as V
-    g = np.load(os.path.join(G, "vae_encoder_tiny.npz"))
+    g = golden_io.load("vae_encoder_tiny")
     cfg = V.tiny_config()
     P = {k[2:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("P.")}
     out = V.encoder_forward(P, cfg, torch.from_numpy(g["x"]))
@@ -265,7 +277,7 @@ def test_unet_oracle_matches_reference_unet_output_and_gradients():
     """oracle/unet_oracle.py vs the reference's own UNetModel (openaimodel3d.py:313-694) run by tests/golden/make_golden_unet.py:
     output, eps-MSE loss, checksums of ALL 626 parameter gradients and 15 gradients in full."""
     U, cfg, P = _unet_params()
-    g = np.load(os.path.join(G, "unet_tiny.npz"))
+    g = golden_io.load("unet_tiny")
     for v in P.values():
         v.requires_grad_(True)
     T = lambda k: torch.from_numpy(g[k])
@@ -290,7 +302,7 @@ def test_unet_oracle_blocks_match_reference_blocks():
     """each block alone (ResBlock with temporal conv + 1x1 skip, TemporalConvBlock, SpatialTransformer, TemporalTransformer,
     CrossAttention with a context longer than 77, Downsample, Upsample): output, input gradients, every parameter gradient"""
     U, cfg, P = _unet_params()
-    g = np.load(os.path.join(G, "unet_blocks.npz"))
+    g = golden_io.load("unet_blocks")
     T = lambda k: torch.from_numpy(g[k]).double()
 
     def check(tag, pre, fn, nin):
@@ -341,7 +353,7 @@ def test_unet_oracle_train_mode_dropout_matches_reference():
     (tests/golden/make_golden_unet_train.py recorded the keep masks they drew): the oracle with those masks reproduces output, input
     gradient and parameter gradients -- pins WHERE the dropout sits (GroupNorm -> SiLU -> Dropout -> Conv3d, conv2..conv4) and its 1 / (1 - p)"""
     U, cfg, P = _unet_params()
-    g = np.load(os.path.join(G, "unet_train.npz"))
+    g = golden_io.load("unet_train")
     T = lambda k: torch.from_numpy(g[k]).double()
     pre = "input_blocks.1.0.temopral_conv"
     masks = {k[len("tconv.mask."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("tconv.mask.")}
@@ -382,7 +394,7 @@ def test_unet_oracle_lora_matches_reference_with_hand_injected_adapters():
     UNetModel with peft's Linear formula y = W x + (lora_alpha / r) B(A x) (vc2_t2v_lora.yaml:7-12; ddpm3d.py:100-117, 434-445), base
     frozen.  The oracle with the same adapters: output, loss, all 180 adapter gradients."""
     U, cfg, P = _unet_params()
-    g = np.load(os.path.join(G, "unet_train.npz"))
+    g = golden_io.load("unet_train")
     T = lambda k: torch.from_numpy(g[k]).double()
     L = U.init_lora(cfg, r=int(g["lora.r"]), lora_alpha=float(g["lora.alpha"]), seed=3, zero_b=False)
     assert len(U.lora_sites(cfg)) == 90

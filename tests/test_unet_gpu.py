@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import golden_io
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -36,10 +38,10 @@ def _relerr(a, b):
 
 
 def test_tiny_unet_forward_matches_golden_and_oracle(dev):
-    """forward on the golden inputs of the REFERENCE UNetModel run (tests/golden/unet_tiny.npz): vs the reference output itself
+    """forward on the golden inputs of the REFERENCE UNetModel run (tests/golden/unet_tiny.part*.npz): vs the reference output itself
     (weights differ only by bf16 rounding) and vs the oracle on the rounded weights"""
     U, cfg, m, Pr = _tiny(dev)
-    g = np.load(os.path.join(G, "unet_tiny.npz"))
+    g = golden_io.load("unet_tiny")
     x = torch.from_numpy(g["x"]); ctx = torch.from_numpy(g["context"]); t = torch.from_numpy(g["t"]); fps = torch.from_numpy(g["fps"])
     with torch.no_grad():
         out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
@@ -55,7 +57,7 @@ def test_tiny_unet_train_step_matches_oracle(dev):
     from vt355.optim import FusedAdamW
     U, cfg, m, Pr = _tiny(dev)
     ts = m.enable_training()
-    g = np.load(os.path.join(G, "unet_tiny.npz"))
+    g = golden_io.load("unet_tiny")
     x = torch.from_numpy(g["x"]); ctx = torch.from_numpy(g["context"]); t = torch.from_numpy(g["t"]); fps = torch.from_numpy(g["fps"])
     noise = torch.from_numpy(g["noise"])
     out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
@@ -109,7 +111,7 @@ def _grad_report(m, ts, Pr, names=None):
 def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
     """model.train(): TemporalConvBlock's three nn.Dropout(0.1) per ResBlock (openaimodel3d.py:278-296) are applied by vt_dropout_bf16.  The
     masks are a pure function of (seed, site, element): recomputed here bit for bit by oracle/philox.py from the sites the forward
-    recorded and handed to the oracle (itself pinned to the reference's real nn.Dropout run by tests/golden/unet_train.npz); loss and
+    recorded and handed to the oracle (itself pinned to the reference's real nn.Dropout run by tests/golden/unet_train.part*.npz); loss and
     every parameter gradient must agree, and must differ from the eval-mode run."""
     import philox
     from vt355 import ops
@@ -117,7 +119,7 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
     ts = m.enable_training()
     m.train()
     m.dropout_seed = 20240607
-    g = np.load(os.path.join(G, "unet_tiny.npz"))
+    g = golden_io.load("unet_tiny")
     x = torch.from_numpy(g["x"]); ctx = torch.from_numpy(g["context"]); t = torch.from_numpy(g["t"]); fps = torch.from_numpy(g["fps"])
     noise = torch.from_numpy(g["noise"])
     B, _, T, H, W = x.shape
@@ -159,12 +161,12 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
 def test_tiny_unet_lora_train_step_matches_oracle(dev):
     """vc2_t2v_lora.yaml's recipe on the tiny UNet: rank-4 adapters on to_q / to_k / to_v of every CrossAttention (K-extension GEMMs), base
     frozen.  Output, eps-MSE loss and all 180 adapter gradients vs the fp64 oracle with the same adapters (oracle/unet_oracle.lora_linear,
-    pinned to the REFERENCE UNetModel with hand-injected peft-formula adapters by tests/golden/unet_train.npz); no base-weight gradient
+    pinned to the REFERENCE UNetModel with hand-injected peft-formula adapters by tests/golden/unet_train.part*.npz); no base-weight gradient
     buffer exists; one fused AdamW step moves only the adapters"""
     from vt355 import ops
     from vt355.optim import FusedAdamW
     U, cfg, m, Pr = _tiny(dev)
-    g = np.load(os.path.join(G, "unet_train.npz"))
+    g = golden_io.load("unet_train")
     L = U.init_lora(cfg, r=int(g["lora.r"]), lora_alpha=float(g["lora.alpha"]), seed=3, zero_b=False)
     m.add_lora(int(g["lora.r"]), float(g["lora.alpha"]), ("to_q", "to_k", "to_v"))
     sd = m.state_dict()
@@ -221,7 +223,7 @@ def _cl(x5):
 def _block_case(dev, kind, full=False):
     """one layer of the tiny UNet through the engine (forward, input gradient, parameter gradients) vs the oracle's function for
     that block -- the oracle functions are pinned to the reference's own blocks by tests/test_oracle_golden.py
-    (tests/golden/unet_blocks.npz: ResBlock + TemporalConvBlock, SpatialTransformer, TemporalTransformer, Downsample, Upsample)"""
+    (tests/golden/unet_blocks.part*.npz: ResBlock + TemporalConvBlock, SpatialTransformer, TemporalTransformer, Downsample, Upsample)"""
     from vt355.unet import _Run, _Var
     import unet_oracle as UO
     if full:
@@ -310,7 +312,7 @@ def test_unet_block_alone(dev, kind):
 def test_unet_level0_blocks_at_the_recipes_full_size(dev, kind):
     """BASELINE configs[3] at its stated shapes: one ResBlock (+ TemporalConvBlock), one SpatialTransformer and one TemporalTransformer of the
     first UNet level -- 320 channels, 5 heads x 64, 16 frames of 40 x 64 latents, 77 x 1024 text context -- through the engine against the
-    fp32 oracle functions (pinned to the reference's own blocks by tests/golden/unet_blocks.npz): output, input gradient and every parameter
+    fp32 oracle functions (pinned to the reference's own blocks by tests/golden/unet_blocks.part*.npz): output, input gradient and every parameter
     gradient of the layer.  (Batch 2; the SpatialTransformer at batch 1: the oracle's 16 x 5 x 2560 x 2560 score tensors.)"""
     _block_case(dev, kind, full=True)
 

@@ -1,6 +1,6 @@
 """HunyuanVideo denoiser at the shipped recipe's sequence, whole model, LoRA: the backward predicts its own forward (no oracle reaches this
-size).  Kept in a file of its own that sorts last: the property is measured on a loss change of 1.4e-4 of the loss, the one test of the suite
-whose margin is set by rounding noise, and the driver runs the suite with -x."""
+size).  Kept in a file of its own that sorts last: its margin is set by the rounding noise of a bf16 forward, and the driver runs the
+suite with -x."""
 import pytest
 import torch
 
@@ -13,7 +13,7 @@ def test_denoiser_at_the_shipped_sequence_lora_backward_predicts_its_own_forward
     width 3072, 24 heads of 128) through HunyuanVideoFlow.training_step with a REDUCED DEPTH (3 double + 5 single blocks of 20 + 40: the
     12.8 B-parameter trunk takes minutes to initialise) -- every kernel at its production shape, the embedders, token refiner and final
     layer included.  Property (no oracle reaches this size): the adapter gradient predicts the forward.  For each of four adapter groups a
-    random subset of the weights is moved along the group's own gradient by a few bf16 ulps;  L(w+) - L(w-)  must equal  <g, w+ - w->."""
+    random subset of the weights is moved along the group's own gradient by 30 % of its RMS;  L(w+) - L(w-)  must equal  <g, w+ - w->."""
     from vt355.hunyuan import HYVideoDiffusionTransformer, HunyuanVideoFlow
     model = HYVideoDiffusionTransformer(mm_double_blocks_depth=3, mm_single_blocks_depth=5, lora_rank=4).to(dev).init_weights(11)
     model.lora.init_weights(12, zero_b=False)
@@ -39,7 +39,9 @@ def test_denoiser_at_the_shipped_sequence_lora_backward_predicts_its_own_forward
     grad = ts.grad.clone()
     assert torch.isfinite(grad).all() and grad.abs().max().item() > 0
     L0 = L()
-    assert abs(L0 - loss.item()) <= 1e-6 * abs(L0)
+    # the no-grad path draws the same sigma / noise and computes the same loss; the forward is not bit-repeatable (the LoRA down-projection
+    # and split-K GEMMs accumulate in fp32 atomics): repeats measured 4e-7 apart, once 1.6e-6; a different draw is off by percents
+    assert abs(L0 - loss.item()) <= 1e-5 * abs(L0)
     groups = {"double A": [], "double B": [], "single A": [], "single B": []}
     for n in model.lora.shapes:
         groups[("double" if n.startswith("double_blocks") else "single") + (" A" if ".lora_A" in n else " B")].append(n)
@@ -54,7 +56,7 @@ def test_denoiser_at_the_shipped_sequence_lora_backward_predicts_its_own_forward
             gn = gv.float().pow(2).mean().sqrt()
             if gn > 0:
                 model.lora._view(d, n).copy_(gv * (wv.float().pow(2).mean().sqrt() / gn))
-        eps = 0.03
+        eps = 0.3           # the loss change grows with eps, the bf16 rounding noise of L() does not (eps 0.03: a change of 1.4e-4 of the loss)
         pred_full = eps * (grad.double() * d.double()).sum().item()
         rho = min(1.0, 0.01 * abs(L0) / max(pred_full, 1e-30))
         d = d * (torch.rand(d.shape, device=dev, generator=dgen) < rho)
@@ -67,8 +69,9 @@ def test_denoiser_at_the_shipped_sequence_lora_backward_predicts_its_own_forward
         predicted = (grad.double() * (vals[+1][1] - vals[-1][1]).double()).sum().item()
         report.append((k, len(names), measured, predicted))
     print(f"[hunyuan 10 456 tokens, 3 + 5 blocks] loss {L0:.5f}; " + "; ".join(f"{k} ({n} tensors): dL {a:.4e} vs <g, dw> {b:.4e}" for k, n, a, b in report))
-    # all adapters moved (the subset is everything): the change is 1.4e-4 of the loss, near the rounding of a bf16 forward -- measured
-    # deviations 2-8 % over many runs with one outlier above 15 % (run-to-run: the gradient's fp32 atomics and the loss's own rounding), so the
-    # bar is 25 %; a wrong gradient (a missing adapter, a lost scaling) is off by factors, not by tens of percent
+    # all adapters moved (the subset is everything).  Measured deviation per group against eps, same seeds: 0.03 -> 2-6.5 % (a change of
+    # 1.4e-4 of the loss, near the rounding of a bf16 forward; one outlier above 15 % seen), 0.1 -> <= 1.5 %, 0.3 -> <= 1.1 %, 1.0 -> up to
+    # 4 % (third-order terms); the forward repeats to 4e-7 of the loss, the gradient to 8e-8.  A wrong gradient (a missing adapter, a lost
+    # scaling) is off by factors
     for k, n, a, b in report:
-        assert b > 0 and abs(a - b) <= 0.25 * b, (k, a, b)
+        assert b > 0 and abs(a - b) <= 0.10 * b, (k, a, b)
