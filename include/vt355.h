@@ -386,6 +386,28 @@ int vt_gemm_fp8(const void* A, int lda, const void* W, int ldw, void* C, int ldc
 int vt_quantize_fp8(const void* x, long long ldx, void* y, long long ldy, long long M, int K, float* scale, unsigned int* ws,
                     int given_scale, void* stream);
 
+/* MX-scaled FP8 GEMM and delayed per-tensor scaling (csrc/gemm_mxfp8.hip; HunyuanVideo fp8="mfma").
+ * vt_gemm_mxfp8: C = epilogue((Aq Wq^T) * scale_a * scale_w [+ At Wt^T] + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3, unit block
+ * scales); epilogue EPI_BIAS / EPI_BIAS_GELU / EPI_GATED_RES with the operands of vt_gemm_bf16; optional bf16 tail At [M, Kt], Wt [N, Kt]
+ * (Kt 0, 32 or 64); optional e4m3 copy Cq = e4m3(C / scale_out) with max |C| into amax.  K % 128 == 0, N % 4 == 0; scales on the device.
+ * vt_cast_fp8_scaled: x bf16 -> e4m3 with a device scale, max |x| into amax; row m reads x row (m / L) * Lj + off + m % L (L = 0: m) and
+ * is optionally copied (bf16) to cp.  vt_ln_modulate_fwd_fp8: vt_ln_modulate_fwd plus an e4m3 copy of y and its amax.
+ * vt_fp8_scale_update: per site, history [n, H] <- (amax, history[:, :-1]), scale = max(history) / 448 (1 if 0), amax cleared.
+ * amax slots are uint32 holding non-negative float bits. */
+int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias,
+                  const float* scale_a, const float* scale_w, int epilogue, const void* residual, int ldr,
+                  const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St, void* pre_act_out, int ldc2,
+                  const void* At, int ldat, const void* Wt, int ldwt, int Kt, void* Cq, int ldcq, const float* scale_out,
+                  unsigned int* amax, void* stream);
+int vt_cast_fp8_scaled(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
+                       int Lj, int off, const float* scale, unsigned int* amax, void* stream);
+int vt_ln_modulate_fwd_fp8(const void* x, int ldx, void* y, int ldy, const void* gamma, const void* beta,
+                           const float* shift_txt, const float* scale_txt, const float* shift_vid,
+                           const float* scale_vid, int mod_bstride, float* mean, float* rstd,
+                           int M, int D, int S, int St, float eps, void* q, int ldq, const float* qscale, unsigned int* amax,
+                           void* stream);
+int vt_fp8_scale_update(unsigned int* amax, float* history, float* scale, int n, int H, void* stream);
+
 /* HunyuanVideo q/k preparation, head_dim 128 (csrc/qknorm128.hip): per-head RMSNorm(eps, weight [128]) of the q and k thirds of a fused
  * [M, 3*H*128] projection, rotary embedding of the first S_rope positions of every sample (image tokens; cos / sin fp32 [S_rope, 128] | NULL),
  * and the scatter of q^ | k^ | v into the joint [image; text] sequence: out row = (m / L) * Lout + row_off + m % L.  rstd fp32 [M, 2H].

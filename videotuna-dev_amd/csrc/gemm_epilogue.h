@@ -68,9 +68,10 @@ __device__ __forceinline__ GateCtx gate_ctx_load(const GemmParams& p, int row0, 
 
 // v = accumulators of (row m, columns n..n+3), bias4 = bias of those columns (zeros if none).  Caller guarantees
 // m < M and n < N (N % 4 == 0).
-template <int EPI, bool OUT_F32>
-__device__ __forceinline__ void gemm_epilogue_store_aux(const GemmParams& p, int m, int n, f32x4 v, const float* bias4, u32x2 aux,
-                                                        const GateCtx* gc = nullptr) {
+// The arithmetic of the epilogue: o = epilogue(v + bias4) of (row m, columns n..n+3), the second output (C2) written here.
+template <int EPI>
+__device__ __forceinline__ f32x4 gemm_epilogue_apply(const GemmParams& p, int m, int n, f32x4 v, const float* bias4, u32x2 aux,
+                                                     const GateCtx* gc) {
                 float o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = v[j] + bias4[j];
@@ -118,6 +119,14 @@ __device__ __forceinline__ void gemm_epilogue_store_aux(const GemmParams& p, int
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = o[j] * gelu_tanh_grad_f(u[j]);
                 }
+                return (f32x4){o[0], o[1], o[2], o[3]};
+}
+
+template <int EPI, bool OUT_F32>
+__device__ __forceinline__ void gemm_epilogue_store_aux(const GemmParams& p, int m, int n, f32x4 v, const float* bias4, u32x2 aux,
+                                                        const GateCtx* gc = nullptr) {
+                const f32x4 r = gemm_epilogue_apply<EPI>(p, m, n, v, bias4, aux, gc);
+                const float o[4] = {r[0], r[1], r[2], r[3]};
                 if (OUT_F32) {
                     if (p.splits > 1) {            // split-K partial tile: C was zeroed by the host entry point
                         float* c = (float*)p.C + (size_t)m * p.ldc + n;

@@ -4,7 +4,8 @@
 // the double / single stream block weights as E4M3 with a per-tensor scale (scale = max|W| / 448, :58-60), de-quantises them to bf16 and
 // calls F.linear.  BASELINE's north_star asks for the real thing (configs[4]): here the weight stays E4M3 in HBM (half
 // the bytes), the activation is quantised per tensor on the fly (one amax pass + one cast pass) and the product runs on
-// v_mfma_f32_16x16x32_fp8_fp8 at twice the bf16 rate; the two scales are applied to the fp32 accumulators in the epilogue.
+// v_mfma_f32_16x16x32_fp8_fp8, which on gfx950 runs at the bf16 rate (the gain is the halved staging bytes; the block-scaled
+// instruction of gemm_mxfp8.hip reaches twice the bf16 rate); the two scales are applied to the fp32 accumulators in the epilogue.
 //
 // Kernel: the 128x128 tile / LDS-DMA staging / XOR-swizzled 128-byte rows of gemm_bf16.hip; a K-tile is 128 bytes per row = 128 fp8
 // elements = four 32-wide MFMA k-steps (an 8-byte fragment per lane and k-step).  K % 128 == 0, N % 4 == 0.

@@ -21,9 +21,11 @@ struct LnParams {
     float* mean; float* rstd;
     int M, D, S, St;
     float eps;
+    unsigned char* q; int ldq; const float* qscale; unsigned int* amax;    // Q: e4m3 copy of y (vt_ln_modulate_fwd_fp8)
 };
 
-template <int NCH>
+// Q = true: also q = satfinite(RNE(y_bf16 / qscale[0])) and max |y_bf16| into amax (the bf16 output is the same as with Q = false)
+template <int NCH, bool Q = false>
 __global__ __launch_bounds__(256) void ln_modulate_fwd_kernel(LnParams p) {
     const int lane = threadIdx.x & 63;
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -65,6 +67,7 @@ __global__ __launch_bounds__(256) void ln_modulate_fwd_kernel(LnParams p) {
         scp = (s < p.St ? p.scale_txt : p.scale_vid) + (size_t)b * p.mod_bstride;
     }
     bf16_t* yr = p.y + (size_t)m * p.ldy;
+    float qmax = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         const int c = lane + 64 * i;
@@ -90,8 +93,33 @@ __global__ __launch_bounds__(256) void ln_modulate_fwd_kernel(LnParams p) {
                     o[j + 4] = o[j + 4] * (1.f + s1[j]) + h1[j];
                 }
             }
-            *(u32x4*)(yr + c * 8) = pack8(o);
+            const u32x4 packed = pack8(o);
+            *(u32x4*)(yr + c * 8) = packed;
+            if constexpr (Q) {
+                float b[8];
+                unpack8(packed, b);
+                const float qs = p.qscale[0];
+                unsigned int w[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    float t[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        qmax = fmaxf(qmax, fabsf(b[4 * h + j]));
+                        t[j] = fminf(fmaxf(__fdiv_rn(b[4 * h + j], qs), -448.0f), 448.0f);
+                    }
+                    int r = 0;
+                    r = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], r, false);
+                    r = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], r, true);
+                    w[h] = (unsigned int)r;
+                }
+                *(u32x2*)(p.q + (size_t)m * p.ldq + c * 8) = (u32x2){w[0], w[1]};
+            }
         }
+    }
+    if constexpr (Q) {
+        qmax = wave_max(qmax);
+        if (lane == 0) atomicMax(p.amax, __float_as_uint(qmax));
     }
 }
 
@@ -191,6 +219,31 @@ extern "C" int vt_ln_modulate_fwd(const void* x, int ldx, void* y, int ldy, cons
     if (nch <= 1) hipLaunchKernelGGL(ln_modulate_fwd_kernel<1>, grid, block, 0, st, p);
     else if (nch <= 4) hipLaunchKernelGGL(ln_modulate_fwd_kernel<4>, grid, block, 0, st, p);
     else hipLaunchKernelGGL(ln_modulate_fwd_kernel<8>, grid, block, 0, st, p);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
+// vt_ln_modulate_fwd plus an e4m3 copy q [M, ldq] of y with the device scale qscale[0] and max |y| into amax (uint32 float bits,
+// accumulated): the quantised input of the Linear that reads y (delayed scaling, vt_gemm_mxfp8).  y is the same as vt_ln_modulate_fwd's.
+extern "C" int vt_ln_modulate_fwd_fp8(const void* x, int ldx, void* y, int ldy, const void* gamma, const void* beta,
+                                      const float* shift_txt, const float* scale_txt, const float* shift_vid,
+                                      const float* scale_vid, int mod_bstride, float* mean, float* rstd,
+                                      int M, int D, int S, int St, float eps, void* q, int ldq, const float* qscale, unsigned int* amax,
+                                      void* stream) {
+    if (M <= 0 || D <= 0 || (D % 8) || D > 4096 || (ldx % 8) || (ldy % 8) || (ldq % 8) || ldq < D) return VT_ERR_BAD_SHAPE;
+    if (q == nullptr || qscale == nullptr || amax == nullptr) return VT_ERR_BAD_SHAPE;
+    if ((gamma == nullptr) != (beta == nullptr)) return VT_ERR_BAD_SHAPE;
+    if (shift_vid != nullptr && (shift_txt == nullptr || scale_txt == nullptr || scale_vid == nullptr || (mod_bstride % 4)))
+        return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)x) | ((uintptr_t)y)) & 15 || (((uintptr_t)q) & 7)) return VT_ERR_BAD_ALIGN;
+    LnParams p{(const bf16_t*)x, ldx, (bf16_t*)y, ldy, (const bf16_t*)gamma, (const bf16_t*)beta,
+               shift_txt, scale_txt, shift_vid, scale_vid, mod_bstride, mean, rstd, M, D, S > 0 ? S : 1, St, eps,
+               (unsigned char*)q, ldq, qscale, amax};
+    dim3 grid((M + 3) / 4), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const int nch = nch_for(D);
+    if (nch <= 1) hipLaunchKernelGGL((ln_modulate_fwd_kernel<1, true>), grid, block, 0, st, p);
+    else if (nch <= 4) hipLaunchKernelGGL((ln_modulate_fwd_kernel<4, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((ln_modulate_fwd_kernel<8, true>), grid, block, 0, st, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 

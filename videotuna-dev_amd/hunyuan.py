@@ -13,6 +13,13 @@ proj, the MLPs, linear1 / linear2, the modulation Linears -- holds its weight as
 ``F.linear(x, dequant(W))`` in bf16; here the de-quantised bf16 copies are the GEMM operands (forward and dX), built once per weight version.
 ``fp8="matmul"`` additionally runs the qkv projections' forward on the fp8 matrix cores (vt_gemm_fp8, activations quantised per tensor on
 the fly -- beyond the reference, which never quantises activations); gradients stay bf16.
+``fp8="mfma"`` runs the FORWARD product of every double / single block Linear (qkv, proj, fc1, fc2, both row ranges of linear1, linear2;
+not the modulation Linears) on the MX-scaled fp8 matrix cores (vt_gemm_mxfp8): E4M3 weights with their per-tensor scale as above, E4M3
+activations with a per-site DELAYED scale (max of the last ``fp8_amax_history`` recorded amaxes / 448, fixed for a forward, updated by one
+vt_fp8_scale_update launch at its start).  The producer of each quantised input writes the fp8 copy next to its bf16 output (LayerNorm +
+modulate, the fc1 / linear1 GELU epilogue, the attention-output split); the first forward (and the first after load_state_dict or a change
+of ``fp8``) has no history and scales just in time.  LoRA sites keep their K-extension columns in bf16 (the GEMM's bf16 tail).  The
+backward is that of ``"weights"`` mode: bf16, from the saved bf16 activations and the de-quantised weights.
 
 NOT built (recorded in DESIGN.md): the embedders / token refiner / final layer of HYVideoDiffusionTransformer, the diffusers
 ``HunyuanVideoTransformer3DModel`` key map and LoRA wrappers of the shipped recipe, (the head_dim-128 attention backward is atomics-only: no dQ hand-off chains yet).  Padding text rows attend to the valid keys here
@@ -108,11 +115,14 @@ class HunyuanBlocks(FlatParamModule):
 
     def __init__(self, hidden_size: int = 3072, heads_num: int = 24, mlp_width_ratio: float = 4.0, mm_double_blocks_depth: int = 20,
                  mm_single_blocks_depth: int = 40, fp8: bool = False, lora_rank: int = 0, lora_alpha: float = 1.0,
-                 shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None):
+                 shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None, fp8_amax_history: int = 16):
         super().__init__()
         if hidden_size // heads_num != 128 or hidden_size % 128:
             raise ValueError("HunyuanVideo heads are 128 wide")
+        if fp8_amax_history < 1:
+            raise ValueError("fp8_amax_history: at least one recorded amax")
         self.hidden_size, self.heads_num, self.ratio = hidden_size, heads_num, mlp_width_ratio
+        self.fp8_amax_history = fp8_amax_history
         self.n_double, self.n_single, self.fp8 = mm_double_blocks_depth, mm_single_blocks_depth, fp8
         sh: Dict[str, tuple] = {}
         for i in range(mm_double_blocks_depth):
@@ -123,6 +133,44 @@ class HunyuanBlocks(FlatParamModule):
         # LoRA mode: the block weights stay frozen (no fp32 master, no gradients, no dW GEMMs); only the adapters train
         self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha) if lora_rank > 0 else None
         self.sp_group = None
+
+    @property
+    def fp8(self):
+        return self._fp8
+
+    @fp8.setter
+    def fp8(self, mode):
+        if mode not in (False, True, "weights", "matmul", "mfma"):
+            raise ValueError(f"fp8={mode!r}: one of False, True / 'weights', 'matmul', 'mfma'")
+        if mode == "mfma" and (self.hidden_size % 128 or int(self.hidden_size * self.ratio) % 128):
+            raise ValueError(f"fp8='mfma': the MX-fp8 GEMM needs every block Linear's input width (hidden_size {self.hidden_size}, MLP width "
+                             f"{int(self.hidden_size * self.ratio)}) to be a multiple of 128")
+        self._fp8 = mode
+        self.fp8_reset()
+
+    @property
+    def n_fp8_sites(self) -> int:
+        """activation sites of fp8='mfma': per double block and stream the qkv / proj / fc1 / fc2 inputs, per single block linear1 / linear2"""
+        return 8 * self.n_double + 2 * self.n_single
+
+    def fp8_reset(self):
+        """forget the delayed-scaling history: the next fp8='mfma' forward scales just in time and seeds it"""
+        self._fp8_state = None
+
+    def fp8_state(self):
+        """(amax, history, scale) device tensors of the activation sites, created (unseeded) on first use"""
+        st = self._fp8_state
+        if st is None or st.amax.device != self.device:
+            n, H = self.n_fp8_sites, self.fp8_amax_history
+            st = SimpleNamespace(amax=torch.zeros(n, dtype=F32, device=self.device), history=torch.zeros(n, H, dtype=F32, device=self.device),
+                                 scale=torch.ones(n, dtype=F32, device=self.device), seeded=False)
+            self._fp8_state = st
+        return st
+
+    def load_state_dict(self, sd, strict: bool = True, **kw):
+        out = super().load_state_dict(sd, strict=strict, **kw)
+        self.fp8_reset()
+        return out
 
     def set_sequence_parallel(self, group):
         """Ulysses sequence parallelism over ``group`` (vt355.sp; SURVEY 8(e), the 119 k-token 720p sequence): ``img`` and ``freqs_cis`` passed
@@ -189,6 +237,9 @@ class _HYFn(torch.autograd.Function):
         return None, None, dimg, dtxt, dvec, None, None
 
 
+_MFMA_LINEARS = ("_attn_qkv.weight", "_attn_proj.weight", "_mlp.fc1.weight", "_mlp.fc2.weight", "linear1.weight", "linear2.weight")
+
+
 def _packed_hy(model: HunyuanBlocks) -> SimpleNamespace:
     ver = -1 if model.train_state is None else model.train_state.version
     if model._packed is not None and model._packed_version == ver:
@@ -204,8 +255,8 @@ def _packed_hy(model: HunyuanBlocks) -> SimpleNamespace:
                     wq, sw = ops.quantize_fp8(w)
                     w = (wq.to(torch.float32) * sw).to(BF16)        # ... and what the reference multiplies with: dequant(W) (:50-53, 72-78)
                     P.w[n] = w
-                    if model.fp8 == "matmul" and n.endswith("_attn_qkv.weight"):
-                        P.q[n] = (wq, sw)
+                    if (model.fp8 == "matmul" and n.endswith("_attn_qkv.weight")) or (model.fp8 == "mfma" and n.endswith(_MFMA_LINEARS)):
+                        P.q[n] = (wq, sw)               # mfma: linear1's two row ranges share the tensor's one scale
                 if (model.train_state is not None or (model.lora is not None and model.lora.train_state is not None)) and not lora_site:
                     P.wt[n] = ops.transpose(w)
     model._packed, model._packed_version = P, ver
@@ -319,6 +370,42 @@ class _HYRun(_STRun):
         if self.sp is not None:
             import torch.distributed as dist
             self.spP = dist.get_world_size(self.sp)
+        self.q8 = model.fp8 == "mfma"   # fp8="mfma": block Linears' forward on vt_gemm_mxfp8
+        self.q8s = None                 # (amax, history, scale) of the activation sites, set by forward()
+        self.jit = False                # no history yet: every site scales just in time
+
+    # ---- fp8="mfma": activation sites and their delayed scales ----
+    def qsite(self, site):
+        """(scale, amax) of activation site `site`: 1-element device views.  Within a forward the scale is fixed"""
+        st = self.q8s
+        return st.scale[site:site + 1], st.amax[site:site + 1]
+
+    def steady(self, site):
+        """(scale, amax) for a PRODUCER to write the site's fp8 copy with, or None when the site scales just in time"""
+        return None if (site is None or self.jit) else self.qsite(site)
+
+    def fp8_in(self, site, x, xq=None, copy=None, rows=None, M=None):
+        """the e4m3 input of site `site`: xq when its producer already wrote it, else cast from the bf16 x (rows / copy: vt_cast_fp8_scaled's
+        row map and bf16 copy).  Just in time (no history): an amax pass, the site's scale from that amax (which seeds its history), the cast"""
+        if xq is not None:
+            return xq
+        scale, amax = self.qsite(site)
+        y = torch.empty(x.shape[0] if M is None else M, x.shape[1], dtype=ops.FP8, device=self.dev)
+        if self.jit:
+            ops.cast_fp8_scaled(x, y, scale, amax, copy=copy, rows=rows)
+            st = self.q8s
+            ops.fp8_scale_update(amax, st.history[site:site + 1], scale)
+            copy = None
+        ops.cast_fp8_scaled(x, y, scale, amax, copy=copy, rows=rows)
+        return y
+
+    def mx_gemm(self, xq, site, wname, y, bias, rows=None, **epi):
+        """y = epilogue((xq Wq^T) sa sw + bias) on vt_gemm_mxfp8; rows = (lo, hi): that row range of the weight (linear1)"""
+        wq, sw = self.P.q[wname]
+        if rows is not None:
+            wq = wq[rows[0]:rows[1]]
+        ops.gemm_mxfp8(xq, wq, y, self.qsite(site)[0], sw, bias, **epi)
+        return y
 
     def W(self, name):
         """the parameter view, or in fp8 mode the de-quantised E4M3 copy of a block Linear's weight (biases / norm weights stay bf16)"""
@@ -349,16 +436,21 @@ class _HYRun(_STRun):
         """activation buffer of an adapted Linear's input: [M, D + EXT], the Linear reads all of it, producers write [:, :D]"""
         return self.E(M, self.m.hidden_size + EXT)
 
-    def lora_linear(self, xe, mod: str, bias, y=None, **epi):
+    def lora_linear(self, xe, mod: str, bias, y=None, q8=None, **epi):
         """y = [x | x A3^T] W_ext^T + bias (+ epilogue) for the adapted Linear `mod`; xe: ext buffer whose [:, :D] holds x.  Returns
-        (y, backward(g) -> dx [M, D]) -- the caller decides what g is (gated or not) and where dx goes."""
+        (y, backward(g) -> dx [M, D]) -- the caller decides what g is (gated or not) and where dx goes.  q8 = (xq, site, wname, rows):
+        the base product x W^T on vt_gemm_mxfp8 from the e4m3 input, the extension columns as its bf16 tail."""
         D = self.m.hidden_size
         M = xe.shape[0]
         wext, a3 = self.LP.wext[mod], self.LP.a3[mod]
         ops.gemm(xe[:, :D], a3, xe[:, D:], None, K=D)                  # t = x A3^T into the extension columns
         if y is None:
             y = self.E(M, wext.shape[0])
-        ops.gemm(xe, wext, y, bias, **epi)
+        if q8 is not None:
+            xq, site, wname, rows = q8
+            self.mx_gemm(xq, site, wname, y, bias, rows=rows, tail=(xe[:, D:], wext[:, D:]), **epi)
+        else:
+            ops.gemm(xe, wext, y, bias, **epi)
 
         def backward(g):
             L, r = self.lora, self.lora.r
@@ -407,7 +499,7 @@ class _HYRun(_STRun):
             GA.index_add_(0, P.idx1, P.DA[n3:, :r])
         self._lora_ran.clear()
 
-    def linear(self, x: _Var, wname: str, bname, residual=None, wspan=None, out=None) -> _Var:
+    def linear(self, x: _Var, wname: str, bname, residual=None, wspan=None, out=None, site=None, xq=None) -> _Var:
         """block Linear without epilogue (the qkv projections).  Adapted module (LoRA): one GEMM over the K-extended operands.  fp8=True: the
         FORWARD product on the fp8 matrix cores (activation quantised per tensor here, weight copy + scale from _packed_hy).  Parameter
         gradients only when the block weights train."""
@@ -415,8 +507,11 @@ class _HYRun(_STRun):
         mod = wname[:-7]
         M = x.d.shape[0]
         b = None if bname is None else self.W(bname)
+        mx = self.q8 and wname in self.P.q
+        if mx:
+            xq = self.fp8_in(site, x.d, xq)
         if self.lora is not None and mod in self.lora.sites:
-            y, bw = self.lora_linear(x.ext, mod, b)
+            y, bw = self.lora_linear(x.ext, mod, b, q8=(xq, site, wname, None) if mx else None)
             yv = _Var(y)
             if self.save:
                 def bwd_linear_lora():
@@ -426,7 +521,9 @@ class _HYRun(_STRun):
             return yv
         w = self.W(wname)
         y = self.E(M, w.shape[0])
-        if self.m.fp8 and wname in self.P.q:
+        if mx:
+            self.mx_gemm(xq, site, wname, y, b)
+        elif self.m.fp8 and wname in self.P.q:
             wq, sw = self.P.q[wname]
             xq, sa = ops.quantize_fp8(x.d)
             ops.gemm_fp8(xq, wq, y, sa, sw, b)
@@ -444,16 +541,25 @@ class _HYRun(_STRun):
             self.tape.append(bwd_linear)
         return yv
 
-    def ln_mod(self, x: _Var, shift, scale, bstride: int, rows_per_sample: int, dshift, dscale, dbstride: int, ext: bool = False) -> _Var:
-        """as _STRun.ln_mod; ext=True: the result is written into the first D columns of an extended buffer (input of an adapted Linear)"""
-        if not ext:
-            return super().ln_mod(x, shift, scale, bstride, rows_per_sample, dshift, dscale, dbstride)
+    def ln_mod(self, x: _Var, shift, scale, bstride: int, rows_per_sample: int, dshift, dscale, dbstride: int, ext: bool = False, site=None):
+        """as _STRun.ln_mod; ext=True: the result is written into the first D columns of an extended buffer (input of an adapted Linear).
+        site given (fp8="mfma"): returns (y, yq) -- yq the e4m3 copy of y for that activation site (None while it scales just in time)"""
+        q = self.steady(site) if self.q8 else None
+        if not ext and q is None:
+            yv = super().ln_mod(x, shift, scale, bstride, rows_per_sample, dshift, dscale, dbstride)
+            return yv if site is None else (yv, None)
         M, D = x.d.shape
-        buf = self.ext(M)
-        y = buf[:, :D]
+        buf = self.ext(M) if ext else None
+        y = buf[:, :D] if ext else self.E(M, D)
         mean, rstd = self.E(M, dt=F32), self.E(M, dt=F32)
-        ops.ln_modulate_fwd(x.d, y, None, None, (shift, scale, shift, scale, bstride), mean, rstd, D, rows_per_sample, 0, 1e-6)
-        yv = _XVar(y, buf)
+        yq = None
+        if q is not None:
+            yq = torch.empty(M, D, dtype=ops.FP8, device=self.dev)
+            ops.ln_modulate_fwd_fp8(x.d, y, None, None, (shift, scale, shift, scale, bstride), mean, rstd, D, rows_per_sample, 0, 1e-6,
+                                    yq, q[0], q[1])
+        else:
+            ops.ln_modulate_fwd(x.d, y, None, None, (shift, scale, shift, scale, bstride), mean, rstd, D, rows_per_sample, 0, 1e-6)
+        yv = _XVar(y, buf) if ext else _Var(y)
         if self.save:
             def bwd_ln_mod_ext():
                 g = yv.g
@@ -464,19 +570,30 @@ class _HYRun(_STRun):
                 ops.ln_modulate_bwd(g, x.d, mean, rstd, None, (scale, scale, bstride), x.g, dx, D, rows_per_sample, 0)
                 x.g = dx
             self.tape.append(bwd_ln_mod_ext)
-        return yv
+        return yv if site is None else (yv, yq)
 
-    def mlp(self, x: _Var, pre: str, residual=None, gate=None, dgate=None) -> _Var:
-        """_STRun.mlp with the parameter gradients behind the frozen-weights switch"""
+    def mlp(self, x: _Var, pre: str, residual=None, gate=None, dgate=None, sites=None, xq=None) -> _Var:
+        """_STRun.mlp with the parameter gradients behind the frozen-weights switch; fp8="mfma": sites = (fc1 input, fc2 input), xq the
+        e4m3 fc1 input (or None), the GELU epilogue of fc1 writing fc2's e4m3 input"""
         M = x.d.shape[0]
         w1, w2 = self.W(pre + "fc1.weight"), self.W(pre + "fc2.weight")
         H4, Dout = w1.shape[0], w2.shape[0]
         u = self.E(M, H4); ga = self.E(M, H4)
-        ops.gemm(x.d, w1, ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u)
         y = self.E(M, Dout)
         branch = self.E(M, Dout) if (self.save and dgate is not None) else None          # the pre-gate branch: only d(gate) reads it
-        ops.gemm(ga, w2, y, self.W(pre + "fc2.bias"), epilogue=EPI_GATED_RES, residual=residual.d, gate_txt=gate[0], gate_vid=gate[0],
-                 gate_bstride=gate[1], S=gate[2], St=0, pre_act_out=branch)
+        epi2 = dict(epilogue=EPI_GATED_RES, residual=residual.d, gate_txt=gate[0], gate_vid=gate[0], gate_bstride=gate[1], S=gate[2], St=0,
+                    pre_act_out=branch)
+        if self.q8:
+            s1, s2 = sites
+            q2 = self.steady(s2)
+            gq = None if q2 is None else torch.empty(M, H4, dtype=ops.FP8, device=self.dev)
+            self.mx_gemm(self.fp8_in(s1, x.d, xq), s1, pre + "fc1.weight", ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u,
+                         out_fp8=None if q2 is None else (gq, q2[0], q2[1]))
+            self.mx_gemm(self.fp8_in(s2, ga, gq), s2, pre + "fc2.weight", y, self.W(pre + "fc2.bias"), **epi2)
+            del gq
+        else:
+            ops.gemm(x.d, w1, ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u)
+            ops.gemm(ga, w2, y, self.W(pre + "fc2.bias"), **epi2)
         yv = _Var(y)
         if self.save:
             def bwd_mlp():
@@ -510,8 +627,9 @@ class _HYRun(_STRun):
             self.tape.append(bwd_modulation)
         return mod, dmod
 
-    def glinear(self, x: _Var, wname: str, bname: str, residual: _Var, gate, dgate, rps: int, bs: int) -> _Var:
-        """y = residual + gate[b] * (x W^T + b)   (apply_gate, modulate_layers.py:49-66); adapted module: over the K-extended operands"""
+    def glinear(self, x: _Var, wname: str, bname: str, residual: _Var, gate, dgate, rps: int, bs: int, site=None, xq=None) -> _Var:
+        """y = residual + gate[b] * (x W^T + b)   (apply_gate, modulate_layers.py:49-66); adapted module: over the K-extended operands.
+        fp8="mfma": the product from the e4m3 input xq of activation site `site`"""
         mod = wname[:-7]
         adapted = self.lora is not None and mod in self.lora.sites
         w = self.W(wname)
@@ -520,8 +638,11 @@ class _HYRun(_STRun):
         branch = self.E(M, N) if (self.save and dgate is not None) else None           # the pre-gate branch: only d(gate) reads it
         epi = dict(epilogue=EPI_GATED_RES, residual=residual.d, gate_txt=gate, gate_vid=gate, gate_bstride=bs, S=rps, St=0, pre_act_out=branch)
         bw = None
+        mx = self.q8 and wname in self.P.q
         if adapted:
-            y, bw = self.lora_linear(x.ext, mod, self.W(bname), y=y, **epi)
+            y, bw = self.lora_linear(x.ext, mod, self.W(bname), y=y, q8=(xq, site, wname, None) if mx else None, **epi)
+        elif mx:
+            self.mx_gemm(xq, site, wname, y, self.W(bname), **epi)
         else:
             ops.gemm(x.d, w, y, self.W(bname), **epi)
         yv = _Var(y)
@@ -602,31 +723,45 @@ class _HYRun(_STRun):
         return ov
 
     # ------------------------------------------------------------------------------------------------------------------
-    def double_block(self, pre: str, img: _Var, txt: _Var, sv: _Var, B, Li, Lt, kv_len, rope):
+    def double_block(self, pre: str, img: _Var, txt: _Var, sv: _Var, B, Li, Lt, kv_len, rope, site0: int = 0):
+        """site0: the first of this block's 8 fp8 activation sites (per stream img, txt: qkv, proj, fc1, fc2 inputs)"""
         D, H = self.m.hidden_size, self.m.heads_num
         C, Lj = D, Li + Lt
         bs = 6 * D
         joint = self.E(B * Lj, 3 * C)                         # every row is written by the two scatters below
         dj = [None]
         streams = {}
-        for s, x, L, off, rp in (("img", img, Li, 0, rope), ("txt", txt, Lt, Li, None)):
+        q8 = self.q8
+        for si, (s, x, L, off, rp) in enumerate((("img", img, Li, 0, rope), ("txt", txt, Lt, Li, None))):
             mod, dmod = self.modulation(sv, pre + s + "_mod", 6)
             sl = lambda k, buf=mod: buf[:, k * D:(k + 1) * D]
             dsl = (lambda k, buf=dmod: buf[:, k * D:(k + 1) * D]) if dmod is not None else (lambda k: None)
             adapted = self.lora is not None and s == "img"
-            xm = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted)
-            qkv = self.linear(xm, pre + s + "_attn_qkv.weight", pre + s + "_attn_qkv.bias")
-            streams[s] = (x, L, off, sl, dsl, qkv, rp)
+            qs = site0 + 4 * si                                                     # this stream's qkv / proj / fc1 / fc2 input sites
+            if q8:
+                xm, xq = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted, site=qs)
+                qkv = self.linear(xm, pre + s + "_attn_qkv.weight", pre + s + "_attn_qkv.bias", site=qs, xq=xq)
+                del xq
+            else:
+                xm = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted)
+                qkv = self.linear(xm, pre + s + "_attn_qkv.weight", pre + s + "_attn_qkv.bias")
+            streams[s] = (x, L, off, sl, dsl, qkv, rp, qs)
         # the backward of the scatter must run AFTER the attention's backward has produced the joint gradient: push order = forward order
         for s in ("img", "txt"):
-            x, L, off, sl, dsl, qkv, rp = streams[s]
+            x, L, off, sl, dsl, qkv, rp, qs = streams[s]
             self.qkv_to_joint(qkv, pre + s + "_attn_q_norm.weight", pre + s + "_attn_k_norm.weight", joint, dj, L, Lj, off, rp)
         o = self.E(B * Lj, C)
         ov = self.joint_attention(joint, B, Lj, kv_len, o, dj)
         outs = {}
         for s in ("img", "txt"):
-            x, L, off, sl, dsl, qkv, rp = streams[s]
-            if self.lora is not None and s == "img":                                 # input of the adapted projection: extended buffer
+            x, L, off, sl, dsl, qkv, rp, qs = streams[s]
+            aq = None
+            if q8:                          # this stream's rows of the joint output: the bf16 copy and the e4m3 proj input in one pass
+                ae = self.ext(B * L) if (self.lora is not None and s == "img") else None
+                ad = ae[:, :C] if ae is not None else self.E(B * L, C)
+                aq = self.fp8_in(qs + 1, o, copy=ad, rows=(L, Lj, off), M=B * L)
+                av = _XVar(ad, ae) if ae is not None else _Var(ad)
+            elif self.lora is not None and s == "img":                               # input of the adapted projection: extended buffer
                 ae = self.ext(B * L)
                 ae.view(B, L, C + EXT)[:, :, :C].copy_(o.view(B, Lj, C)[:, off:off + L])
                 av = _XVar(ae[:, :C], ae)
@@ -638,12 +773,19 @@ class _HYRun(_STRun):
                         ov.g = self.E(B * Lj, C)              # both streams' splits fill all of it
                     ov.g.view(B, Lj, C)[:, off:off + L].copy_(av.g.view(B, L, C))
                 self.tape.append(bwd_split)
-            x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs)
-            hm = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs)
-            outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5))
+            x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs, site=qs + 1, xq=aq)
+            del aq
+            if q8:
+                hm, hq = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs, site=qs + 2)
+                outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5), sites=(qs + 2, qs + 3), xq=hq)
+                del hq
+            else:
+                hm = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs)
+                outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5))
         return outs["img"], outs["txt"]
 
-    def single_block(self, pre: str, x: _Var, sv: _Var, B, Li, Lt, kv_len, rope):
+    def single_block(self, pre: str, x: _Var, sv: _Var, B, Li, Lt, kv_len, rope, site0: int = 0):
+        """site0: this block's fp8 activation sites (linear1 input, linear2 input = site0 + 1)"""
         D, H = self.m.hidden_size, self.m.heads_num
         M4 = int(D * self.m.ratio)
         Lj = Li + Lt
@@ -654,17 +796,32 @@ class _HYRun(_STRun):
         dsl = (lambda k: dmod[:, k * D:(k + 1) * D]) if dmod is not None else (lambda k: None)
         mod1 = pre + "linear1"
         adapted = self.lora is not None and mod1 in self.lora.sites
-        xm = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=adapted)
+        q8 = self.q8
+        xq = catq = None
+        if q8:
+            xm, xq = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=adapted, site=site0)
+            xq = self.fp8_in(site0, xm.d, xq)
+        else:
+            xm = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=adapted)
         w1, b1 = self.W(pre + "linear1.weight"), self.W(pre + "linear1.bias")
         qkv = self.E(M, 3 * D)
         bw1 = None
         if adapted:
-            qkv, bw1 = self.lora_linear(xm.ext, mod1, b1[:3 * D], y=qkv)
+            qkv, bw1 = self.lora_linear(xm.ext, mod1, b1[:3 * D], y=qkv, q8=(xq, site0, pre + "linear1.weight", (0, 3 * D)) if q8 else None)
+        elif q8:
+            self.mx_gemm(xq, site0, pre + "linear1.weight", qkv, b1[:3 * D], rows=(0, 3 * D))
         else:
             ops.gemm(xm.d, w1[:3 * D], qkv, b1[:3 * D])
         cat = self.E(M, D + M4)                                  # [attn | gelu(mlp)], read by linear2
         u = self.E(M, M4)
-        ops.gemm(xm.d, w1[3 * D:], cat[:, D:], b1[3 * D:], epilogue=EPI_BIAS_GELU, pre_act_out=u)
+        if q8:                                                   # the GELU epilogue writes its columns of linear2's e4m3 input
+            q2 = self.steady(site0 + 1)
+            catq = None if q2 is None else torch.empty(M, D + M4, dtype=ops.FP8, device=self.dev)
+            self.mx_gemm(xq, site0, pre + "linear1.weight", cat[:, D:], b1[3 * D:], rows=(3 * D, 3 * D + M4), epilogue=EPI_BIAS_GELU,
+                         pre_act_out=u, out_fp8=None if q2 is None else (catq[:, D:], q2[0], q2[1]))
+            del xq
+        else:
+            ops.gemm(xm.d, w1[3 * D:], cat[:, D:], b1[3 * D:], epilogue=EPI_BIAS_GELU, pre_act_out=u)
         qkvv = _Var(qkv)
         joint = self.E(M, 3 * D)
         dj = [None]
@@ -692,8 +849,14 @@ class _HYRun(_STRun):
         w2 = self.W(pre + "linear2.weight")
         y = self.E(M, D)
         branch = self.E(M, D) if (self.save and dmod is not None) else None
-        ops.gemm(cat, w2, y, self.W(pre + "linear2.bias"), epilogue=EPI_GATED_RES, residual=x.d, gate_txt=sl(2), gate_vid=sl(2), gate_bstride=bs, S=Lj,
-                 St=0, pre_act_out=branch)
+        epi2 = dict(epilogue=EPI_GATED_RES, residual=x.d, gate_txt=sl(2), gate_vid=sl(2), gate_bstride=bs, S=Lj, St=0, pre_act_out=branch)
+        if q8:
+            if catq is not None:                                 # the attention columns: one cast pass
+                ops.cast_fp8_scaled(cat[:, :D], catq[:, :D], *self.qsite(site0 + 1))
+            self.mx_gemm(self.fp8_in(site0 + 1, cat, catq), site0 + 1, pre + "linear2.weight", y, self.W(pre + "linear2.bias"), **epi2)
+            del catq
+        else:
+            ops.gemm(cat, w2, y, self.W(pre + "linear2.bias"), **epi2)
         yv = _Var(y)
         if self.save:
             def bwd_linear2():
@@ -732,8 +895,13 @@ class _HYRun(_STRun):
         self._dsv = torch.zeros(B, D, dtype=F32, device=self.dev) if self.save else None
         iv, tv = _Var(img.to(BF16).reshape(B * Li, D).contiguous()), _Var(txt.to(BF16).reshape(B * Lt, D).contiguous())
         self._in = (iv, tv)
+        if self.q8:                 # delayed scaling: the scales of this forward from the amaxes recorded so far (none yet: just in time)
+            st = m.fp8_state()
+            self.q8s, self.jit = st, not st.seeded
+            if st.seeded:
+                ops.fp8_scale_update(st.amax, st.history, st.scale)
         for i in range(m.n_double):
-            iv, tv = self.double_block(f"double_blocks.{i}.", iv, tv, svv, B, Li, Lt, kv_len, rope)
+            iv, tv = self.double_block(f"double_blocks.{i}.", iv, tv, svv, B, Li, Lt, kv_len, rope, site0=8 * i)
         Lj = Li + Lt
         x = self.E(B, Lj, D)
         x[:, :Li].copy_(iv.d.view(B, Li, D)); x[:, Li:].copy_(tv.d.view(B, Lt, D))          # torch.cat((img, txt), 1) (models.py trunk)
@@ -744,7 +912,9 @@ class _HYRun(_STRun):
                 self.acc(iv, g[:, :Li].reshape(B * Li, D)); self.acc(tv, g[:, Li:].reshape(B * Lt, D))
             self.tape.append(bwd_cat)
         for i in range(m.n_single):
-            xv = self.single_block(f"single_blocks.{i}.", xv, svv, B, Li, Lt, kv_len, rope)
+            xv = self.single_block(f"single_blocks.{i}.", xv, svv, B, Li, Lt, kv_len, rope, site0=8 * m.n_double + 2 * i)
+        if self.q8:
+            self.q8s.seeded = True
         self._out = xv
         self._dims = (B, Lj, D)
         return xv.d.view(B, Lj, D)
@@ -775,7 +945,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  mm_single_blocks_depth: int = 40, rope_dim_list=(16, 56, 56), qkv_bias: bool = True, qk_norm: bool = True, qk_norm_type: str = "rms",
                  guidance_embed: bool = False, text_projection: str = "single_refiner", use_attention_mask: bool = True,
                  text_states_dim: Optional[int] = None, text_states_dim_2: Optional[int] = None, fp8: bool = False, lora_rank: int = 0,
-                 lora_alpha: float = 1.0, dtype=None, device=None, **unused):
+                 lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, **unused):
         if text_projection != "single_refiner" or mlp_act_type != "gelu_tanh" or not qkv_bias or not qk_norm or qk_norm_type != "rms":
             raise NotImplementedError("only the shipped HunyuanVideo-T2V configuration (single_refiner, gelu_tanh, rms qk-norm) is built")
         if sum(rope_dim_list) != hidden_size // heads_num:
@@ -806,7 +976,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
         after = {"final_layer.linear.weight": (pt * ph * pw * oc, D), "final_layer.linear.bias": (pt * ph * pw * oc,),
                  "final_layer.adaLN_modulation.1.weight": (2 * D, D), "final_layer.adaLN_modulation.1.bias": (2 * D,)}
         super().__init__(hidden_size, heads_num, mlp_width_ratio, mm_double_blocks_depth, mm_single_blocks_depth, fp8, lora_rank, lora_alpha,
-                         shapes_before=before, shapes_after=after)
+                         shapes_before=before, shapes_after=after, fp8_amax_history=fp8_amax_history)
         self.patch_size, self.in_channels, self.out_channels, self.guidance_embed = tuple(patch_size), in_channels, oc, guidance_embed
         self.text_states_dim, self.text_states_dim_2 = td, td2
 

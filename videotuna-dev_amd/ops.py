@@ -1005,6 +1005,84 @@ def gemm_fp8(aq, wq, out, scale_a, scale_w, bias=None):
     return out
 
 
+def _amax_slot(amax):
+    """an amax slot: a 1-element view of an fp32 (non-negative float bits, max'ed atomically as uint32) or int32 device tensor"""
+    if not amax.is_cuda or amax.dtype not in (torch.float32, torch.int32) or amax.numel() < 1:
+        raise ValueError("amax: expected an fp32 / int32 device tensor")
+    return amax.data_ptr()
+
+
+def gemm_mxfp8(aq, wq, out, scale_a, scale_w, bias=None, *, epilogue: int = EPI_BIAS, residual: Optional[torch.Tensor] = None,
+               gate_txt: Optional[torch.Tensor] = None, gate_vid: Optional[torch.Tensor] = None, gate_bstride: int = 0, S: int = 1, St: int = 0,
+               pre_act_out: Optional[torch.Tensor] = None, tail=None, out_fp8=None):
+    """out bf16 [M, N] = epilogue((aq [M, K] @ wq [N, K]^T) * scale_a * scale_w [+ At @ Wt^T] + bias) on the MX-scaled fp8 matrix cores
+    (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales).  scale_a / scale_w: device fp32 scalars (views).  Epilogue keywords as gemm()
+    (EPI_BIAS, EPI_BIAS_GELU, EPI_GATED_RES).  tail = (At bf16 [M, Kt], Wt bf16 [N, Kt]), Kt 32 or 64: a bf16 K segment added into the same
+    accumulators.  out_fp8 = (Cq float8_e4m3fn [M, N], scale, amax): Cq = e4m3(out / scale), max |out| into the amax slot."""
+    _req(aq, FP8, "aq", 2); _req(wq, FP8, "wq", 2); _req(out, BF16, "out", 2)
+    M, K, N = aq.shape[0], aq.shape[1], wq.shape[0]
+    if wq.shape[1] != K or out.shape[0] != M or out.shape[1] < N:
+        raise ValueError(f"gemm_mxfp8: aq {tuple(aq.shape)}, wq {tuple(wq.shape)}, out {tuple(out.shape)}")
+    At = Wt = None
+    Kt = 0
+    if tail is not None:
+        At, Wt = tail
+        _req(At, BF16, "tail A", 2); _req(Wt, BF16, "tail W", 2)
+        Kt = At.shape[1]
+        if Wt.shape[1] != Kt or At.shape[0] != M or Wt.shape[0] != N:
+            raise ValueError(f"gemm_mxfp8: tail {tuple(At.shape)} x {tuple(Wt.shape)}^T for a [{M}, {N}] product")
+    cq = sq = am = None
+    if out_fp8 is not None:
+        cq, sq, am = out_fp8
+        _req(cq, FP8, "out_fp8", 2)
+        if cq.shape[0] != M or cq.shape[1] < N:
+            raise ValueError(f"gemm_mxfp8: out_fp8 {tuple(cq.shape)} for a [{M}, {N}] product")
+        am = _amax_slot(am)
+    check(load_library().vt_gemm_mxfp8(aq.data_ptr(), aq.stride(0), wq.data_ptr(), wq.stride(0), out.data_ptr(), out.stride(0), M, N, K,
+                                       _p(bias), scale_a.data_ptr(), scale_w.data_ptr(), epilogue,
+                                       _p(residual), 0 if residual is None else residual.stride(0),
+                                       _p(gate_txt), _p(gate_vid), gate_bstride, S, St,
+                                       _p(pre_act_out), 0 if pre_act_out is None else pre_act_out.stride(0),
+                                       _p(At), 0 if At is None else At.stride(0), _p(Wt), 0 if Wt is None else Wt.stride(0), Kt,
+                                       _p(cq), 0 if cq is None else cq.stride(0), _p(sq), am, _stream()), "vt_gemm_mxfp8")
+    return out
+
+
+def cast_fp8_scaled(x, y, scale, amax, copy=None, rows=None):
+    """y float8_e4m3fn [M, K] = satfinite(RNE(x / scale)), max |x| into the amax slot; rows = (L, Lj, off): row m reads x row
+    (m // L) * Lj + off + m % L (one stream's rows of a joint buffer), else row m; copy: bf16 [M, K] that receives those rows of x"""
+    _req(x, BF16, "x", 2); _req(y, FP8, "y", 2)
+    if copy is not None:
+        _req(copy, BF16, "copy", 2)
+    M, K = y.shape
+    L, Lj, off = rows if rows is not None else (0, 0, 0)
+    if x.shape[1] < K or (rows is None and x.shape[0] < M) or (rows is not None and (M % L or x.shape[0] < M // L * Lj)):
+        raise ValueError(f"cast_fp8_scaled: x {tuple(x.shape)} -> y {tuple(y.shape)}, rows {rows}")
+    check(load_library().vt_cast_fp8_scaled(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _p(copy), 0 if copy is None else copy.stride(0),
+                                            M, K, L, Lj, off, scale.data_ptr(), _amax_slot(amax), _stream()), "vt_cast_fp8_scaled")
+    return y
+
+
+def ln_modulate_fwd_fp8(x, y, gamma, beta, mod, mean, rstd, D: int, S: int, St: int, eps: float, q, qscale, amax):
+    """ln_modulate_fwd plus q float8_e4m3fn [M, D] = e4m3(y / qscale) and max |y| into the amax slot (y is the same as ln_modulate_fwd's)"""
+    _req(x, BF16, "x", 2); _req(y, BF16, "y", 2); _req(q, FP8, "q", 2)
+    sh_t, sc_t, sh_v, sc_v, bstride = mod if mod is not None else (None, None, None, None, 0)
+    check(load_library().vt_ln_modulate_fwd_fp8(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _p(gamma), _p(beta),
+                                                _p(sh_t), _p(sc_t), _p(sh_v), _p(sc_v), bstride, _p(mean), _p(rstd),
+                                                x.shape[0], D, S, St, eps, q.data_ptr(), q.stride(0), qscale.data_ptr(), _amax_slot(amax),
+                                                _stream()), "vt_ln_modulate_fwd_fp8")
+
+
+def fp8_scale_update(amax, history, scale):
+    """delayed scaling, all sites in one launch: history [n, H] <- (amax, history[:, :-1]) (newest first), scale [n] = max(history) / 448
+    (1 where that is 0), amax [n] cleared"""
+    _req(history, torch.float32, "history", 2); _req(scale, torch.float32, "scale", 1)
+    n, H = history.shape
+    if amax.numel() != n or scale.numel() != n or not (amax.is_contiguous() and history.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("fp8_scale_update: amax [n], history [n, H], scale [n], contiguous")
+    check(load_library().vt_fp8_scale_update(_amax_slot(amax), history.data_ptr(), scale.data_ptr(), n, H, _stream()), "vt_fp8_scale_update")
+
+
 def qk_rmsnorm_rope128_fwd(qkv, out, gq, gk, rstd, H: int, L: int, Lout: int, row_off: int, rope=None, eps: float = 1e-6):
     """qkv bf16 [M, 3*H*128] -> out rows (m // L) * Lout + row_off + m % L: q^ | k^ | v.  rope = (cos, sin) fp32 [S_rope, 128] for the
     first S_rope positions of every sample"""
