@@ -59,6 +59,9 @@ int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ld
 /* tile selection of vt_gemm_bf16: 0 = by shape (default), 1 = always the 128x128 kernel, 2 = always the 256x256 kernel,
  * 3 = always the 256x128 producer/consumer kernel */
 int vt_gemm_set_tile(int mode);
+/* which kernel vt_gemm_bf16 runs for an (M, N, K) problem under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128
+ * producer/consumer, 4 = the producer/consumer kernel's 128-row instantiation; < 0 on a bad shape */
+int vt_gemm_bf16_kernel(int M, int N, int K);
 /* convolution tile choice: 0 = per shape (default), 1 = always the 128 x 128 kernels, 2 = the 320-wide loader / multiplier kernels whenever
  * Cout % 320 == 0 (tests and A/B timing; csrc/convnd.hip) */
 int vt_conv_set_tile(int mode);

@@ -239,6 +239,16 @@ static int VT_CAT(pick_tile, VT_SUFFIX)(int M, int N, int K) {
     return 1;
 }
 
+int VT_CAT(vt_gemm_pc_bm, VT_SUFFIX)(int M);     // gemm_pc_bf16.hip
+// which kernel vt_gemm_bf16 launches for an (M, N, K) problem under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128
+// producer / consumer, 4 = the producer / consumer kernel's 128-row instantiation.  The three kernels sum the same MFMA products in the
+// same K order, so their outputs are bit-identical and cannot tell which one ran (tests: dispatch coverage of the production shapes)
+extern "C" int VT_CAT(vt_gemm_bf16_kernel, VT_SUFFIX)(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return VT_ERR_BAD_SHAPE;
+    const int tile = VT_CAT(pick_tile, VT_SUFFIX)(M, N, K);
+    return tile == 3 && VT_CAT(vt_gemm_pc_bm, VT_SUFFIX)(M) == 128 ? 4 : tile;
+}
+
 extern "C" int GEMM_ENTRY(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
                             int M, int N, int K, const void* bias, int epilogue, int out_fp32,
                             const void* R, int ldr, int r_mod,

@@ -335,6 +335,8 @@ __global__ __launch_bounds__(512, 1) void GEMM_PC_KERNEL(GemmParams p) {
 
 // BM = 128 (four-stage ring, three K-tiles in flight) for GEMMs with few rows: twice the workgroups on the narrow outputs
 static bool VT_CAT(pc_small_m, VT_SUFFIX)(const GemmParams& p) { return p.M <= 1024; }
+// rows of the tile launch_pc runs for an M-row problem (vt_gemm_bf16_kernel reports it)
+int VT_CAT(vt_gemm_pc_bm, VT_SUFFIX)(int M) { GemmParams p{}; p.M = M; return VT_CAT(pc_small_m, VT_SUFFIX)(p) ? 128 : GP_BM; }
 
 template <int EPI, bool F32>
 static int VT_CAT(launch_pc, VT_SUFFIX)(const GemmParams& p, hipStream_t st) {

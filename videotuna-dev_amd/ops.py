@@ -439,6 +439,15 @@ def gemm_set_tile(mode: int = 0):
     check(load_library().vt_gemm_set_tile(mode), "vt_gemm_set_tile")
 
 
+def gemm_kernel(M: int, N: int, K: int) -> int:
+    """the kernel vt_gemm_bf16 runs for this shape under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128 producer / consumer,
+    4 = the producer / consumer kernel's 128-row instantiation"""
+    k = load_library().vt_gemm_bf16_kernel(M, N, K)
+    if k < 0:
+        check(k, "vt_gemm_bf16_kernel")
+    return k
+
+
 def attn_bwd_set_chain(chain_len: int = 0, slots: int = 0):
     """tuning / test knob of the dQ hand-off chains (0 = defaults); see include/vt355.h"""
     check(load_library().vt_attn_bwd_set_chain(chain_len, slots), "vt_attn_bwd_set_chain")
