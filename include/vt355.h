@@ -355,6 +355,27 @@ int vt_attn_small_bwd(const void* q, const void* k, const void* v, const void* o
                       long long o_rs, long long o_bs, long long do_rs, long long do_bs, long long dq_rs, long long dq_bs,
                       long long dk_rs, long long dv_rs, float softmax_scale, int mask_block, void* stream);
 
+/* Dual-context cross-attention, head_dim 64 (csrc/attn_dual.hip): o = softmax(q K^T s) V + img_scale * softmax(q K_ip^T s) V_ip, two
+ * separate softmaxes over the text keys of the sample (k, v [B, Sa <= 96, .]) and the image keys of the query's frame (k_ip, v_ip
+ * [B * Sq / rows_per_frame, Sb <= 32, .]; rows [f*rows_per_frame, (f+1)*rows_per_frame) of sample b meet item b * Sq / rows_per_frame + f)
+ * -- DynamiCrafter's CrossAttention with img_cross_attention (lvdm/modules/attention.py:45-170).  rows_per_frame divides Sq and need
+ * not be a multiple of 32; rows_per_frame = Sq is one image set per sample.  Strides as vt_attn_small_*.  lse2: fp32 [2, B, H, Sq]
+ * (text plane, image plane).  Backward: dq bf16 like q; dk32, dv32 fp32 [B, Sa, H*64] and dkip32, dvip32 fp32
+ * [B * Sq / rows_per_frame, Sb, H*64], contiguous and fully written; the forward's o is not needed.  ws: scratch of
+ * vt_attn_dual_ws_floats(...) fp32 elements (per-chunk partial sums added in a fixed order: no atomics, reproducible bits). */
+long long vt_attn_dual_ws_floats(int B, int H, int Sq, int rows_per_frame, int Sa, int Sb);
+int vt_attn_dual_fwd(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, void* o, float* lse2,
+                     int B, int H, int Sq, int rows_per_frame, int Sa, int Sb,
+                     long long q_rs, long long q_bs, long long k_rs, long long k_bs, long long v_rs, long long v_bs,
+                     long long kip_rs, long long kip_bs, long long vip_rs, long long vip_bs, long long o_rs, long long o_bs,
+                     float softmax_scale, float img_scale, void* stream);
+int vt_attn_dual_bwd(const void* q, const void* k, const void* v, const void* k_ip, const void* v_ip, const void* dout,
+                     const float* lse2, void* dq, float* dk32, float* dv32, float* dkip32, float* dvip32, float* ws,
+                     long long ws_floats, int B, int H, int Sq, int rows_per_frame, int Sa, int Sb,
+                     long long q_rs, long long q_bs, long long k_rs, long long k_bs, long long v_rs, long long v_bs,
+                     long long kip_rs, long long kip_bs, long long vip_rs, long long vip_bs, long long do_rs, long long do_bs,
+                     long long dq_rs, long long dq_bs, float softmax_scale, float img_scale, void* stream);
+
 /* Flash attention for head dimensions other than 64 (csrc/attn_gen.hip): head_dim 80 (OpenSora STDiT's 72, zero padded: 16 heads x 72,
  * opensora/models/layers/blocks.py:139-225 `Attention` and :472-505 `MultiHeadCrossAttention`) or 128 (HunyuanVideo,
  * hunyuan/hyvideo_t2v/modules/attenion.py:60-156).  Element (item b, row s, head h, d) at base + b*bs + s*rs + h*hstride + d.

@@ -24,6 +24,10 @@ TARGET_REMAP = {
     "videotuna.models.lvdm.ddpm3d.LVDMFlow": "vt355.lvdm.LVDMFlow",
     "videotuna.schedulers.ddpm.LDDPM": "vt355.lvdm.LDDPM",
     "videotuna.schedulers.diffusion_schedulers.LDMScheduler": "vt355.lvdm.LDMScheduler",
+    # DynamiCrafter (configs/002_dynamicrafter/dc_i2v_1024.yaml)
+    "videotuna.models.lvdm.modules.networks.openaimodel3d_dc.UNetModel": "vt355.unet.UNetModel",
+    "videotuna.models.lvdm.ddpm3d.LatentVisualDiffusionFlow": "vt355.lvdm.LatentVisualDiffusionFlow",
+    "videotuna.models.lvdm.modules.encoders.ip_resampler.Resampler": "vt355.resampler.Resampler",
     # OpenSora v1.0 (configs/003_opensora/opensorav10_256x256.yaml)
     "videotuna.models.opensora.models.stdit.stdit.STDiT_XL_2": "vt355.stdit.STDiT_XL_2",
     "videotuna.models.opensora.models.stdit.stdit.STDiT": "vt355.stdit.STDiT",

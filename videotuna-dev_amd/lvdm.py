@@ -32,17 +32,32 @@ from .config import instantiate_from_config
 from .optim import FusedAdamW
 
 
+def zero_terminal_snr_betas(betas: np.ndarray) -> np.ndarray:
+    """Algorithm 1 of "Common Diffusion Noise Schedules and Sample Steps are Flawed" (arXiv 2305.08891), as the reference applies it for
+    ``rescale_betas_zero_snr: True`` (schedulers/ddpm.py:83, utils/diffusion_utils.py:141): sqrt(abar) is shifted so that its last value is
+    zero and rescaled so that its first value is kept; float64 throughout.  The last alphas_cumprod is then exactly 0."""
+    root = np.sqrt(np.cumprod(1.0 - np.asarray(betas, dtype=np.float64), axis=0))
+    first, last = root[0].copy(), root[-1].copy()
+    root = (root - last) * (first / (first - last))
+    abar = root ** 2
+    alphas = np.concatenate([abar[0:1], abar[1:] / abar[:-1]])
+    return 1.0 - alphas
+
+
 class LDDPM:
     """schedule tables of videotuna/schedulers/ddpm.py:64-153 (beta_schedule "linear": linspace(sqrt(s), sqrt(e))^2, float64) and
     q_sample / get_v (:216-228)"""
 
     def __init__(self, timesteps: int = 1000, beta_schedule: str = "linear", linear_start: float = 1e-4, linear_end: float = 2e-2,
-                 parameterization: str = "eps", **unused):
+                 parameterization: str = "eps", rescale_betas_zero_snr: bool = False, **unused):
         if beta_schedule != "linear":
             raise NotImplementedError("only the 'linear' beta schedule of the VideoCrafter2 recipes is built")
         self.num_timesteps = int(timesteps)
         self.parameterization = parameterization
+        self.rescale_betas_zero_snr = bool(rescale_betas_zero_snr)
         betas = np.linspace(linear_start ** 0.5, linear_end ** 0.5, timesteps, dtype=np.float64) ** 2
+        if self.rescale_betas_zero_snr:
+            betas = zero_terminal_snr_betas(betas)
         self.alphas_cumprod = torch.from_numpy(np.cumprod(1.0 - betas, axis=0))
         self.logvar = torch.zeros(timesteps)
         self.learn_logvar = False
@@ -250,3 +265,135 @@ class LVDMFlow(nn.Module):
 
 
 VideocrafterFlow = LVDMFlow
+
+
+class _JointOptimizer:
+    """the fused AdamW of every trained module of a flow (the UNet, the Resampler) behind one optimizer interface: each module keeps its own
+    flat master / gradient buffer, so a step is one fused launch per module"""
+
+    def __init__(self, optimizers):
+        self.optimizers = list(optimizers)
+        self.param_groups = [g for o in self.optimizers for g in o.param_groups]
+
+    def zero_grad(self, set_to_none: bool = False):
+        for o in self.optimizers:
+            o.zero_grad(set_to_none)
+
+    def step(self, *a, **k):
+        for o in self.optimizers:
+            o.step(*a, **k)
+
+    def check_errors(self, wait: bool = True):
+        for o in self.optimizers:
+            o.check_errors(wait)
+
+
+class LatentVisualDiffusionFlow(LVDMFlow):
+    """DynamiCrafter's image-to-video flow (videotuna/models/lvdm/ddpm3d.py:1311-1480 get_batch_input, :787-848 p_losses) on pre-encoded
+    batches ``{'latents' [B,4,T,H,W], 'context' [B,77,C], 'image_tokens' [B,257,1280], 'fps' | 'frame_stride' [B]}`` (optionally
+    ``'cond_frame_index'``, ``'null_context'``, ``'null_image_tokens'``).  The frozen 2-D VAE and the OpenCLIP text / image towers stay outside
+    (their config nodes are recorded in ``frozen_stage_configs``, not instantiated); the image-context projector (``image_proj_stage_config``:
+    vt355.resampler.Resampler) is part of the flow and trains with the UNet when ``image_proj_model_trainable``.
+
+    The reference zeroes the conditioning IMAGE of a sample whose image condition is dropped and encodes it; with pre-encoded tokens the
+    caller supplies that encoding once as ``null_image_tokens`` [257, 1280] (the image tower's output for an all-zero image)."""
+
+    def __init__(self, img_cond_stage_config=None, finegrained=False, image_proj_stage_config=None, freeze_embedder=True,
+                 image_proj_model_trainable=True, rand_cond_frame: bool = False, fps_condition_type: str = "fs", interp_mode: bool = False,
+                 conditioning_key: str = "hybrid", null_image_tokens=None, first_stage_config=None, cond_stage_config=None, **kwargs):
+        if kwargs.get("lora_args"):
+            raise NotImplementedError("LoRA on the DynamiCrafter flow: the reference ships no such recipe")
+        super().__init__(**kwargs)
+        if image_proj_stage_config is None or finegrained:
+            raise NotImplementedError("only the Resampler projector of the DynamiCrafter recipe (image_proj_stage_config) is built")
+        if interp_mode:
+            raise NotImplementedError("interp_mode is not built")
+        if conditioning_key != "hybrid":
+            raise NotImplementedError("conditioning_key 'hybrid' (concat of the conditioning frame's latent + cross-attention) is the recipe's")
+        if fps_condition_type not in ("fs", "fps"):
+            raise ValueError(f"fps_condition_type {fps_condition_type!r}: 'fs' (batch['frame_stride']) or 'fps' (batch['fps'])")
+        self.frozen_stage_configs = dict(img_cond_stage_config=img_cond_stage_config, first_stage_config=first_stage_config,
+                                         cond_stage_config=cond_stage_config, freeze_embedder=freeze_embedder)
+        self.image_proj_model = instantiate_from_config(image_proj_stage_config)
+        self.image_proj_model.bfloat16()
+        self.image_proj_model_trainable = bool(image_proj_model_trainable)
+        self.rand_cond_frame, self.fps_condition_type, self.conditioning_key = bool(rand_cond_frame), fps_condition_type, conditioning_key
+        self.null_image_tokens = None if null_image_tokens is None else torch.as_tensor(null_image_tokens)
+
+    def configure_optimizers(self):
+        ts = self.model.enable_training()
+        opts = [FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts)]
+        if self.image_proj_model_trainable:
+            rs = self.image_proj_model.enable_training()
+            opts.append(FusedAdamW(rs.params, lr=self.learning_rate, fullft_state=rs))
+        return _JointOptimizer(opts)
+
+    def condition_masks(self, random_num: torch.Tensor):
+        """ddpm3d.py:1391-1397: text dropped where r < 2p, image dropped where p <= r < 3p (p = uncond_prob): 5 % text only, 5 % both, 5 % image
+        only at the recipe's p = 0.05.  Returns (drop_text bool [B], keep_image bool [B])"""
+        p = self.uncond_prob
+        drop_text = random_num < 2 * p
+        keep_image = ~((random_num >= p) & (random_num < 3 * p))
+        return drop_text, keep_image
+
+    def drop_conditions(self, context, image_tokens, random_num, null_context=None, null_image_tokens=None):
+        drop_text, keep_image = self.condition_masks(random_num)
+        B = context.shape[0]
+        if bool(drop_text.any()):
+            null = null_context if null_context is not None else self.null_context
+            if null is None:
+                raise RuntimeError("dropping the text condition needs the embedding of the empty prompt: batch['null_context'] [77, C] or null_context=")
+            null = null.to(device=context.device, dtype=context.dtype)
+            context = torch.where(drop_text.to(context.device).view(B, 1, 1), null.expand_as(context) if null.dim() == 3 else null.unsqueeze(0).expand_as(context), context)
+        if not bool(keep_image.all()):
+            null = null_image_tokens if null_image_tokens is not None else self.null_image_tokens
+            if null is None:
+                raise RuntimeError("dropping the image condition needs the image tower's tokens of an all-zero image: batch['null_image_tokens'] "
+                                   "[257, 1280] or null_image_tokens=")
+            null = null.to(device=image_tokens.device, dtype=image_tokens.dtype)
+            image_tokens = torch.where(keep_image.to(image_tokens.device).view(B, 1, 1), image_tokens,
+                                       null.expand_as(image_tokens) if null.dim() == 3 else null.unsqueeze(0).expand_as(image_tokens))
+        return context, image_tokens
+
+    def loss_from(self, z, context, image_tokens, t, noise, fs=None, cond_frame_index: int = 0):
+        """deterministic core of training_step (fixed t / noise / conditioning frame): Resampler -> context = [text | image tokens per frame],
+        hybrid input = [q_sample(z * scale) | latent of the conditioning frame repeated over time], UNet, v / eps / x0 MSE"""
+        z = z.to(torch.float32)
+        B, C, T = z.shape[:3]
+        img_ctx = self.image_proj_model(image_tokens.to(torch.bfloat16).contiguous())                    # [B, T*16, ctx]
+        ctx = torch.cat([context.to(torch.bfloat16), img_ctx], dim=1)
+        cond = z[:, :, cond_frame_index:cond_frame_index + 1].expand(B, C, T, *z.shape[3:])             # c_concat: from z BEFORE use_scale
+        x_start = (z * self.scale_arr[t].view(-1, 1, 1, 1, 1) if self.use_scale else z).contiguous()
+        noise = noise.to(torch.float32).contiguous()
+        sa, sb = self.scheduler.coefficients(t)
+        x_noisy = torch.empty(x_start.shape, dtype=torch.bfloat16, device=z.device)
+        ops.q_sample(x_start, noise, sa, sb, None, x_noisy)
+        x_in = torch.cat([x_noisy, cond.to(torch.bfloat16)], dim=1).contiguous()
+        out = self.model(x_in, t, context=ctx, fs=None if fs is None else torch.as_tensor(fs, device=z.device).long())
+        if self.parameterization == "eps":
+            target = noise
+        elif self.parameterization == "x0":
+            target = x_start
+        else:
+            target = sa.view(-1, 1, 1, 1, 1) * noise - sb.view(-1, 1, 1, 1, 1) * x_start
+        return _EpsLoss.apply(out, target.contiguous())
+
+    def training_step(self, batch, batch_idx=0):
+        for k in ("latents", "context", "image_tokens"):
+            if k not in batch:
+                raise RuntimeError("the DynamiCrafter path takes pre-encoded batches {'latents', 'context', 'image_tokens', 'fps' | 'frame_stride'}: "
+                                   "the frozen 2-D VAE and the OpenCLIP text / image towers are outside this engine's hot path")
+        z = batch["latents"]
+        B, T = z.shape[0], z.shape[2]
+        context, tokens = batch["context"], batch["image_tokens"]
+        if self.training and self.uncond_prob > 0.0:                      # shared_step(random_uncond=True)
+            context, tokens = self.drop_conditions(context, tokens, torch.rand(B, device=z.device), batch.get("null_context"),
+                                                   batch.get("null_image_tokens"))
+        idx = batch.get("cond_frame_index")
+        if idx is None:
+            import random
+            idx = random.randint(0, T - 1) if self.rand_cond_frame else 0
+        fs = batch["frame_stride"] if self.fps_condition_type == "fs" else batch["fps"]
+        t = torch.randint(0, self.num_timesteps, (B,), device=z.device).long()
+        noise = torch.randn(z.shape, dtype=torch.float32, device=z.device)
+        return self.loss_from(z, context, tokens, t, noise, fs, int(idx))

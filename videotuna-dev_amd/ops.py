@@ -941,6 +941,70 @@ def attn_small_bwd(q, k, v, o, do, lse2, dq, dk, dv, H: int, scale: float, mask_
                                            dk.stride(1), dv.stride(1), scale, mask_block, _stream()), "vt_attn_small_bwd")
 
 
+def attn_dual_ws_floats(B: int, H: int, Sq: int, rows_per_frame: int, Sa: int, Sb: int) -> int:
+    n = load_library().vt_attn_dual_ws_floats(B, H, Sq, rows_per_frame, Sa, Sb)
+    if n < 0:
+        raise ValueError(f"attn_dual: rows_per_frame {rows_per_frame} does not divide Sq {Sq}")
+    return n
+
+
+def _attn_dual_shapes(q, k, k_ip, rows_per_frame):
+    B, Sq, Sa, Sb = q.shape[0], q.shape[1], k.shape[1], k_ip.shape[1]
+    if rows_per_frame <= 0 or Sq % rows_per_frame or k.shape[0] != B or k_ip.shape[0] != B * (Sq // rows_per_frame):
+        raise ValueError(f"attn_dual: q {tuple(q.shape)}, k {tuple(k.shape)}, k_ip {tuple(k_ip.shape)} do not fit rows_per_frame={rows_per_frame}")
+    return B, Sq, Sa, Sb
+
+
+def attn_dual_fwd(q, k, v, k_ip, v_ip, o, lse2, H: int, scale: float, rows_per_frame: int, img_scale: float = 1.0):
+    """q, o: [B, Sq, >=H*64]; text k, v: [B, Sa<=96, >=H*64]; image k_ip, v_ip: [B*Sq/rows_per_frame, Sb<=32, >=H*64]; lse2 fp32 [2, B, H, Sq]"""
+    for n, t in (("q", q), ("k", k), ("v", v), ("k_ip", k_ip), ("v_ip", v_ip), ("o", o)):
+        _req(t, BF16, n, 3)
+    B, Sq, Sa, Sb = _attn_dual_shapes(q, k, k_ip, rows_per_frame)
+    if v.shape[:2] != k.shape[:2] or v_ip.shape[:2] != k_ip.shape[:2] or o.shape[:2] != q.shape[:2]:
+        raise ValueError("attn_dual_fwd: v / v_ip / o do not match k / k_ip / q")
+    if lse2 is not None:
+        _req(lse2, torch.float32, "lse2")
+        if tuple(lse2.shape) != (2, B, H, Sq) or not lse2.is_contiguous():
+            raise ValueError(f"attn_dual_fwd: lse2 must be contiguous [2, {B}, {H}, {Sq}]")
+    check(load_library().vt_attn_dual_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_ip.data_ptr(), v_ip.data_ptr(), o.data_ptr(), _p(lse2),
+                                          B, H, Sq, rows_per_frame, Sa, Sb,
+                                          q.stride(1), q.stride(0), k.stride(1), k.stride(0), v.stride(1), v.stride(0),
+                                          k_ip.stride(1), k_ip.stride(0), v_ip.stride(1), v_ip.stride(0), o.stride(1), o.stride(0),
+                                          scale, img_scale, _stream()), "vt_attn_dual_fwd")
+
+
+def attn_dual_bwd(q, k, v, k_ip, v_ip, do, lse2, dq, dk, dv, dk_ip, dv_ip, H: int, scale: float, rows_per_frame: int,
+                  img_scale: float = 1.0, ws=None):
+    """dq bf16 like q; dk, dv fp32 [B, Sa, H*64] and dk_ip, dv_ip fp32 [B*Sq/rows_per_frame, Sb, H*64], contiguous, fully written.
+    ws: fp32 scratch of attn_dual_ws_floats(...) elements (allocated here when None)."""
+    for n, t in (("q", q), ("k", k), ("v", v), ("k_ip", k_ip), ("v_ip", v_ip), ("do", do), ("dq", dq)):
+        _req(t, BF16, n, 3)
+    B, Sq, Sa, Sb = _attn_dual_shapes(q, k, k_ip, rows_per_frame)
+    D = H * 64
+    for n, t, shp in (("dk", dk, (B, Sa, D)), ("dv", dv, (B, Sa, D)), ("dk_ip", dk_ip, (k_ip.shape[0], Sb, D)), ("dv_ip", dv_ip, (k_ip.shape[0], Sb, D))):
+        _req(t, torch.float32, n, 3)
+        if tuple(t.shape) != shp or not t.is_contiguous():
+            raise ValueError(f"attn_dual_bwd: {n} must be contiguous fp32 {shp}, got {tuple(t.shape)}")
+    if do.shape[:2] != q.shape[:2] or dq.shape[:2] != q.shape[:2]:
+        raise ValueError("attn_dual_bwd: do / dq do not match q")
+    _req(lse2, torch.float32, "lse2")
+    if tuple(lse2.shape) != (2, B, H, Sq) or not lse2.is_contiguous():
+        raise ValueError(f"attn_dual_bwd: lse2 must be contiguous [2, {B}, {H}, {Sq}]")
+    need = attn_dual_ws_floats(B, H, Sq, rows_per_frame, Sa, Sb)
+    if ws is None and need > 0:
+        ws = torch.empty(need, dtype=torch.float32, device=q.device)
+    if need > 0:
+        _req(ws, torch.float32, "ws")
+        if ws.numel() < need or not ws.is_contiguous():
+            raise ValueError(f"attn_dual_bwd: workspace of {ws.numel()} floats, {need} needed")
+    check(load_library().vt_attn_dual_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), k_ip.data_ptr(), v_ip.data_ptr(), do.data_ptr(),
+                                          lse2.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), dk_ip.data_ptr(), dv_ip.data_ptr(),
+                                          _p(ws) if need > 0 else None, ws.numel() if need > 0 else 0, B, H, Sq, rows_per_frame, Sa, Sb,
+                                          q.stride(1), q.stride(0), k.stride(1), k.stride(0), v.stride(1), v.stride(0),
+                                          k_ip.stride(1), k_ip.stride(0), v_ip.stride(1), v_ip.stride(0), do.stride(1), do.stride(0),
+                                          dq.stride(1), dq.stride(0), scale, img_scale, _stream()), "vt_attn_dual_bwd")
+
+
 def attn_gen_fwd(q, k, v, o, lse2, H: int, head_dim: int, hstride: int, scale: float, kv_len=None, mask_block: int = 0):
     """head_dim 80 | 128 (csrc/attn_gen.hip).  q, o [NB, Sq, >= H*hstride]; k, v [NB, Sk, ...]; kv_len int32 [NB] | None"""
     for n, t in (("q", q), ("k", k), ("v", v), ("o", o)):

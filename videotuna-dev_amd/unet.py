@@ -20,6 +20,10 @@ Train mode (``model.train()``, the nn.Module default, with gradients enabled): T
 site, element), so the backward pass re-derives it and nothing is stored; a fresh seed per forward comes from torch's CPU generator
 (``torch.manual_seed`` reproduces a run), ``model.dropout_seed = s`` pins it.  ``model.eval()`` switches the masks off (the golden
 fixtures of the reference were taken that way).
+DynamiCrafter (configs/002_dynamicrafter, openaimodel3d_dc.py) is the same network with ``img_cross_attention`` (every spatial attn2
+gets to_k_ip / to_v_ip and a second softmax over the 16 image tokens of the query's frame: csrc/attn_dual.hip), ``fs_condition``
+(the fps_embedding path, fed by ``fs``), 8 input channels and ResBlock dropout; the gradient of the image context rows is returned
+through autograd because the Resampler that produces them trains.
 There is no CPU / eager fallback.
 """
 from __future__ import annotations
@@ -85,24 +89,26 @@ def _param_shapes(c, st) -> Dict[str, tuple]:
     """reference state_dict keys in registration order"""
     mc, te = c.model_channels, 4 * c.model_channels
     sh: Dict[str, tuple] = {}
-    for n in ["time_embed"] + (["fps_embedding"] if c.fps_cond else []):
+    for n in ["time_embed"] + (["fps_embedding"] if (c.fps_cond or c.fs_condition) else []):
         sh[n + ".0.weight"] = (te, mc); sh[n + ".0.bias"] = (te,)
         sh[n + ".2.weight"] = (te, te); sh[n + ".2.bias"] = (te,)
 
-    def transformer(l, ctx_dim):
+    def transformer(l, ctx_dim, img=False):
         pre, cc, inner = l.pre, l.c, l.inner
         k1 = (1,) if getattr(l, "conv1d", False) else ()
         sh[pre + ".norm.weight"] = (cc,); sh[pre + ".norm.bias"] = (cc,)
         sh[pre + ".proj_in.weight"] = (inner, cc) + k1; sh[pre + ".proj_in.bias"] = (inner,)
         b = pre + ".transformer_blocks.0."
 
-        def attn(a, kd):
+        def attn(a, kd, ip=False):
             sh[b + a + ".to_q.weight"] = (inner, inner); sh[b + a + ".to_k.weight"] = (inner, kd); sh[b + a + ".to_v.weight"] = (inner, kd)
             sh[b + a + ".to_out.0.weight"] = (inner, inner); sh[b + a + ".to_out.0.bias"] = (inner,)
+            if ip:          # CrossAttention(img_cross_attention=True) registers the image projections after to_out (attention.py:82-84)
+                sh[b + a + ".to_k_ip.weight"] = (inner, kd); sh[b + a + ".to_v_ip.weight"] = (inner, kd)
         attn("attn1", inner)
         sh[b + "ff.net.0.proj.weight"] = (8 * inner, inner); sh[b + "ff.net.0.proj.bias"] = (8 * inner,)
         sh[b + "ff.net.2.weight"] = (inner, 4 * inner); sh[b + "ff.net.2.bias"] = (inner,)
-        attn("attn2", inner if ctx_dim is None else ctx_dim)
+        attn("attn2", inner if ctx_dim is None else ctx_dim, img)
         for n in ("norm1", "norm2", "norm3"):
             sh[b + n + ".weight"] = (inner,); sh[b + n + ".bias"] = (inner,)
         sh[pre + ".proj_out.weight"] = (cc, inner) + k1; sh[pre + ".proj_out.bias"] = (cc,)
@@ -127,7 +133,7 @@ def _param_shapes(c, st) -> Dict[str, tuple]:
                     sh[pre + f".temopral_conv.conv{j}.{last}.weight"] = (co, co, 3, 1, 1)
                     sh[pre + f".temopral_conv.conv{j}.{last}.bias"] = (co,)
         elif l.kind == "st":
-            transformer(l, c.context_dim)
+            transformer(l, c.context_dim, c.img_cross_attention)
         elif l.kind == "tt":
             transformer(l, None)
         elif l.kind == "down":
@@ -324,16 +330,27 @@ class UNetModel(FlatParamModule):
                  temporal_conv=False, tempspatial_aware=False, temporal_attention=True, temporal_selfatt_only=True,
                  use_relative_position=True, use_causal_attention=False, temporal_length=None, use_fp16=False,
                  addition_attention=False, use_image_attention=False, temporal_transformer_depth=1, fps_cond=False,
-                 text_context_len: int = 77):
+                 text_context_len: int = 77, img_cross_attention=False, img_cross_attention_scale_learnable=False, default_fs=4,
+                 fs_condition=False):
         super().__init__()
+        if img_cross_attention_scale_learnable:
+            raise NotImplementedError("img_cross_attention_scale_learnable (a learnable alpha on the image branch) is not used by the "
+                                      "DynamiCrafter recipe (configs/002_dynamicrafter) and is not implemented")
+        if fps_cond and fs_condition:
+            raise ValueError("fps_cond (openaimodel3d.UNetModel) and fs_condition (openaimodel3d_dc.UNetModel) name the same fps_embedding")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        if in_channels > 8:
+            raise NotImplementedError("the input convolution takes up to 8 channels (4 latent + 4 conditioning-frame channels)")
         unsupported = dict(use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown, tempspatial_aware=tempspatial_aware,
                            use_relative_position=use_relative_position, use_causal_attention=use_causal_attention,
                            use_image_attention=use_image_attention, not_use_linear=not use_linear, not_conv_resample=not conv_resample,
-                           not_selfatt_only=not temporal_selfatt_only, dropout=dropout != 0.0, depth=transformer_depth != 1 or temporal_transformer_depth != 1,
+                           not_selfatt_only=not temporal_selfatt_only, depth=transformer_depth != 1 or temporal_transformer_depth != 1,
                            dims=dims != 2, num_heads=num_heads != -1)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
-            raise NotImplementedError(f"vt355 UNetModel implements the VideoCrafter2 recipe (configs/001_videocrafter2); unsupported options: {bad}")
+            raise NotImplementedError(f"vt355 UNetModel implements the VideoCrafter2 and DynamiCrafter recipes (configs/001_videocrafter2, "
+                                      f"configs/002_dynamicrafter); unsupported options: {bad}")
         if num_head_channels != 64:
             raise NotImplementedError("the attention kernels are built for num_head_channels = 64")
         if model_channels % 64 or context_dim is None or context_dim % 64:
@@ -345,10 +362,13 @@ class UNetModel(FlatParamModule):
                                       channel_mult=tuple(channel_mult), context_dim=context_dim, num_head_channels=num_head_channels,
                                       temporal_conv=temporal_conv, temporal_attention=temporal_attention, temporal_length=temporal_length,
                                       addition_attention=addition_attention, fps_cond=fps_cond, use_checkpoint=use_checkpoint,
-                                      text_context_len=text_context_len)
+                                      text_context_len=text_context_len, img_cross_attention=bool(img_cross_attention),
+                                      img_cross_attention_scale=1.0, img_context_len=16, default_fs=int(default_fs),
+                                      fs_condition=bool(fs_condition), dropout=float(dropout))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.tconv_dropout_p = 0.1          # TemporalConvBlock(dropout=0.1), hard-coded in ResBlock (openaimodel3d.py:205-210)
         self.dropout_seed: Optional[int] = None      # None: a fresh seed per training forward from torch's CPU generator
+        self.last_emb = None                         # embedding sum [B, 4*model_channels] of the last forward (everything timesteps / fps / fs decide)
         self.last_dropout_sites: List = []           # (site name, counter offset, rows, channels) of the last training forward (tests)
         self.structure = build_structure(self.config)
         self._setup_flat(_param_shapes(self.config, self.structure))
@@ -360,6 +380,8 @@ class UNetModel(FlatParamModule):
     # ---- LoRA (vc2_t2v_lora.yaml) ----
     def add_lora(self, r: int = 4, lora_alpha: float = 1.0, target_modules=LORA_TARGETS, seed: int = 0):
         """peft.get_peft_model's effect on this network: adapters on the target projections of every CrossAttention, every base weight frozen"""
+        if self.config.img_cross_attention:
+            raise NotImplementedError("LoRA on the image-conditioned UNet: the reference ships no such recipe")
         if self.train_state is not None:
             raise RuntimeError("add_lora() after enable_training(): the full fine-tune state already exists")
         if self.lora is not None:
@@ -416,9 +438,20 @@ class UNetModel(FlatParamModule):
         return self
 
     # ---- forward ----
-    def forward(self, x, timesteps, context=None, features_adapter=None, fps=16, **kwargs):
+    def resolve_fs(self, fs, B: int, device):
+        """the frame-stride / fps condition the network embeds: ``fs`` (int | int64 [B]), default_fs when None (openaimodel3d_dc.py:700-704)"""
+        if fs is None:
+            fs = self.config.default_fs
+        if isinstance(fs, int):
+            return torch.full((B,), fs, dtype=torch.int64, device=device)
+        return fs.to(device=device, dtype=torch.int64)
+
+    def forward(self, x, timesteps, context=None, features_adapter=None, fps=16, fs=None, **kwargs):
         """x [B, C, T, H, W] bf16, timesteps int64 [B], context [B, L, context_dim], fps int | int64 [B] -> [B, C_out, T, H, W]
-        (openaimodel3d.py:650-694)"""
+        (openaimodel3d.py:650-694).  With fs_condition (openaimodel3d_dc.py:676-735) the frame-stride / fps condition is ``fs`` (int64 [B];
+        None = default_fs) and ``fps`` is not read.  With img_cross_attention the context is [B, 77 + T*16, context_dim] (77 text tokens,
+        then 16 image tokens per frame) or [B, 77 + n <= 32, context_dim] (one image set for all frames); when it requires grad, the
+        gradient of its image rows comes back through autograd (the text rows get zeros: the text encoder is frozen)."""
         if features_adapter is not None:
             raise NotImplementedError("features_adapter is not part of the VideoCrafter2 training path")
         if not x.is_cuda:
@@ -428,13 +461,17 @@ class UNetModel(FlatParamModule):
         if context is None:
             raise ValueError("context (text embeddings [B, L, context_dim]) is required")
         B = x.shape[0]
+        if self.config.fs_condition:
+            fps = self.resolve_fs(fs, B, x.device)
         if isinstance(fps, int):
             fps = torch.full((B,), fps, dtype=torch.int64, device=x.device)
         need_grad = torch.is_grad_enabled() and (self.train_state is not None or (self.lora is not None and self.lora.train_state is not None))
         if need_grad:
             anchor = torch.zeros(1, device=x.device, requires_grad=True)
             return _UNetFn.apply(anchor, self, x, timesteps, context, fps)
-        out, _ = _Run(self, save=False).forward(x, timesteps, context, fps)
+        run = _Run(self, save=False)
+        out, _ = run.forward(x, timesteps, context, fps)
+        self.last_emb = run.emb
         return out
 
 
@@ -444,14 +481,16 @@ class _UNetFn(torch.autograd.Function):
         run = _Run(model, save=True)
         out, _ = run.forward(x, t, context, fps)
         model.last_dropout_sites = run.drop_sites
+        model.last_emb = run.emb
         ctx.run = run
         return out
 
     @staticmethod
     def backward(ctx, dout):
         ctx.run.backward(dout)
+        dctx = ctx.run.context_grad() if ctx.needs_input_grad[4] else None
         ctx.run = None
-        return None, None, None, None, None, None
+        return None, None, None, None, dctx, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -597,10 +636,11 @@ def _trace_file():
 
 class _Var:
     """an activation [rows, C] (bf16, row stride may exceed C) and, during the backward pass, its gradient"""
-    __slots__ = ("d", "g", "ext", "shared")
+    __slots__ = ("d", "g", "ext", "shared", "g32")
 
     def __init__(self, d, ext=None, shared=False):
         self.d, self.g, self.ext = d, None, ext          # ext: the [rows, C + EXT] buffer d is the first C columns of (input of a LoRA'd Linear)
+        self.g32 = None                                  # fp32 accumulator for a gradient summed over many layers (the image context)
         self.shared = shared                             # several adapted Linears read this buffer (the text context): each keeps its own x A^T
 
 
@@ -608,6 +648,8 @@ class _Run:
     # defaults for the engines that subclass this tape (vt355.stdit, vt355.hunyuan) and set up their own state
     frozen = False
     lora = LP = lts = drop = None
+    _img_ctx = None
+    _dual_ws = None
 
     def __init__(self, model: UNetModel, save: bool):
         self.m, self.save = model, save
@@ -647,7 +689,9 @@ class _Run:
         return self.E(M, C), None
 
     def acc(self, v: _Var, g):
-        if v.g is None:
+        if v.g32 is not None:
+            v.g32.add_(g)
+        elif v.g is None:
             v.g = g
         else:
             ops.add_rows(v.g, g, v.g)
@@ -786,11 +830,13 @@ class _Run:
             self.tape.append(bwd)
         return yv
 
-    def dropout(self, x: _Var, site: str) -> _Var:
+    def dropout(self, x: _Var, site: str, p: Optional[float] = None) -> _Var:
         """nn.Dropout(p) in training mode; the backward pass re-derives the mask from (seed, offset)"""
         if self.drop is None:
             return x
         p_, seed = self.drop
+        if p is not None:
+            p_ = float(p)
         off = len(self.drop_sites) << 36
         M, C = x.d.shape
         self.drop_sites.append((site, off, M, C))
@@ -871,11 +917,15 @@ class _Run:
             self.tape.append(bwd)
         return self.linear(ov, pre + ".to_out.0.weight", pre + ".to_out.0.bias", residual=residual)
 
-    def cross_attention(self, x: _Var, pre: str, heads: int, B: int, ctx: _Var, L: int, residual: _Var) -> _Var:
-        """text cross-attention: the M/B rows of a sample against its L context rows (attention.py:101-181, context[:, :77])"""
+    def cross_attention(self, x: _Var, pre: str, heads: int, B: int, ctx: _Var, L: int, residual: _Var, img=None) -> _Var:
+        """text cross-attention: the M/B rows of a sample against its L context rows (attention.py:101-181, context[:, :77]).
+        img = (image context _Var [NI*Sb, ctx], NI, Sb): the image branch of CrossAttention(img_cross_attention=True) -- a second softmax
+        over the Sb image keys of the query's frame (NI = B*T items) or of its sample (NI = B), added to the text result"""
         M, C = x.d.shape
         q = self.linear(x, pre + ".to_q.weight", None)
         kv = self.linear(ctx, None, None, wspan=(pre + ".to_k.weight", pre + ".to_v.weight"))        # [B*L, 2C]
+        if img is not None:
+            return self._dual_attention(x, pre, heads, B, q, kv, L, residual, *img)
         o = self.E(M, C)
         lse = self.E(B, heads, M // B, dt=F32)
         kv3 = kv.d.view(B, L, 2 * C)
@@ -892,6 +942,40 @@ class _Run:
                 ops.residual_cast(dk.view(B * L, C), None, dkv[:, :C])
                 ops.residual_cast(dv.view(B * L, C), None, dkv[:, C:])
                 kv.g = dkv
+            self.tape.append(bwd)
+        return self.linear(ov, pre + ".to_out.0.weight", pre + ".to_out.0.bias", residual=residual)
+
+    def _dual_attention(self, x, pre, heads, B, q, kv, L, residual, imgv, NI, Sb) -> _Var:
+        M, C = x.d.shape
+        Sq = M // B
+        rpf = Sq // (NI // B)                       # rows of one frame at this level (NI == B: one image set per sample)
+        kvi = self.linear(imgv, None, None, wspan=(pre + ".to_k_ip.weight", pre + ".to_v_ip.weight"))          # [NI*Sb, 2C]
+        o = self.E(M, C)
+        lse = self.E(2, B, heads, Sq, dt=F32)
+        q3, o3 = q.d.view(B, Sq, C), o.view(B, Sq, C)
+        kv3, kvi3 = kv.d.view(B, L, 2 * C), kvi.d.view(NI, Sb, 2 * C)
+        c_img = float(self.c.img_cross_attention_scale)
+        ops.attn_dual_fwd(q3, kv3[:, :, :C], kv3[:, :, C:], kvi3[:, :, :C], kvi3[:, :, C:], o3, lse, heads, 0.125, rpf, c_img)
+        ov = _Var(o)
+        if self.save:
+            def bwd():
+                dq = self.E(M, C)
+                dk = self.E(B, L, C, dt=F32); dv = self.E(B, L, C, dt=F32)
+                dki = self.E(NI, Sb, C, dt=F32); dvi = self.E(NI, Sb, C, dt=F32)
+                need = ops.attn_dual_ws_floats(B, heads, Sq, rpf, L, Sb)
+                if self._dual_ws is None or self._dual_ws.numel() < need:          # one scratch buffer for all blocks of the run (grows to the largest level)
+                    self._dual_ws = self.E(max(need, 1), dt=F32)
+                ops.attn_dual_bwd(q3, kv3[:, :, :C], kv3[:, :, C:], kvi3[:, :, :C], kvi3[:, :, C:], ov.g.view(B, Sq, C), lse,
+                                  dq.view(B, Sq, C), dk, dv, dki, dvi, heads, 0.125, rpf, c_img, ws=self._dual_ws)
+                q.g = dq
+                dkv = self.E(B * L, 2 * C)
+                ops.residual_cast(dk.view(B * L, C), None, dkv[:, :C])
+                ops.residual_cast(dv.view(B * L, C), None, dkv[:, C:])
+                kv.g = dkv
+                dkvi = self.E(NI * Sb, 2 * C)
+                ops.residual_cast(dki.view(NI * Sb, C), None, dkvi[:, :C])
+                ops.residual_cast(dvi.view(NI * Sb, C), None, dkvi[:, C:])
+                kvi.g = dkvi
             self.tape.append(bwd)
         return self.linear(ov, pre + ".to_out.0.weight", pre + ".to_out.0.bias", residual=residual)
 
@@ -977,6 +1061,8 @@ class _Run:
                 h0.g = self.conv_bwd(g5, h0.d.view(B, T, H, W_, ci), pre + ".in_layers.2.weight", pre + ".in_layers.2.bias", k2, p2, 1).view(M, ci)
             self.tape.append(bwd1)
         h2 = self.groupnorm(h1, pre + ".out_layers.0", B * T, 1e-5, True)
+        if self.c.dropout > 0.0:
+            h2 = self.dropout(h2, pre + ".out_layers.2", p=self.c.dropout)      # ResBlock's nn.Dropout(p=dropout) (openaimodel3d.py:186-192)
         if ci != co:
             skip = self.linear(x, pre + ".skip_connection.weight", pre + ".skip_connection.bias")
         else:
@@ -1017,17 +1103,17 @@ class _Run:
         b = pre + ".transformer_blocks.0."
         if mode == "spatial":
             x = self.self_attention_spatial(self.layernorm(x, b + "norm1", ext=True), b + "attn1", heads, kw["nseq"], x)
-            x = self.cross_attention(self.layernorm(x, b + "norm2", ext=True), b + "attn2", heads, kw["B"], kw["ctx"], kw["L"], x)
+            x = self.cross_attention(self.layernorm(x, b + "norm2", ext=True), b + "attn2", heads, kw["B"], kw["ctx"], kw["L"], x, img=kw.get("img"))
         else:
             x = self.attention_packed(self.layernorm(x, b + "norm1", ext=True), b + "attn1", heads, kw["T"], x)
             x = self.attention_packed(self.layernorm(x, b + "norm2", ext=True), b + "attn2", heads, kw["T"], x)
         return self.feed_forward(self.layernorm(x, b + "norm3"), b + "ff", x)
 
-    def spatial_transformer(self, l, x: _Var, shape, ctx: _Var, L: int) -> _Var:
+    def spatial_transformer(self, l, x: _Var, shape, ctx: _Var, L: int, img=None) -> _Var:
         B, T, H, W_ = shape
         n = self.groupnorm(x, l.pre + ".norm", B * T, 1e-6, False)
         h = self.linear(n, l.pre + ".proj_in.weight", l.pre + ".proj_in.bias")
-        h = self.basic_block(h, l.pre, l.heads, "spatial", nseq=B * T, B=B, ctx=ctx, L=L)
+        h = self.basic_block(h, l.pre, l.heads, "spatial", nseq=B * T, B=B, ctx=ctx, L=L, img=img)
         return self.linear(h, l.pre + ".proj_out.weight", l.pre + ".proj_out.bias", residual=x)
 
     def temporal_transformer(self, l, x: _Var, shape) -> _Var:
@@ -1073,11 +1159,13 @@ class _Run:
             return sin, l0, a0
         sin_t, l0_t, a0_t = embed(timesteps, "time_embed")
         emb = self.E(B, te); ops.gemm(a0_t, self.W("time_embed.2.weight"), emb, self.W("time_embed.2.bias"))
-        if c.fps_cond:
+        fcond = c.fps_cond or c.fs_condition
+        if fcond:
             sin_f, l0_f, a0_f = embed(fps, "fps_embedding")
             emb2 = self.E(B, te)
             ops.gemm(a0_f, self.W("fps_embedding.2.weight"), emb2, self.W("fps_embedding.2.bias"), epilogue=EPI_GATED_RES, residual=emb)
             emb = emb2
+        self.emb = emb                      # time (+ fps / fs) embedding sum [B, te] before SiLU: UNetModel.last_emb
         se = self.E(B, te); ops.silu(emb, se)
         sev = _Var(se)
         demb = torch.zeros(B, te, dtype=F32, device=dev) if self.save else None            # d loss / d SiLU(emb), summed over the ResBlocks
@@ -1085,7 +1173,7 @@ class _Run:
             def bwd_emb():
                 d_emb = torch.zeros(B, te, dtype=F32, device=dev)
                 ops.silu_bwd(demb, emb, d_emb)
-                for (sin, l0, a0, name) in ([(sin_t, l0_t, a0_t, "time_embed")] + ([(sin_f, l0_f, a0_f, "fps_embedding")] if c.fps_cond else [])):
+                for (sin, l0, a0, name) in ([(sin_t, l0_t, a0_t, "time_embed")] + ([(sin_f, l0_f, a0_f, "fps_embedding")] if fcond else [])):
                     da0 = torch.zeros(B, te, dtype=F32, device=dev)
                     ops.small_linear_bwd(d_emb, a0, self.W(name + ".2.weight"), self.G(name + ".2.weight"), self.G(name + ".2.bias"), da0)
                     dl0 = torch.zeros(B, te, dtype=F32, device=dev)
@@ -1098,6 +1186,27 @@ class _Run:
         ctx2, ctx_ext = self.act(B * L, cdim, True)      # LoRA mode: to_k / to_v of the text cross-attentions are adapted -> extended buffer
         ctx2.copy_(context[:, :L].reshape(B * L, cdim))
         ctxv = _Var(ctx2, ctx_ext, shared=True); ctxv.g = False       # frozen text encoder: no gradient wanted
+        # image context (openaimodel3d_dc.py:686-693): 77 + T*16 rows = 16 image tokens for EVERY frame -> B*T items; any other length:
+        # the rows after the text are one image set per sample -> B items
+        img = None
+        self._img_ctx = None
+        if c.img_cross_attention:
+            Lc, Li = context.shape[1], c.img_context_len
+            if Lc <= L:
+                raise ValueError(f"img_cross_attention: the context has {Lc} rows, no image tokens after the {L} text tokens")
+            NI, Sb = (B * T, Li) if Lc == L + T * Li else (B, Lc - L)
+            if Sb > 32:
+                raise NotImplementedError(f"img_cross_attention: {Sb} image tokens per item (context of {Lc} rows, {T} frames); "
+                                          f"the attention kernel holds up to 32 (csrc/attn_dual.hip)")
+            img2 = self.E(NI * Sb, cdim)
+            img2.copy_(context[:, L:].reshape(NI * Sb, cdim))
+            imgv = _Var(img2)
+            if self.save and context.requires_grad:
+                imgv.g32 = torch.zeros(NI * Sb, cdim, dtype=F32, device=dev)      # summed over the 16 blocks in fp32
+                self._img_ctx = (imgv, B, L, Lc, context.dtype)
+            else:
+                imgv.g = False
+            img = (imgv, NI, Sb)
         # input: [B,C,T,H,W] -> channels-last rows, 4 channels padded to one 64-wide K-tile
         x64 = torch.zeros(B, T, H, W_, 64, dtype=BF16, device=dev)
         x64[..., :Cin] = x.permute(0, 2, 3, 4, 1)
@@ -1124,7 +1233,7 @@ class _Run:
                 elif l.kind == "res":
                     h = self.res_block(l, h, shape, sev, demb)
                 elif l.kind == "st":
-                    h = self.spatial_transformer(l, h, shape, ctxv, L)
+                    h = self.spatial_transformer(l, h, shape, ctxv, L, img)
                 elif l.kind == "tt":
                     h = self.temporal_transformer(l, h, shape)
                 elif l.kind == "down":
@@ -1186,6 +1295,16 @@ class _Run:
             self.tape.append(bwd_out)
         out = y5.permute(0, 4, 1, 2, 3).contiguous()                     # -> [B, C_out, T, H, W] (the reference's layout at the boundary)
         return out, None
+
+    def context_grad(self):
+        """d loss / d context after backward(): zeros for the text rows (frozen encoder), the fp32 sum over all blocks for the image rows"""
+        if self._img_ctx is None:
+            return None
+        imgv, B, L, Lc, dt = self._img_ctx
+        cdim = imgv.g32.shape[1]
+        g = torch.zeros(B, Lc, cdim, dtype=F32, device=self.dev)
+        g[:, L:] = imgv.g32.view(B, Lc - L, cdim)
+        return g.to(dt)
 
     def backward(self, dout):
         """dout [B, C_out, T, H, W] bf16"""
