@@ -417,7 +417,16 @@ int vt_quantize_fp8(const void* x, long long ldx, void* y, long long ldy, long l
  * vt_cast_fp8_scaled: x bf16 -> e4m3 with a device scale, max |x| into amax; row m reads x row (m / L) * Lj + off + m % L (L = 0: m) and
  * is optionally copied (bf16) to cp.  vt_ln_modulate_fwd_fp8: vt_ln_modulate_fwd plus an e4m3 copy of y and its amax.
  * vt_fp8_scale_update: per site, history [n, H] <- (amax, history[:, :-1]), scale = max(history) / 448 (1 if 0), amax cleared.
- * amax slots are uint32 holding non-negative float bits. */
+ * amax slots are uint32 holding non-negative float bits.
+ * Input-gradient products of that mode (HunyuanBlocks fp8_dgrad; format codes 0 = e4m3, 1 = e5m2, both OCP):
+ * vt_gemm_mxfp8_dx: C = epilogue((Gq WqT^T) * scale_g * scale_w [+ At Wt^T]), Gq [M, ldg] the quantised output gradient in format fmt_g,
+ * WqT [N, ldw] e4m3 bytes of the transposed weight (row / column slices through ldw); epilogue EPI_BIAS (plain), EPI_DGELU (times
+ * gelu'(pre_act_in)) or EPI_GATED_RES (+ residual, no gates); Cq (EPI_DGELU only): copy of C in format fmt_out, as vt_gemm_mxfp8's.
+ * vt_cast_fp8_fmt: vt_cast_fp8_scaled with the target format as an argument (e5m2 saturates at +-57344).
+ * vt_gate_mul_fp8: vt_gate_mul (y bit-equal) plus q = fp8(y / scale) in format fmt and max |y| into amax.
+ * vt_fp8_scale_update_fmax: vt_fp8_scale_update with scale = max(history) / fmax (448: e4m3, 57344: e5m2).
+ * Measured (M 10 456): the dX products 1.4-1.9x vt_gemm_bf16 (profiles/r05_mxfp8_dx_kbench.txt); the LoRA step 614.7 -> 584.3 ms
+ * (profiles/r05_hunyuan_fp8_dgrad_ab.json). */
 int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias,
                   const float* scale_a, const float* scale_w, int epilogue, const void* residual, int ldr,
                   const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St, void* pre_act_out, int ldc2,
@@ -431,6 +440,15 @@ int vt_ln_modulate_fwd_fp8(const void* x, int ldx, void* y, int ldy, const void*
                            int M, int D, int S, int St, float eps, void* q, int ldq, const float* qscale, unsigned int* amax,
                            void* stream);
 int vt_fp8_scale_update(unsigned int* amax, float* history, float* scale, int n, int H, void* stream);
+int vt_gemm_mxfp8_dx(const void* G, int ldg, int fmt_g, const void* WT, int ldw, void* C, int ldc, int M, int N, int K,
+                     const float* scale_g, const float* scale_w, int epilogue, const void* residual, int ldr,
+                     const void* pre_act_in, int ldu, const void* At, int ldat, const void* Wt, int ldwt, int Kt,
+                     void* Cq, int ldcq, int fmt_out, const float* scale_out, unsigned int* amax, void* stream);
+int vt_cast_fp8_fmt(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
+                    int Lj, int off, int fmt, const float* scale, unsigned int* amax, void* stream);
+int vt_gate_mul_fp8(const void* x, int ldx, void* y, int ldy, const float* g_txt, const float* g_vid, int bstride, long long M,
+                    int D, int S, int St, void* q, int ldq, int fmt, const float* scale, unsigned int* amax, void* stream);
+int vt_fp8_scale_update_fmax(unsigned int* amax, float* history, float* scale, int n, int H, float fmax, void* stream);
 
 /* HunyuanVideo q/k preparation, head_dim 128 (csrc/qknorm128.hip): per-head RMSNorm(eps, weight [128]) of the q and k thirds of a fused
  * [M, 3*H*128] projection, rotary embedding of the first S_rope positions of every sample (image tokens; cos / sin fp32 [S_rope, 128] | NULL),

@@ -3,13 +3,16 @@
 HunyuanVideoFlow.training_step with backward and optimizer step.
 
 A model needs 126-151 GB, so two cannot share a card: every (mode, round) runs in a child process of its own, under its own time limit,
-and the modes alternate (False, "weights", "mfma", False, ...) for ``--rounds`` rounds.  A child that fails ends the run (no retries).
+and the modes alternate (False, "weights", "mfma", "mfma+dgrad", "mfma+dgrad-e4m3", False, ...) for ``--rounds`` rounds.  A child that
+fails ends the run (no retries).  "mfma+dgrad" / "mfma+dgrad-e4m3": fp8="mfma" with the input-gradient products on the fp8 matrix cores
+too (fp8_dgrad, gradients quantised to E5M2 / E4M3).
 The parent prints ONE JSON line: per mode the median and spread (max - min) of the rounds' ms/step and the loss on the bench's fixed batch
-(fixed sigma / noise draws, ``loss_only`` of bench.py), plus the relative step-time and loss deltas of "mfma" vs bf16.
+(fixed sigma / noise draws, ``loss_only`` of bench.py), plus the relative step-time and loss deltas of "mfma" vs bf16 and, per dgrad mode,
+of that mode vs "mfma" in the same run (``dgrad_vs_mfma``: is the median below "mfma"'s by more than the larger of the two spreads?).
 
 Weights: seeded random init drawn on the device (the same for every mode; the CPU draw of bench.py takes minutes per child at this size).
 
-    python tools/bench_hunyuan_fp8_ab.py [--rounds 3] [--steps 4] [--warmup 2] [--timeout 900]
+    python tools/bench_hunyuan_fp8_ab.py [--rounds 3] [--steps 4] [--warmup 2] [--timeout 900] [--modes bf16,mfma,mfma+dgrad]
 """
 import argparse
 import json
@@ -20,7 +23,8 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODES = {"bf16": False, "weights": "weights", "mfma": "mfma"}
+MODES = {"bf16": False, "weights": "weights", "mfma": "mfma", "mfma+dgrad": "mfma", "mfma+dgrad-e4m3": "mfma"}
+DGRAD = {"mfma+dgrad": "e5m2", "mfma+dgrad-e4m3": "e4m3"}
 
 
 def child(mode: str, steps: int, warmup: int):
@@ -30,7 +34,8 @@ def child(mode: str, steps: int, warmup: int):
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
     B, Lt, (lT, lH, lW) = 1, 256, (5, 68, 120)
-    model = HYVideoDiffusionTransformer(mm_double_blocks_depth=20, mm_single_blocks_depth=40, lora_rank=4, fp8=MODES[mode]).to(dev)
+    model = HYVideoDiffusionTransformer(mm_double_blocks_depth=20, mm_single_blocks_depth=40, lora_rank=4, fp8=MODES[mode],
+                                        fp8_dgrad=DGRAD.get(mode, False)).to(dev)
     g = torch.Generator(device=dev).manual_seed(11)
     with torch.no_grad():                     # HunyuanBlocks.init_weights' distribution, drawn on the device
         for n, p in model._plist.items():
@@ -82,13 +87,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=900, help="seconds per child")
     ap.add_argument("--child", choices=list(MODES), default=None)
+    ap.add_argument("--modes", default=",".join(MODES), help="comma-separated subset of " + ", ".join(MODES) + " (bf16 and mfma always run)")
     args = ap.parse_args()
     if args.child:
         child(args.child, args.steps, args.warmup)
         return
-    runs = {m: [] for m in MODES}
+    chosen = set(args.modes.split(",")) | {"bf16", "mfma"}
+    if not chosen <= set(MODES):
+        raise SystemExit(f"--modes: unknown {sorted(chosen - set(MODES))}")
+    modes = [m for m in MODES if m in chosen]
+    runs = {m: [] for m in modes}
     for r in range(args.rounds):
-        for mode in MODES:
+        for mode in modes:
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", mode,
                    "--steps", str(args.steps), "--warmup", str(args.warmup)]
             p = subprocess.run(cmd, capture_output=True, text=True)
@@ -105,11 +115,21 @@ def main():
         out[mode] = {"ms_per_step_median": statistics.median(ms), "ms_per_step_spread": max(ms) - min(ms), "ms_per_step": ms,
                      "loss_fixed_batch": rs[0]["loss_fixed_batch"], "peak_hbm_gb": max(x["peak_hbm_gb"] for x in rs)}
     b, q = out["bf16"], out["mfma"]
+    dg = {}
+    for mode in DGRAD:
+        if mode in out:
+            d = out[mode]
+            gain = q["ms_per_step_median"] - d["ms_per_step_median"]
+            dg[mode] = {"step_time_rel_delta": d["ms_per_step_median"] / q["ms_per_step_median"] - 1.0, "ms_gain_median": gain,
+                        "faster_beyond_spread": gain > max(q["ms_per_step_spread"], d["ms_per_step_spread"]),
+                        "loss_fixed_batch_rel_delta_vs_bf16": abs(d["loss_fixed_batch"] - b["loss_fixed_batch"]) / abs(b["loss_fixed_batch"]),
+                        "peak_hbm_gb_delta": round(d["peak_hbm_gb"] - q["peak_hbm_gb"], 1)}
     print(json.dumps({"workload": "HYVideoDiffusionTransformer 20 + 40 blocks, latents 1x16x5x68x120 + 256 text tokens, LoRA r 4, "
                                   "HunyuanVideoFlow.training_step + backward + FusedAdamW step",
                       "rounds": args.rounds, "steps": args.steps, "warmup": args.warmup, "modes": out,
                       "mfma_vs_bf16": {"step_time_rel_delta": q["ms_per_step_median"] / b["ms_per_step_median"] - 1.0,
-                                       "loss_fixed_batch_rel_delta": abs(q["loss_fixed_batch"] - b["loss_fixed_batch"]) / abs(b["loss_fixed_batch"])}}),
+                                       "loss_fixed_batch_rel_delta": abs(q["loss_fixed_batch"] - b["loss_fixed_batch"]) / abs(b["loss_fixed_batch"])},
+                      **({"dgrad_vs_mfma": dg} if dg else {})}),
           flush=True)
 
 

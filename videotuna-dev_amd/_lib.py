@@ -99,6 +99,11 @@ PROTOTYPES = {
     "vt_cast_fp8_scaled": [_vp, _ll, _vp, _ll, _vp, _ll, _ll, _i, _i, _i, _i, _fp, _vp, _vp],
     "vt_ln_modulate_fwd_fp8": [_vp, _i, _vp, _i, _vp, _vp, _fp, _fp, _fp, _fp, _i, _fp, _fp, _i, _i, _i, _i, _f, _vp, _i, _fp, _vp, _vp],
     "vt_fp8_scale_update": [_vp, _fp, _fp, _i, _i, _vp],
+    "vt_gemm_mxfp8_dx": [_vp, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _fp, _fp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i,
+                         _vp, _i, _i, _fp, _vp, _vp],
+    "vt_cast_fp8_fmt": [_vp, _ll, _vp, _ll, _vp, _ll, _ll, _i, _i, _i, _i, _i, _fp, _vp, _vp],
+    "vt_gate_mul_fp8": [_vp, _i, _vp, _i, _fp, _fp, _i, _ll, _i, _i, _i, _vp, _i, _i, _fp, _vp, _vp],
+    "vt_fp8_scale_update_fmax": [_vp, _fp, _fp, _i, _i, _f, _vp],
     "vt_opensora_loss": [_fp, _fp, _fp, _vp, _vp, _fp, _ll, _i, _i, _f, _vp],
     "vt_attn_gen_fwd": [_vp, _vp, _vp, _vp, _fp, _vp, _i, _i, _i, _i, _i, _i] + [_ll] * 8 + [_f, _i, _vp],
     "vt_attn_gen_bwd": [_vp, _vp, _vp, _vp, _vp, _fp, _vp, _vp, _vp, _vp, _fp, _fp, _i, _i, _i, _i, _i, _i] + [_ll] * 14 + [_f, _i, _vp],

@@ -61,6 +61,19 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// max |x| into an amax slot: a uint32 holding non-negative float bits (they order as the floats do), cleared between the kernels that
+// publish to it.  Thousands of waves publishing to ONE address serialise in the L2 atomic unit (profiles/r05_amax_publish_ab.txt), so a
+// publisher first reads the slot -- it only grows while producers run, a stale read is a smaller value -- and skips the atomic when it
+// could not raise it.  VT_AMAX_ALWAYS_ATOMIC: the unconditional atomic, for that A/B only.
+__device__ __forceinline__ void amax_publish(unsigned int* slot, float v) {
+    const unsigned int b = __float_as_uint(v);
+#ifdef VT_AMAX_ALWAYS_ATOMIC
+    atomicMax(slot, b);
+#else
+    if (b > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, b);
+#endif
+}
+
 // tanh-GELU as x * sigmoid(2u), u = k0 (x + k1 x^3): sigmoid(2u) = 1 - 1 / (2^(2 log2e u) + 1) with the hardware exp2 / rcp
 // (no IEEE division: these run in GEMM epilogues while the matrix pipe waits).  Saturates correctly: 2^w = inf -> s = 1,
 // 2^w = 0 -> s = 0.

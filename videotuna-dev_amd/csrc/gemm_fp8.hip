@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void fp8_amax_kernel(const bf16_t* x, long lon
         for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[j]));
     }
     mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(amax_bits, __float_as_uint(mx));       // non-negative floats order like their bit patterns
+    if ((threadIdx.x & 63) == 0) amax_publish(amax_bits, mx);
 }
 __global__ void fp8_scale_kernel(const unsigned int* amax_bits, float* scale) {
     const float a = __uint_as_float(amax_bits[0]);

@@ -6,6 +6,9 @@
 // [x A3^T | scaling B] columns stay bf16 and go through v_mfma_f32_16x16x32_bf16 into the same accumulators after the scaled fp8 part
 // (the C/D layout of both instructions is the same on gfx950).  The optional fp8 copy of the output, Cq = e4m3(C_bf16 / scale_out) with
 // max |C_bf16| into an amax slot, hands the next Linear its quantised input without another pass.
+// vt_gemm_mxfp8_dx is the same kernel for the input-gradient products dX = g W of the backward: the quantised gradient (second MFMA
+// operand slot, format code in blgp) is E5M2 or E4M3, the weight (first slot, cbsz) the byte-transposed E4M3 copy; epilogues plain,
+// EPI_DGELU (saved pre-activation u) and "+ residual" (EPI_GATED_RES without gates); the fp8 copy of the output in either format.
 //
 // Kernel: the 128x128 tile / LDS-DMA staging / XOR-swizzled 128-byte rows of gemm_fp8.hip.  A K-tile is 128 bytes per row = ONE 128-deep
 // MFMA k-step; lane group q = lane >> 4 takes the 32 bytes [32 q, 32 q + 32) of its row (chunks 2 q, 2 q + 1) for both operands, so
@@ -22,6 +25,8 @@ struct GemmMxParams {
     unsigned char* Cq; int ldcq; const float* scale_out; unsigned int* amax;   // fp8 copy of the output (Cq = null: none)
 };
 
+enum { FMT_E4M3 = 0, FMT_E5M2 = 1 };               // the f8f6f4 format codes of v_mfma_scale (cbsz / blgp), OCP formats on gfx950
+
 __device__ __forceinline__ unsigned int e4m3x4(const float* v, float sc) {
     float t[4];
 #pragma unroll
@@ -32,7 +37,32 @@ __device__ __forceinline__ unsigned int e4m3x4(const float* v, float sc) {
     return (unsigned int)r;
 }
 
-template <int EPI>
+__device__ __forceinline__ unsigned int e5m2x4(const float* v, float sc) {
+    float t[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = fminf(fmaxf(__fdiv_rn(v[j], sc), -57344.0f), 57344.0f);  // satfinite(RNE(x / scale))
+    int r = 0;
+    r = __builtin_amdgcn_cvt_pk_bf8_f32(t[0], t[1], r, false);
+    r = __builtin_amdgcn_cvt_pk_bf8_f32(t[2], t[3], r, true);
+    return (unsigned int)r;
+}
+
+// one publisher per workgroup of 256 threads: wave maxima through LDS
+__device__ __forceinline__ void amax_publish_block(unsigned int* slot, float mx) {
+    __shared__ float red[4];
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) amax_publish(slot, fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
+}
+
+template <int FMT>
+__device__ __forceinline__ unsigned int fp8x4(const float* v, float sc) {
+    return FMT == FMT_E5M2 ? e5m2x4(v, sc) : e4m3x4(v, sc);
+}
+
+// FA: format of the A operand (activation: E4M3; output gradient: either), FO: format of the fp8 copy of the output.  W is always E4M3.
+template <int EPI, int FA = FMT_E4M3, int FO = FMT_E4M3>
 __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     __shared__ __attribute__((aligned(16))) char smem[65536];
     const GemmParams& g = p.g;
@@ -97,8 +127,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
 #pragma unroll
         for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
-            for (int tm = 0; tm < 4; ++tm)      // e4m3 x e4m3 (format 0, 0), unit block scales (E8M0 127)
-                acc[tn][tm] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[tn], af[tm], acc[tn][tm], 0, 0, 0, 127, 0, 127);
+            for (int tm = 0; tm < 4; ++tm)      // first slot (cbsz): the e4m3 weight; second slot (blgp): A in format FA; unit block scales (E8M0 127)
+                acc[tn][tm] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[tn], af[tm], acc[tn][tm], FMT_E4M3, FA, 0, 127, 0, 127);
         __syncthreads();
     }
     const float sc = p.scale_a[0] * p.scale_w[0];
@@ -128,6 +158,20 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     float* Cs = (float*)smem;
     const int er = tid >> 5, ec = (tid & 31) * 4;
     const int n = col0 + ec;
+    // EPI_DGELU: this thread's 16 x 4 saved pre-activations are fetched now, ahead of the LDS transposes, instead of one dependent 8-byte
+    // load per row pass (the epilogue of the N 12288 product was latency-bound on them)
+    constexpr bool PRE = EPI == EPI_DGELU;
+    constexpr int UNR = PRE ? 8 : 2;
+    u32x2 auxp[2][8];
+    if (PRE) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+            for (int pass = 0; pass < 8; ++pass) {
+                const int m = row0 + half * 64 + pass * 8 + er;
+                auxp[half][pass] = (m < g.M && n < g.N) ? gemm_epilogue_aux_load<EPI>(g, m, n) : (u32x2){0u, 0u};
+            }
+    }
     float bias4[4] = {0.f, 0.f, 0.f, 0.f};
     if (g.bias != nullptr && n < g.N) {
 #pragma unroll
@@ -146,13 +190,13 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
                     *(f32x4*)(Cs + (tm * 16 + frow) * 132 + wn * 64 + tn * 16 + fq * 4) = acc[tn][tm];
         }
         __syncthreads();
-#pragma unroll 2
+#pragma unroll UNR
         for (int pass = 0; pass < 8; ++pass) {
             const int ml = pass * 8 + er;
             const int m = row0 + half * 64 + ml;
             if (m < g.M && n < g.N) {
                 const f32x4 v = *(const f32x4*)(Cs + ml * 132 + ec);
-                const f32x4 o = gemm_epilogue_apply<EPI>(g, m, n, v, bias4, gemm_epilogue_aux_load<EPI>(g, m, n), &gc);
+                const f32x4 o = gemm_epilogue_apply<EPI>(g, m, n, v, bias4, PRE ? auxp[half][pass] : gemm_epilogue_aux_load<EPI>(g, m, n), &gc);
                 u32x2 c2;
                 c2[0] = pack2(o[0], o[1]);
                 c2[1] = pack2(o[2], o[3]);
@@ -162,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
                                         __uint_as_float(c2[1] << 16), __uint_as_float(c2[1] & 0xffff0000u)};     // the bf16 values as written
 #pragma unroll
                     for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(b[j]));
-                    *(unsigned int*)(p.Cq + (size_t)m * p.ldcq + n) = e4m3x4(b, qsc);
+                    *(unsigned int*)(p.Cq + (size_t)m * p.ldcq + n) = fp8x4<FO>(b, qsc);
                 }
             }
         }
@@ -173,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
         float* red = (float*)smem;
         if (lane == 0) red[wave] = amax;
         __syncthreads();
-        if (tid == 0) atomicMax(p.amax, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
+        if (tid == 0) amax_publish(p.amax, fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])));
     }
 }
 
@@ -215,7 +259,55 @@ extern "C" int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, voi
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
+// The input-gradient product of a Linear whose forward ran on vt_gemm_mxfp8: C[M, N] = epilogue((Gq[M, K] WqT[N, K]^T) scale_g scale_w
+// [+ At Wt^T]).  Gq: the quantised output gradient, fmt_g 0 = e4m3 / 1 = e5m2; WqT: e4m3 bytes of the transposed weight (a column or row
+// slice of it: ldw = its full row length).  epilogue: EPI_BIAS (plain store, there is no bias), EPI_DGELU (times gelu'(pre_act_in)),
+// EPI_GATED_RES (+ residual, no gates).  At / Wt: the bf16 tail (LoRA: dt [M, 64], A3^T [N, 64]).  Cq: fp8 copy of C in format fmt_out
+// (EPI_DGELU only: d(u) for the fc1 / linear1 product that follows) with scale_out and amax as vt_gemm_mxfp8.  K % 128 == 0, N % 4 == 0.
+template <int EPI, int FA, int FO>
+static void launch_mxfp8_dx(const GemmMxParams& p, int tiles, hipStream_t st) {
+    hipLaunchKernelGGL((gemm_mxfp8_kernel<EPI, FA, FO>), dim3(tiles), dim3(256), 0, st, p);
+}
+extern "C" int vt_gemm_mxfp8_dx(const void* G, int ldg, int fmt_g, const void* WT, int ldw, void* C, int ldc, int M, int N, int K,
+                                const float* scale_g, const float* scale_w, int epilogue, const void* residual, int ldr,
+                                const void* pre_act_in, int ldu, const void* At, int ldat, const void* Wt, int ldwt, int Kt,
+                                void* Cq, int ldcq, int fmt_out, const float* scale_out, unsigned int* amax, void* stream) {
+    if (M <= 0 || N <= 0 || K <= 0 || (K % 128) || (N % 4) || (ldg % 16) || (ldw % 16) || (ldc % 4) || ldg < K || ldw < K || ldc < N) return VT_ERR_BAD_SHAPE;
+    if (scale_g == nullptr || scale_w == nullptr) return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)G) | ((uintptr_t)WT)) & 15 || (((uintptr_t)C) & 7)) return VT_ERR_BAD_ALIGN;
+    if ((fmt_g != FMT_E4M3 && fmt_g != FMT_E5M2) || (fmt_out != FMT_E4M3 && fmt_out != FMT_E5M2)) return VT_ERR_UNSUPPORTED;
+    if (epilogue != EPI_BIAS && epilogue != EPI_DGELU && epilogue != EPI_GATED_RES) return VT_ERR_UNSUPPORTED;
+    if (epilogue == EPI_DGELU && (pre_act_in == nullptr || ldu < N || (ldu % 4) || (((uintptr_t)pre_act_in) & 7))) return VT_ERR_BAD_SHAPE;
+    if (epilogue == EPI_GATED_RES && (residual == nullptr || ldr < N || (ldr % 4) || (((uintptr_t)residual) & 7))) return VT_ERR_BAD_SHAPE;
+    if (Kt < 0 || Kt > 64 || (Kt % 32)) return VT_ERR_BAD_SHAPE;
+    if (Kt > 0 && (At == nullptr || Wt == nullptr || ldat < Kt || ldwt < Kt || (ldat % 8) || (ldwt % 8))) return VT_ERR_BAD_SHAPE;
+    if (Kt > 0 && ((((uintptr_t)At) | ((uintptr_t)Wt)) & 15)) return VT_ERR_BAD_ALIGN;
+    if (Cq != nullptr && epilogue != EPI_DGELU) return VT_ERR_UNSUPPORTED;
+    if (Cq != nullptr && (scale_out == nullptr || amax == nullptr || ldcq < N || (ldcq % 4))) return VT_ERR_BAD_SHAPE;
+    if (Cq != nullptr && (((uintptr_t)Cq) & 3)) return VT_ERR_BAD_ALIGN;
+    GemmMxParams p{};
+    p.g.C = C; p.g.R = (const bf16_t*)residual; p.g.U = (const bf16_t*)pre_act_in; p.g.M = M; p.g.N = N; p.g.K = K; p.g.ldc = ldc;
+    p.g.ldr = ldr; p.g.ldu = ldu; p.g.S = 1; p.g.r_mod = 0; p.g.splits = 1;
+    p.A = (const unsigned char*)G; p.W = (const unsigned char*)WT; p.lda = ldg; p.ldw = ldw; p.scale_a = scale_g; p.scale_w = scale_w;
+    p.At = (const bf16_t*)At; p.Wt = (const bf16_t*)Wt; p.ldat = ldat; p.ldwt = ldwt; p.Kt = Kt;
+    p.Cq = (unsigned char*)Cq; p.ldcq = ldcq; p.scale_out = scale_out; p.amax = amax;
+    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    hipStream_t st = (hipStream_t)stream;
+    const bool g5 = fmt_g == FMT_E5M2, o5 = fmt_out == FMT_E5M2;
+    if (epilogue == EPI_BIAS) {
+        if (g5) launch_mxfp8_dx<EPI_BIAS, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8_dx<EPI_BIAS, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+    } else if (epilogue == EPI_GATED_RES) {
+        if (g5) launch_mxfp8_dx<EPI_GATED_RES, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8_dx<EPI_GATED_RES, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+    } else if (g5) {
+        if (o5) launch_mxfp8_dx<EPI_DGELU, FMT_E5M2, FMT_E5M2>(p, tiles, st); else launch_mxfp8_dx<EPI_DGELU, FMT_E5M2, FMT_E4M3>(p, tiles, st);
+    } else {
+        if (o5) launch_mxfp8_dx<EPI_DGELU, FMT_E4M3, FMT_E5M2>(p, tiles, st); else launch_mxfp8_dx<EPI_DGELU, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+    }
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
 // ---- bf16 -> e4m3 with a device scale (delayed scaling: the scale was fixed before this forward), amax of the input into a slot ----
+template <int FMT>
 __global__ __launch_bounds__(256) void cast_fp8_scaled_kernel(const bf16_t* x, long long ldx, unsigned char* y, long long ldy, bf16_t* cp,
                                                               long long ldcp, long long M, int K, int L, int Lj, int off, const float* scale,
                                                               unsigned int* amax_bits) {
@@ -233,28 +325,90 @@ __global__ __launch_bounds__(256) void cast_fp8_scaled_kernel(const bf16_t* x, l
         unpack8(raw, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[j]));
-        *(u32x2*)(y + m * ldy + c) = (u32x2){e4m3x4(v, sc), e4m3x4(v + 4, sc)};
+        *(u32x2*)(y + m * ldy + c) = (u32x2){fp8x4<FMT>(v, sc), fp8x4<FMT>(v + 4, sc)};
     }
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(amax_bits, __float_as_uint(mx));
+    amax_publish_block(amax_bits, mx);
 }
 // Row m of y (and of the bf16 copy cp, if not null) comes from row (m / L) * Lj + off + m % L of x (L = 0: row m) -- one stream's rows
 // of a joint [B * Lj, K] buffer.  y = satfinite(RNE(x / scale[0])); max |x| into amax (uint32 float bits, accumulated).
-extern "C" int vt_cast_fp8_scaled(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
-                                  int Lj, int off, const float* scale, unsigned int* amax, void* stream) {
+static int cast_fp8_launch(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
+                           int Lj, int off, int fmt, const float* scale, unsigned int* amax, void* stream) {
     if (M <= 0 || K <= 0 || (K % 8) || (ldx % 8) || (ldy % 8) || ldx < K || ldy < K || scale == nullptr || amax == nullptr) return VT_ERR_BAD_SHAPE;
     if (cp != nullptr && (ldcp % 8 || ldcp < K)) return VT_ERR_BAD_SHAPE;
     if (L < 0 || (L > 0 && (Lj < L || off < 0 || off + L > Lj))) return VT_ERR_BAD_SHAPE;
     if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 7) || (((uintptr_t)cp) & 15)) return VT_ERR_BAD_ALIGN;
+    if (fmt != FMT_E4M3 && fmt != FMT_E5M2) return VT_ERR_UNSUPPORTED;
     const long long b = (M * (K >> 3) + 255) / 256;
     const unsigned blocks = (unsigned)(b > 4096 ? 4096 : b);
-    hipLaunchKernelGGL(cast_fp8_scaled_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (unsigned char*)y, ldy,
-                       (bf16_t*)cp, ldcp, M, K, L, Lj, off, scale, amax);
+    if (fmt == FMT_E5M2)
+        hipLaunchKernelGGL(cast_fp8_scaled_kernel<FMT_E5M2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
+                           (unsigned char*)y, ldy, (bf16_t*)cp, ldcp, M, K, L, Lj, off, scale, amax);
+    else
+        hipLaunchKernelGGL(cast_fp8_scaled_kernel<FMT_E4M3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
+                           (unsigned char*)y, ldy, (bf16_t*)cp, ldcp, M, K, L, Lj, off, scale, amax);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+extern "C" int vt_cast_fp8_scaled(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
+                                  int Lj, int off, const float* scale, unsigned int* amax, void* stream) {
+    return cast_fp8_launch(x, ldx, y, ldy, cp, ldcp, M, K, L, Lj, off, FMT_E4M3, scale, amax, stream);
+}
+// vt_cast_fp8_scaled with the target format as an argument (0 = e4m3, 1 = e5m2: satfinite at +-57344): the gradient cast
+extern "C" int vt_cast_fp8_fmt(const void* x, long long ldx, void* y, long long ldy, void* cp, long long ldcp, long long M, int K, int L,
+                               int Lj, int off, int fmt, const float* scale, unsigned int* amax, void* stream) {
+    return cast_fp8_launch(x, ldx, y, ldy, cp, ldcp, M, K, L, Lj, off, fmt, scale, amax, stream);
+}
+
+// ---- y = x * gate[b(m), seg(m)] (vt_gate_mul, bit for bit) plus the fp8 copy of y and max |y|: the gated gradients of the backward ----
+template <int FMT>
+__global__ __launch_bounds__(256) void gate_mul_fp8_kernel(const bf16_t* x, int ldx, bf16_t* y, int ldy, const float* g_txt, const float* g_vid,
+                                                          int bstride, long long M, int D, int S, int St, unsigned char* q, int ldq,
+                                                          const float* scale, unsigned int* amax_bits) {
+    const int nch = D >> 3;
+    const long long total = M * nch;
+    const float sc = scale[0];
+    float mx = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long m = i / nch;
+        const int c = (int)(i - m * nch);
+        const int b = (int)(m / S);
+        const int s = (int)(m - (long long)b * S);
+        const float* g = (s < St ? g_txt : g_vid) + (size_t)b * bstride + c * 8;
+        float v[8];
+        unpack8(*(const u32x4*)(x + (size_t)m * ldx + c * 8), v);
+        const f32x4 a = *(const f32x4*)g, bq = *(const f32x4*)(g + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] *= a[j]; v[j + 4] *= bq[j]; }
+        const u32x4 out = pack8(v);
+        *(u32x4*)(y + (size_t)m * ldy + c * 8) = out;
+        unpack8(out, v);                                   // the bf16 values as written
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[j]));
+        *(u32x2*)(q + (size_t)m * ldq + c * 8) = (u32x2){fp8x4<FMT>(v, sc), fp8x4<FMT>(v + 4, sc)};
+    }
+    amax_publish_block(amax_bits, mx);
+}
+// x, y, gates, M, D, S, St as vt_gate_mul; q: fp8 [M, ldq] = satfinite(RNE(y / scale[0])) in format fmt (0 = e4m3, 1 = e5m2);
+// max |y| into amax (uint32 float bits, accumulated)
+extern "C" int vt_gate_mul_fp8(const void* x, int ldx, void* y, int ldy, const float* g_txt, const float* g_vid, int bstride, long long M,
+                               int D, int S, int St, void* q, int ldq, int fmt, const float* scale, unsigned int* amax, void* stream) {
+    if (M <= 0 || D <= 0 || (D % 8) || (ldx % 8) || (ldy % 8) || (ldq % 8) || ldx < D || ldy < D || ldq < D || (bstride % 4) || S <= 0)
+        return VT_ERR_BAD_SHAPE;
+    if (q == nullptr || scale == nullptr || amax == nullptr) return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)g_txt) | ((uintptr_t)g_vid)) & 15 || (((uintptr_t)q) & 7)) return VT_ERR_BAD_ALIGN;
+    if (fmt != FMT_E4M3 && fmt != FMT_E5M2) return VT_ERR_UNSUPPORTED;
+    const long long total = M * (D >> 3);
+    const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    if (fmt == FMT_E5M2)
+        hipLaunchKernelGGL(gate_mul_fp8_kernel<FMT_E5M2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy,
+                           g_txt, g_vid, bstride, M, D, S, St, (unsigned char*)q, ldq, scale, amax);
+    else
+        hipLaunchKernelGGL(gate_mul_fp8_kernel<FMT_E4M3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (bf16_t*)y, ldy,
+                           g_txt, g_vid, bstride, M, D, S, St, (unsigned char*)q, ldq, scale, amax);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
 // ---- delayed scaling: one thread per site rolls its amax history, sets the scale for the next forward and clears the slot ----
-__global__ void fp8_scale_update_kernel(unsigned int* amax_bits, float* history, float* scale, int n, int H) {
+__global__ void fp8_scale_update_kernel(unsigned int* amax_bits, float* history, float* scale, int n, int H, float fmax) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float* h = history + (size_t)i * H;
@@ -265,12 +419,18 @@ __global__ void fp8_scale_update_kernel(unsigned int* amax_bits, float* history,
         mx = fmaxf(mx, v);
     }
     h[0] = __uint_as_float(amax_bits[i]);
-    scale[i] = mx > 0.f ? __fdiv_rn(mx, 448.0f) : 1.0f;
+    scale[i] = mx > 0.f ? __fdiv_rn(mx, fmax) : 1.0f;
     amax_bits[i] = 0u;
 }
 // amax: uint32 [n] (float bits); history: fp32 [n, H], newest first; scale: fp32 [n] = max(history) / 448 (1 if that is 0).
 extern "C" int vt_fp8_scale_update(unsigned int* amax, float* history, float* scale, int n, int H, void* stream) {
     if (n <= 0 || H <= 0 || amax == nullptr || history == nullptr || scale == nullptr) return VT_ERR_BAD_SHAPE;
-    hipLaunchKernelGGL(fp8_scale_update_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, amax, history, scale, n, H);
+    hipLaunchKernelGGL(fp8_scale_update_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, amax, history, scale, n, H, 448.0f);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+// the same with the format's largest finite value as the divisor: scale = max(history) / fmax (448: e4m3, 57344: e5m2)
+extern "C" int vt_fp8_scale_update_fmax(unsigned int* amax, float* history, float* scale, int n, int H, float fmax, void* stream) {
+    if (n <= 0 || H <= 0 || amax == nullptr || history == nullptr || scale == nullptr || !(fmax > 0.f)) return VT_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(fp8_scale_update_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, amax, history, scale, n, H, fmax);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void ln_modulate_fwd_kernel(LnParams p) {
     }
     if constexpr (Q) {
         qmax = wave_max(qmax);
-        if (lane == 0) atomicMax(p.amax, __float_as_uint(qmax));
+        if (lane == 0) amax_publish(p.amax, qmax);
     }
 }
 

@@ -20,6 +20,13 @@ vt_fp8_scale_update launch at its start).  The producer of each quantised input 
 modulate, the fc1 / linear1 GELU epilogue, the attention-output split); the first forward (and the first after load_state_dict or a change
 of ``fp8``) has no history and scales just in time.  LoRA sites keep their K-extension columns in bf16 (the GEMM's bf16 tail).  The
 backward is that of ``"weights"`` mode: bf16, from the saved bf16 activations and the de-quantised weights.
+``fp8="mfma", fp8_dgrad=True`` (or ``"e5m2"`` / ``"e4m3"``, the format the gradients are quantised to) additionally runs every
+INPUT-GRADIENT product dX = g W of those Linears on the same matrix cores (vt_gemm_mxfp8_dx): the quantised output gradient against the
+byte-transposed E4M3 weight, one delayed-scaling site per gradient tensor that feeds such a product (per double block and stream d(qkv),
+gated d(proj out), gated d(fc2 out), d(u); per single block gated d(linear2 out), d(qkv), d(u)), scales updated by one launch at the
+start of each backward.  The gated gradients are quantised by the gate multiply (vt_gate_mul_fp8), d(u) by the dGELU epilogue of the
+product that makes it, d(qkv) by one cast pass.  Parameter gradients keep reading the bf16 gradients; the forward is untouched (beyond the
+reference, which never quantises gradients).
 
 NOT built (recorded in DESIGN.md): the embedders / token refiner / final layer of HYVideoDiffusionTransformer, the diffusers
 ``HunyuanVideoTransformer3DModel`` key map and LoRA wrappers of the shipped recipe, (the head_dim-128 attention backward is atomics-only: no dQ hand-off chains yet).  Padding text rows attend to the valid keys here
@@ -115,7 +122,8 @@ class HunyuanBlocks(FlatParamModule):
 
     def __init__(self, hidden_size: int = 3072, heads_num: int = 24, mlp_width_ratio: float = 4.0, mm_double_blocks_depth: int = 20,
                  mm_single_blocks_depth: int = 40, fp8: bool = False, lora_rank: int = 0, lora_alpha: float = 1.0,
-                 shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None, fp8_amax_history: int = 16):
+                 shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None, fp8_amax_history: int = 16,
+                 fp8_dgrad=False):
         super().__init__()
         if hidden_size // heads_num != 128 or hidden_size % 128:
             raise ValueError("HunyuanVideo heads are 128 wide")
@@ -123,6 +131,7 @@ class HunyuanBlocks(FlatParamModule):
             raise ValueError("fp8_amax_history: at least one recorded amax")
         self.hidden_size, self.heads_num, self.ratio = hidden_size, heads_num, mlp_width_ratio
         self.fp8_amax_history = fp8_amax_history
+        self._fp8_dgrad = False
         self.n_double, self.n_single, self.fp8 = mm_double_blocks_depth, mm_single_blocks_depth, fp8
         sh: Dict[str, tuple] = {}
         for i in range(mm_double_blocks_depth):
@@ -133,6 +142,7 @@ class HunyuanBlocks(FlatParamModule):
         # LoRA mode: the block weights stay frozen (no fp32 master, no gradients, no dW GEMMs); only the adapters train
         self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha) if lora_rank > 0 else None
         self.sp_group = None
+        self.fp8_dgrad = fp8_dgrad
 
     @property
     def fp8(self):
@@ -145,8 +155,36 @@ class HunyuanBlocks(FlatParamModule):
         if mode == "mfma" and (self.hidden_size % 128 or int(self.hidden_size * self.ratio) % 128):
             raise ValueError(f"fp8='mfma': the MX-fp8 GEMM needs every block Linear's input width (hidden_size {self.hidden_size}, MLP width "
                              f"{int(self.hidden_size * self.ratio)}) to be a multiple of 128")
+        if mode != "mfma" and getattr(self, "_fp8_dgrad", False):
+            raise ValueError(f"fp8={mode!r}: fp8_dgrad={self._fp8_dgrad!r} needs fp8='mfma' (set fp8_dgrad = False first)")
         self._fp8 = mode
         self.fp8_reset()
+
+    @property
+    def fp8_dgrad(self):
+        """False, or the format the output gradients are quantised to for the fp8 dX products: True / 'e5m2', 'e4m3'"""
+        return self._fp8_dgrad
+
+    @fp8_dgrad.setter
+    def fp8_dgrad(self, mode):
+        if not any(mode is v for v in (False, True)) and mode not in ("e5m2", "e4m3"):
+            raise ValueError(f"fp8_dgrad={mode!r}: one of False, True / 'e5m2', 'e4m3'")
+        if mode and self._fp8 != "mfma":
+            raise ValueError(f"fp8_dgrad={mode!r}: the fp8 input-gradient products belong to fp8='mfma' (fp8={self._fp8!r})")
+        self._fp8_dgrad = mode
+        self._packed = None                 # the transposed operands change: fp8 bytes instead of bf16 copies
+        self.fp8_reset()
+
+    @property
+    def fp8_grad_format(self):
+        """the gradient format: None, 'e5m2' or 'e4m3'"""
+        return None if not self._fp8_dgrad else ("e4m3" if self._fp8_dgrad == "e4m3" else "e5m2")
+
+    @property
+    def n_fp8_grad_sites(self) -> int:
+        """gradient sites of fp8_dgrad: per double block and stream d(qkv), gated d(proj out), gated d(fc2 out), d(u); per single block
+        gated d(linear2 out), d(qkv), d(u)"""
+        return 8 * self.n_double + 3 * self.n_single
 
     @property
     def n_fp8_sites(self) -> int:
@@ -154,8 +192,9 @@ class HunyuanBlocks(FlatParamModule):
         return 8 * self.n_double + 2 * self.n_single
 
     def fp8_reset(self):
-        """forget the delayed-scaling history: the next fp8='mfma' forward scales just in time and seeds it"""
+        """forget the delayed-scaling history: the next fp8='mfma' forward (and fp8_dgrad backward) scales just in time and seeds it"""
         self._fp8_state = None
+        self._fp8_grad_state = None
 
     def fp8_state(self):
         """(amax, history, scale) device tensors of the activation sites, created (unseeded) on first use"""
@@ -165,6 +204,16 @@ class HunyuanBlocks(FlatParamModule):
             st = SimpleNamespace(amax=torch.zeros(n, dtype=F32, device=self.device), history=torch.zeros(n, H, dtype=F32, device=self.device),
                                  scale=torch.ones(n, dtype=F32, device=self.device), seeded=False)
             self._fp8_state = st
+        return st
+
+    def fp8_grad_state(self):
+        """(amax, history, scale) device tensors of the gradient sites (fp8_dgrad), created (unseeded) on first use"""
+        st = self._fp8_grad_state
+        if st is None or st.amax.device != self.device:
+            n, H = self.n_fp8_grad_sites, self.fp8_amax_history
+            st = SimpleNamespace(amax=torch.zeros(n, dtype=F32, device=self.device), history=torch.zeros(n, H, dtype=F32, device=self.device),
+                                 scale=torch.ones(n, dtype=F32, device=self.device), seeded=False)
+            self._fp8_grad_state = st
         return st
 
     def load_state_dict(self, sd, strict: bool = True, **kw):
@@ -244,8 +293,10 @@ def _packed_hy(model: HunyuanBlocks) -> SimpleNamespace:
     ver = -1 if model.train_state is None else model.train_state.version
     if model._packed is not None and model._packed_version == ver:
         return model._packed
-    P = SimpleNamespace(wt={}, w={}, b={}, q={})
+    P = SimpleNamespace(wt={}, w={}, b={}, q={}, qt={})
     fb = model.flat_bf16
+    train = model.train_state is not None or (model.lora is not None and model.lora.train_state is not None)
+    dgrad = model.fp8 == "mfma" and bool(model.fp8_dgrad)
     with torch.no_grad():
         for n, shp in model.shapes.items():
             if n.endswith(".weight") and len(shp) == 2:
@@ -257,7 +308,9 @@ def _packed_hy(model: HunyuanBlocks) -> SimpleNamespace:
                     P.w[n] = w
                     if (model.fp8 == "matmul" and n.endswith("_attn_qkv.weight")) or (model.fp8 == "mfma" and n.endswith(_MFMA_LINEARS)):
                         P.q[n] = (wq, sw)               # mfma: linear1's two row ranges share the tensor's one scale
-                if (model.train_state is not None or (model.lora is not None and model.lora.train_state is not None)) and not lora_site:
+                        if dgrad and train:                                 # fp8 dX: the byte-transposed E4M3 weight, same scale
+                            P.qt[n] = wq.view(torch.uint8).t().contiguous().view(ops.FP8)
+                if train and not lora_site and n not in P.qt:        # fp8_dgrad: nothing reads a bf16 transpose of those Linears
                     P.wt[n] = ops.transpose(w)
     model._packed, model._packed_version = P, ver
     return P
@@ -274,10 +327,13 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
     # The frozen base weight fills all but 64 columns of W_ext: when only the ADAPTERS changed (an optimizer step in LoRA mode: the base weights'
     # version stands still) the previous W_ext / W_ext^T are kept and only their extension columns / rows are rewritten -- re-copying and
     # re-transposing 3072 x 9216 base weights per site and step was 9 ms of the step.
-    base_key = (id(_packed_hy(model)), model.fp8)             # a new base pack (weights loaded / trained / fp8 switched) invalidates the copies
+    base_key = (id(_packed_hy(model)), model.fp8, model.fp8_dgrad)             # a new base pack (weights loaded / trained / fp8 switched) invalidates the copies
     prev = L._packed if (L._packed is not None and getattr(L, "_packed_base", None) == base_key) else None
     D, r = L.D, L.r
     dev = L.flat_bf16.device
+    # fp8_dgrad: the base dX product reads the fp8 transposed weight (_packed_hy's qt), so W_ext^T keeps only its EXT extension rows
+    # (scaling B^T, for dt = g (scaling B)); `to` = the first extension row of the W_ext^T stacks
+    to = 0 if (model.fp8 == "mfma" and model.fp8_dgrad) else D
     if prev is None:
         # Stacked storage: the modules with three adapters (qkv / linear1) and those with one (proj) live in two arrays each, so that the
         # per-step refresh of the extension columns and the gradient scatter are a handful of batched kernels instead of six tiny ones per
@@ -299,8 +355,8 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
         P.idx3 = [torch.tensor([site_of[(m_, t)] for m_ in mods3], dtype=torch.long, device=dev) for t in ("q", "k", "v")]
         P.idx1 = torch.tensor([site_of[(m_, "")] for m_ in mods1], dtype=torch.long, device=dev)
         n3, n1 = len(mods3), len(mods1)
-        P.W3 = torch.zeros(n3, 3 * D, D + EXT, dtype=BF16, device=dev); P.WT3 = torch.zeros(n3, D + EXT, 3 * D, dtype=BF16, device=dev)
-        P.W1 = torch.zeros(n1, D, D + EXT, dtype=BF16, device=dev); P.WT1 = torch.zeros(n1, D + EXT, D, dtype=BF16, device=dev)
+        P.W3 = torch.zeros(n3, 3 * D, D + EXT, dtype=BF16, device=dev); P.WT3 = torch.zeros(n3, to + EXT, 3 * D, dtype=BF16, device=dev)
+        P.W1 = torch.zeros(n1, D, D + EXT, dtype=BF16, device=dev); P.WT1 = torch.zeros(n1, to + EXT, D, dtype=BF16, device=dev)
         P.A3 = torch.zeros(n3 + n1, EXT, D, dtype=BF16, device=dev); P.A3T = torch.zeros(n3 + n1, D, EXT, dtype=BF16, device=dev)
         P.DB3 = torch.zeros(n3, 3 * D, EXT, dtype=F32, device=dev); P.DB1 = torch.zeros(n1, D, EXT, dtype=F32, device=dev)      # gradient staging (fp32)
         P.DA = torch.zeros(n3 + n1, EXT, D, dtype=F32, device=dev)
@@ -312,7 +368,8 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
                     if w is None:
                         w = model.flat(model.flat_bf16, mod + ".weight")
                     Wst[i][:, :D] = w[:nrows]
-                    WTst[i][:D] = ops.transpose(w[:nrows])
+                    if to:
+                        WTst[i][:D] = ops.transpose(w[:nrows])
                     k = i + (0 if grp == 0 else n3)
                     P.wext[mod], P.wtext[mod], P.a3[mod], P.a3t[mod] = Wst[i], WTst[i], P.A3[k], P.A3T[k]
                     P.db[mod], P.da[mod] = DBst[i], P.DA[k]
@@ -327,13 +384,13 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
             for j in range(3):
                 sb, a = sB_all[P.idx3[j]], A_all[P.idx3[j]]                                       # [n3, D, r], [n3, r, D]
                 P.W3[:, j * D:(j + 1) * D, D + j * r:D + (j + 1) * r] = sb
-                P.WT3[:, D + j * r:D + (j + 1) * r, j * D:(j + 1) * D] = sb.transpose(1, 2)
+                P.WT3[:, to + j * r:to + (j + 1) * r, j * D:(j + 1) * D] = sb.transpose(1, 2)
                 P.A3[:n3, j * r:(j + 1) * r] = a
                 P.A3T[:n3, :, j * r:(j + 1) * r] = a.transpose(1, 2)
             if len(P.mods1):
                 sb, a = sB_all[P.idx1], A_all[P.idx1]
                 P.W1[:, :, D:D + r] = sb
-                P.WT1[:, D:D + r] = sb.transpose(1, 2)
+                P.WT1[:, to:to + r] = sb.transpose(1, 2)
                 P.A3[n3:, :r] = a
                 P.A3T[n3:, :, :r] = a.transpose(1, 2)
         else:                                                       # irregular flat layout (r D not a multiple of 8): adapter by adapter
@@ -343,7 +400,7 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
                     dot = "." + t if t else ""
                     sb = (L._plist[f"{mod}.lora_B{dot}.weight"].float() * L.scaling).to(BF16)          # [D, r]
                     wext[j * D:(j + 1) * D, D + j * r:D + (j + 1) * r] = sb
-                    wtext[D + j * r:D + (j + 1) * r, j * D:(j + 1) * D] = sb.t()
+                    wtext[to + j * r:to + (j + 1) * r, j * D:(j + 1) * D] = sb.t()
                     a = L._plist[f"{mod}.lora_A{dot}.weight"]                                           # [r, D]
                     a3[j * r:(j + 1) * r] = a
                     a3t[:, j * r:(j + 1) * r] = a.t()
@@ -373,6 +430,10 @@ class _HYRun(_STRun):
         self.q8 = model.fp8 == "mfma"   # fp8="mfma": block Linears' forward on vt_gemm_mxfp8
         self.q8s = None                 # (amax, history, scale) of the activation sites, set by forward()
         self.jit = False                # no history yet: every site scales just in time
+        self.dg = self.q8 and bool(model.fp8_dgrad)         # fp8_dgrad: the dX products on vt_gemm_mxfp8_dx
+        self.gdt, self.gfmax = (ops.FP8, 448.0) if model.fp8_grad_format == "e4m3" else (ops.FP8_E5M2, 57344.0)
+        self.g8s = None                 # (amax, history, scale) of the gradient sites, set by backward()
+        self.gjit = False
 
     # ---- fp8="mfma": activation sites and their delayed scales ----
     def qsite(self, site):
@@ -398,6 +459,64 @@ class _HYRun(_STRun):
             copy = None
         ops.cast_fp8_scaled(x, y, scale, amax, copy=copy, rows=rows)
         return y
+
+    # ---- fp8_dgrad: gradient sites ----
+    def gsite(self, site):
+        st = self.g8s
+        return st.scale[site:site + 1], st.amax[site:site + 1]
+
+    def gsteady(self, site):
+        """(scale, amax) for a PRODUCER to write the gradient site's fp8 copy with, or None when the site scales just in time"""
+        return None if self.gjit else self.gsite(site)
+
+    def grad_in(self, site, g, gq=None):
+        """the quantised gradient of site `site`: gq when its producer already wrote it, else cast from the bf16 g (just in time: amax pass,
+        scale from that amax -- which seeds the history --, cast; as fp8_in)"""
+        if gq is not None:
+            return gq
+        scale, amax = self.gsite(site)
+        y = torch.empty(g.shape[0], g.shape[1], dtype=self.gdt, device=self.dev)
+        if self.gjit:                   # once per reset, as fp8_in: this first cast serves as the amax pass (what it writes to y is overwritten)
+            ops.cast_fp8_fmt(g, y, scale, amax)
+            ops.fp8_scale_update_fmax(amax, self.g8s.history[site:site + 1], scale, self.gfmax)
+        ops.cast_fp8_fmt(g, y, scale, amax)
+        return y
+
+    def gate_mul_q(self, g, gate, bs, N, rps, site):
+        """(gg, ggq) = g * gate and its quantised copy for gradient site `site`, in one pass once the site has a history (ggq = None
+        without fp8_dgrad)"""
+        M = g.shape[0]
+        gg = self.E(M, N)
+        q = self.gsteady(site) if self.dg else None
+        if q is None:
+            ops.gate_mul(g, gg, gate, gate, bs, N, rps, 0)
+            return gg, (self.grad_in(site, gg) if self.dg else None)
+        ggq = torch.empty(M, N, dtype=self.gdt, device=self.dev)
+        ops.gate_mul_fp8(g, gg, gate, gate, bs, N, rps, 0, ggq, q[0], q[1])
+        return gg, ggq
+
+    def dx_gemm(self, gq, site, wname, dx, rows=None, cols=None, **kw):
+        """dx = epilogue((gq WqT^T) s_g s_w) on vt_gemm_mxfp8_dx; rows / cols = (lo, hi): that slice of the transposed weight [K_in, N_out]
+        (linear2's column ranges are its rows, linear1's row ranges its columns)"""
+        wqt, sw = self.P.qt[wname], self.P.q[wname][1]
+        if rows is not None:
+            wqt = wqt[rows[0]:rows[1]]
+        if cols is not None:
+            wqt = wqt[:, cols[0]:cols[1]]
+        ops.gemm_mxfp8_dx(gq, wqt, dx, self.gsite(site)[0], sw, **kw)
+        return dx
+
+    def dx_dgelu(self, gg, ggq, gsite, usite, wname, du, u, rows=None):
+        """du = (gg W) * gelu'(u) (rows: that row range of the transposed weight).  fp8_dgrad: from the quantised ggq of site `gsite` on the
+        fp8 matrix cores, returning the quantised du of site `usite` (written by the epilogue once the site has a history); else bf16, None"""
+        if not self.dg:
+            wt = self.P.wt[wname]
+            ops.gemm(gg, wt if rows is None else wt[rows[0]:rows[1]], du, None, epilogue=EPI_DGELU, pre_act_in=u)
+            return None
+        q = self.gsteady(usite)
+        duq = None if q is None else torch.empty(du.shape[0], du.shape[1], dtype=self.gdt, device=self.dev)
+        self.dx_gemm(ggq, gsite, wname, du, rows=rows, epilogue=EPI_DGELU, pre_act_in=u, out_fp8=None if q is None else (duq, q[0], q[1]))
+        return self.grad_in(usite, du, duq)
 
     def mx_gemm(self, xq, site, wname, y, bias, rows=None, **epi):
         """y = epilogue((xq Wq^T) sa sw + bias) on vt_gemm_mxfp8; rows = (lo, hi): that row range of the weight (linear1)"""
@@ -452,8 +571,23 @@ class _HYRun(_STRun):
         else:
             ops.gemm(xe, wext, y, bias, **epi)
 
-        def backward(g):
+        def backward(g, gq=None, gsite=None):
             L, r = self.lora, self.lora.r
+            if self.dg and q8 is not None:
+                # dx = (gq WqT^T) s + dt A3: dt = g (scaling B) in bf16, dt A3 through the GEMM's bf16 tail
+                dt = self.E(M, EXT)
+                ops.gemm(g, self.LP.wtext[mod], dt, None)       # fp8_dgrad: W_ext^T holds its extension rows only
+                if self.lts is not None:
+                    db, da = self.LP.db[mod], self.LP.da[mod]
+                    ops.linear_dw(g, xe[:, D:], db, accumulate=False)
+                    ops.linear_dw(dt, xe[:, :D], da, accumulate=False)
+                    self._lora_ran.add(mod)
+                    if not self.LP.regular:
+                        self._lora_scatter_one(mod)
+                dx = self.E(M, D)
+                self.dx_gemm(self.grad_in(gsite, g, gq), gsite, q8[2], dx, cols=q8[3], tail=(dt, self.LP.a3t[mod]))
+                return dx
+            assert not self.dg, "fp8_dgrad: every adapted Linear runs on vt_gemm_mxfp8 (W_ext^T holds no base rows)"
             dxe = self.E(M, D + EXT)
             ops.gemm(g, self.LP.wtext[mod], dxe, None)                  # [dx | dt] = g W_ext
             if self.lts is not None:
@@ -499,7 +633,7 @@ class _HYRun(_STRun):
             GA.index_add_(0, P.idx1, P.DA[n3:, :r])
         self._lora_ran.clear()
 
-    def linear(self, x: _Var, wname: str, bname, residual=None, wspan=None, out=None, site=None, xq=None) -> _Var:
+    def linear(self, x: _Var, wname: str, bname, residual=None, wspan=None, out=None, site=None, xq=None, gsite=None) -> _Var:
         """block Linear without epilogue (the qkv projections).  Adapted module (LoRA): one GEMM over the K-extended operands.  fp8=True: the
         FORWARD product on the fp8 matrix cores (activation quantised per tensor here, weight copy + scale from _packed_hy).  Parameter
         gradients only when the block weights train."""
@@ -516,7 +650,8 @@ class _HYRun(_STRun):
             if self.save:
                 def bwd_linear_lora():
                     self.colsum(yv.g, bname, y.shape[1])
-                    self.acc(x, bw(yv.g))
+                    gq, yv.gq = yv.gq, None
+                    self.acc(x, bw(yv.g, gq, gsite))
                 self.tape.append(bwd_linear_lora)
             return yv
         w = self.W(wname)
@@ -536,7 +671,11 @@ class _HYRun(_STRun):
                 self.colsum(g, bname, w.shape[0])
                 self.dW(g, x.d, self.G(wname))
                 dx = self.E(M, w.shape[1])
-                ops.gemm(g, self.P.wt[wname], dx, None)
+                if self.dg and mx:
+                    gq, yv.gq = yv.gq, None
+                    self.dx_gemm(self.grad_in(gsite, g, gq), gsite, wname, dx)
+                else:
+                    ops.gemm(g, self.P.wt[wname], dx, None)
                 self.acc(x, dx)
             self.tape.append(bwd_linear)
         return yv
@@ -572,7 +711,7 @@ class _HYRun(_STRun):
             self.tape.append(bwd_ln_mod_ext)
         return yv if site is None else (yv, yq)
 
-    def mlp(self, x: _Var, pre: str, residual=None, gate=None, dgate=None, sites=None, xq=None) -> _Var:
+    def mlp(self, x: _Var, pre: str, residual=None, gate=None, dgate=None, sites=None, xq=None, gsites=None) -> _Var:
         """_STRun.mlp with the parameter gradients behind the frozen-weights switch; fp8="mfma": sites = (fc1 input, fc2 input), xq the
         e4m3 fc1 input (or None), the GELU epilogue of fc1 writing fc2's e4m3 input"""
         M = x.d.shape[0]
@@ -601,16 +740,21 @@ class _HYRun(_STRun):
                 self.acc(residual, g_)
                 if dgate is not None:
                     ops.group_colsum(g_, None, y=branch, out2=dgate, D=Dout, S=gate[2], St=0, grouped=True, o_bstride=gate[1], o_segstride=0)
-                gg = self.E(M, Dout)
-                ops.gate_mul(g_, gg, gate[0], gate[0], gate[1], Dout, gate[2], 0)
+                # fp8_dgrad: gated d(fc2 out) and d(u) are quantised by their producers, both dX products run in fp8
+                g2, g1 = gsites if self.dg else (None, None)
+                gg, ggq = self.gate_mul_q(g_, gate[0], gate[1], Dout, gate[2], g2)
                 self.colsum(gg, pre + "fc2.bias", Dout)
                 self.dW(gg, ga, self.G(pre + "fc2.weight"))
                 du = self.E(M, H4)
-                ops.gemm(gg, self.P.wt[pre + "fc2.weight"], du, None, epilogue=EPI_DGELU, pre_act_in=u)
+                duq = self.dx_dgelu(gg, ggq, g2, g1, pre + "fc2.weight", du, u)
+                del ggq
                 self.colsum(du, pre + "fc1.bias", H4)
                 self.dW(du, x.d, self.G(pre + "fc1.weight"))
                 dx = self.E(M, w1.shape[1])
-                ops.gemm(du, self.P.wt[pre + "fc1.weight"], dx, None)
+                if self.dg:
+                    self.dx_gemm(duq, g1, pre + "fc1.weight", dx)
+                else:
+                    ops.gemm(du, self.P.wt[pre + "fc1.weight"], dx, None)
                 self.acc(x, dx)
             self.tape.append(bwd_mlp)
         return yv
@@ -627,7 +771,7 @@ class _HYRun(_STRun):
             self.tape.append(bwd_modulation)
         return mod, dmod
 
-    def glinear(self, x: _Var, wname: str, bname: str, residual: _Var, gate, dgate, rps: int, bs: int, site=None, xq=None) -> _Var:
+    def glinear(self, x: _Var, wname: str, bname: str, residual: _Var, gate, dgate, rps: int, bs: int, site=None, xq=None, gsite=None) -> _Var:
         """y = residual + gate[b] * (x W^T + b)   (apply_gate, modulate_layers.py:49-66); adapted module: over the K-extended operands.
         fp8="mfma": the product from the e4m3 input xq of activation site `site`"""
         mod = wname[:-7]
@@ -652,20 +796,22 @@ class _HYRun(_STRun):
                 self.acc(residual, g_)
                 if dgate is not None:
                     ops.group_colsum(g_, None, y=branch, out2=dgate, D=N, S=rps, St=0, grouped=True, o_bstride=bs, o_segstride=0)
-                gg = self.E(M, N)
-                ops.gate_mul(g_, gg, gate, gate, bs, N, rps, 0)
+                gg, ggq = self.gate_mul_q(g_, gate, bs, N, rps, gsite)
                 self.colsum(gg, bname, N)
                 if adapted:
-                    self.acc(x, bw(gg))
+                    self.acc(x, bw(gg, ggq, gsite))
                 else:
                     self.dW(gg, x.d, self.G(wname))
                     dx = self.E(M, w.shape[1])
-                    ops.gemm(gg, self.P.wt[wname], dx, None)
+                    if ggq is not None:
+                        self.dx_gemm(ggq, gsite, wname, dx)
+                    else:
+                        ops.gemm(gg, self.P.wt[wname], dx, None)
                     self.acc(x, dx)
             self.tape.append(bwd_glinear)
         return yv
 
-    def qkv_to_joint(self, qkv: _Var, pre_q: str, pre_k: str, joint, djoint_ref, L: int, Lj: int, off: int, rope):
+    def qkv_to_joint(self, qkv: _Var, pre_q: str, pre_k: str, joint, djoint_ref, L: int, Lj: int, off: int, rope, gsite=None):
         """RMS q/k norm + rope + scatter into the joint [B*Lj, 3C] buffer; backward reads the joint gradient buffer djoint_ref[0]"""
         H = self.m.heads_num
         M = qkv.d.shape[0]
@@ -677,6 +823,8 @@ class _HYRun(_STRun):
                 dq = self.E(M, qkv.d.shape[1])
                 ops.qk_rmsnorm_rope128_bwd(djoint_ref[0], qkv.d, dq, gq, gk, rstd, self.G(pre_q), self.G(pre_k), H, L, Lj, off, rope)   # frozen: None
                 qkv.g = dq
+                if self.dg:                     # d(qkv): the one gradient site whose producer does not quantise -- one cast pass
+                    qkv.gq = self.grad_in(gsite, dq)
             self.tape.append(bwd_qkv_to_joint)
 
     def joint_attention(self, joint, B: int, Lj: int, kv_len, o_out, djoint_ref):
@@ -724,7 +872,8 @@ class _HYRun(_STRun):
 
     # ------------------------------------------------------------------------------------------------------------------
     def double_block(self, pre: str, img: _Var, txt: _Var, sv: _Var, B, Li, Lt, kv_len, rope, site0: int = 0):
-        """site0: the first of this block's 8 fp8 activation sites (per stream img, txt: qkv, proj, fc1, fc2 inputs)"""
+        """site0: the first of this block's 8 fp8 activation sites (per stream img, txt: qkv, proj, fc1, fc2 inputs) and of its 8 gradient
+        sites (fp8_dgrad; per stream d(qkv), gated d(proj out), gated d(fc2 out), d(u))"""
         D, H = self.m.hidden_size, self.m.heads_num
         C, Lj = D, Li + Lt
         bs = 6 * D
@@ -740,7 +889,7 @@ class _HYRun(_STRun):
             qs = site0 + 4 * si                                                     # this stream's qkv / proj / fc1 / fc2 input sites
             if q8:
                 xm, xq = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted, site=qs)
-                qkv = self.linear(xm, pre + s + "_attn_qkv.weight", pre + s + "_attn_qkv.bias", site=qs, xq=xq)
+                qkv = self.linear(xm, pre + s + "_attn_qkv.weight", pre + s + "_attn_qkv.bias", site=qs, xq=xq, gsite=qs)
                 del xq
             else:
                 xm = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted)
@@ -749,7 +898,7 @@ class _HYRun(_STRun):
         # the backward of the scatter must run AFTER the attention's backward has produced the joint gradient: push order = forward order
         for s in ("img", "txt"):
             x, L, off, sl, dsl, qkv, rp, qs = streams[s]
-            self.qkv_to_joint(qkv, pre + s + "_attn_q_norm.weight", pre + s + "_attn_k_norm.weight", joint, dj, L, Lj, off, rp)
+            self.qkv_to_joint(qkv, pre + s + "_attn_q_norm.weight", pre + s + "_attn_k_norm.weight", joint, dj, L, Lj, off, rp, gsite=qs)
         o = self.E(B * Lj, C)
         ov = self.joint_attention(joint, B, Lj, kv_len, o, dj)
         outs = {}
@@ -773,19 +922,22 @@ class _HYRun(_STRun):
                         ov.g = self.E(B * Lj, C)              # both streams' splits fill all of it
                     ov.g.view(B, Lj, C)[:, off:off + L].copy_(av.g.view(B, L, C))
                 self.tape.append(bwd_split)
-            x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs, site=qs + 1, xq=aq)
+            x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs, site=qs + 1, xq=aq,
+                               gsite=qs + 1)
             del aq
             if q8:
                 hm, hq = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs, site=qs + 2)
-                outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5), sites=(qs + 2, qs + 3), xq=hq)
+                outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5), sites=(qs + 2, qs + 3), xq=hq,
+                                   gsites=(qs + 2, qs + 3))
                 del hq
             else:
                 hm = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs)
                 outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5))
         return outs["img"], outs["txt"]
 
-    def single_block(self, pre: str, x: _Var, sv: _Var, B, Li, Lt, kv_len, rope, site0: int = 0):
-        """site0: this block's fp8 activation sites (linear1 input, linear2 input = site0 + 1)"""
+    def single_block(self, pre: str, x: _Var, sv: _Var, B, Li, Lt, kv_len, rope, site0: int = 0, gsite0: int = 0):
+        """site0: this block's fp8 activation sites (linear1 input, linear2 input = site0 + 1); gsite0: its gradient sites (fp8_dgrad:
+        gated d(linear2 out), d(qkv) = gsite0 + 1, d(u) = gsite0 + 2)"""
         D, H = self.m.hidden_size, self.m.heads_num
         M4 = int(D * self.m.ratio)
         Lj = Li + Lt
@@ -834,16 +986,24 @@ class _HYRun(_STRun):
                     gw, gb = self.G(pre + "linear1.weight"), self.G(pre + "linear1.bias")
                     ops.group_colsum(dqkv, gb[:3 * D], D=3 * D); ops.group_colsum(du, gb[3 * D:], D=M4)
                     self.dW(dqkv, xm.d, gw[:3 * D]); self.dW(du, xm.d, gw[3 * D:])
+                dqq, duq = qkvv.gq, catv.gq         # fp8_dgrad: left by their producers; both row ranges of linear1 are then
+                qkvv.gq = catv.gq = None            # column slices of its transposed fp8 weight
                 if adapted:
-                    dx = bw1(dqkv)
+                    dx = bw1(dqkv, dqq, gsite0 + 1)
                 else:
                     dx = self.E(M, D)
-                    ops.gemm(dqkv, self._wt_rows(pre + "linear1.weight", 0, 3 * D), dx, None)
+                    if self.dg:
+                        self.dx_gemm(dqq, gsite0 + 1, pre + "linear1.weight", dx, cols=(0, 3 * D))
+                    else:
+                        ops.gemm(dqkv, self._wt_rows(pre + "linear1.weight", 0, 3 * D), dx, None)
                 dx2 = self.E(M, D)
-                ops.gemm(du, self._wt_rows(pre + "linear1.weight", 3 * D, 3 * D + M4), dx2, None, epilogue=EPI_GATED_RES, residual=dx)
+                if self.dg:
+                    self.dx_gemm(duq, gsite0 + 2, pre + "linear1.weight", dx2, cols=(3 * D, 3 * D + M4), epilogue=EPI_GATED_RES, residual=dx)
+                else:
+                    ops.gemm(du, self._wt_rows(pre + "linear1.weight", 3 * D, 3 * D + M4), dx2, None, epilogue=EPI_GATED_RES, residual=dx)
                 self.acc(xm, dx2)
             self.tape.append(bwd_linear1)
-        self.qkv_to_joint(qkvv, pre + "q_norm.weight", pre + "k_norm.weight", joint, dj, Lj, Lj, 0, rope)
+        self.qkv_to_joint(qkvv, pre + "q_norm.weight", pre + "k_norm.weight", joint, dj, Lj, Lj, 0, rope, gsite=gsite0 + 1)
         ov = self.joint_attention(joint, B, Lj, kv_len, cat[:, :D], dj)
         # linear2 with the gated residual
         w2 = self.W(pre + "linear2.weight")
@@ -864,13 +1024,16 @@ class _HYRun(_STRun):
                 self.acc(x, g_)
                 if dmod is not None:
                     ops.group_colsum(g_, None, y=branch, out2=dsl(2), D=D, S=Lj, St=0, grouped=True, o_bstride=bs, o_segstride=0)
-                gg = self.E(M, D); ops.gate_mul(g_, gg, sl(2), sl(2), bs, D, Lj, 0)
+                gg, ggq = self.gate_mul_q(g_, sl(2), bs, D, Lj, gsite0)
                 self.colsum(gg, pre + "linear2.bias", D)
                 self.dW(gg, cat, self.G(pre + "linear2.weight"))
                 dcat = self.E(M, D + M4)
-                wt2 = self.P.wt[pre + "linear2.weight"]          # [D + M4, D]
-                ops.gemm(gg, wt2[:D], dcat[:, :D], None)                                     # d attn
-                ops.gemm(gg, wt2[D:], dcat[:, D:], None, epilogue=EPI_DGELU, pre_act_in=u)   # d u = (g W2[:, D:]) * gelu'(u)
+                if self.dg:                      # linear2's two column ranges are row slices of its transposed fp8 weight
+                    self.dx_gemm(ggq, gsite0, pre + "linear2.weight", dcat[:, :D], rows=(0, D))                     # d attn
+                else:
+                    ops.gemm(gg, self.P.wt[pre + "linear2.weight"][:D], dcat[:, :D], None)
+                # d u = (g W2[:, D:]) * gelu'(u) into the mlp columns (fp8_dgrad: with its quantised copy for linear1's product)
+                catv.gq = self.dx_dgelu(gg, ggq, gsite0, gsite0 + 2, pre + "linear2.weight", dcat[:, D:], u, rows=(D, D + M4))
                 catv.g = dcat
                 ov.g = dcat[:, :D]
             self.tape.append(bwd_linear2)
@@ -912,7 +1075,8 @@ class _HYRun(_STRun):
                 self.acc(iv, g[:, :Li].reshape(B * Li, D)); self.acc(tv, g[:, Li:].reshape(B * Lt, D))
             self.tape.append(bwd_cat)
         for i in range(m.n_single):
-            xv = self.single_block(f"single_blocks.{i}.", xv, svv, B, Li, Lt, kv_len, rope, site0=8 * m.n_double + 2 * i)
+            xv = self.single_block(f"single_blocks.{i}.", xv, svv, B, Li, Lt, kv_len, rope, site0=8 * m.n_double + 2 * i,
+                                   gsite0=8 * m.n_double + 3 * i)
         if self.q8:
             self.q8s.seeded = True
         self._out = xv
@@ -922,8 +1086,15 @@ class _HYRun(_STRun):
     def backward(self, dout):
         B, Lj, D = self._dims
         self._out.g = dout.to(BF16).reshape(B * Lj, D).contiguous()
+        if self.dg:                 # delayed scaling of the gradient sites: this backward's scales from the amaxes recorded so far
+            st = self.m.fp8_grad_state()
+            self.g8s, self.gjit = st, not st.seeded
+            if st.seeded:
+                ops.fp8_scale_update_fmax(st.amax, st.history, st.scale, self.gfmax)
         while self.tape:
             self.tape.pop()()
+        if self.dg:
+            self.g8s.seeded = True
         self.lora_scatter()
         iv, tv = self._in
         Li, Lt = iv.d.shape[0] // B, tv.d.shape[0] // B
@@ -945,7 +1116,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  mm_single_blocks_depth: int = 40, rope_dim_list=(16, 56, 56), qkv_bias: bool = True, qk_norm: bool = True, qk_norm_type: str = "rms",
                  guidance_embed: bool = False, text_projection: str = "single_refiner", use_attention_mask: bool = True,
                  text_states_dim: Optional[int] = None, text_states_dim_2: Optional[int] = None, fp8: bool = False, lora_rank: int = 0,
-                 lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, **unused):
+                 lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, fp8_dgrad=False, **unused):
         if text_projection != "single_refiner" or mlp_act_type != "gelu_tanh" or not qkv_bias or not qk_norm or qk_norm_type != "rms":
             raise NotImplementedError("only the shipped HunyuanVideo-T2V configuration (single_refiner, gelu_tanh, rms qk-norm) is built")
         if sum(rope_dim_list) != hidden_size // heads_num:
@@ -976,7 +1147,8 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
         after = {"final_layer.linear.weight": (pt * ph * pw * oc, D), "final_layer.linear.bias": (pt * ph * pw * oc,),
                  "final_layer.adaLN_modulation.1.weight": (2 * D, D), "final_layer.adaLN_modulation.1.bias": (2 * D,)}
         super().__init__(hidden_size, heads_num, mlp_width_ratio, mm_double_blocks_depth, mm_single_blocks_depth, fp8, lora_rank, lora_alpha,
-                         shapes_before=before, shapes_after=after, fp8_amax_history=fp8_amax_history)
+                         shapes_before=before, shapes_after=after, fp8_amax_history=fp8_amax_history,
+                         fp8_dgrad=fp8_dgrad)
         self.patch_size, self.in_channels, self.out_channels, self.guidance_embed = tuple(patch_size), in_channels, oc, guidance_embed
         self.text_states_dim, self.text_states_dim_2 = td, td2
 

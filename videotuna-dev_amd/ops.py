@@ -1156,6 +1156,94 @@ def fp8_scale_update(amax, history, scale):
     check(load_library().vt_fp8_scale_update(_amax_slot(amax), history.data_ptr(), scale.data_ptr(), n, H, _stream()), "vt_fp8_scale_update")
 
 
+FP8_E5M2 = torch.float8_e5m2
+FP8_FORMATS = {FP8: (0, 448.0), FP8_E5M2: (1, 57344.0)}      # dtype -> (format code of the C-ABI, largest finite value)
+
+
+def _fp8_code(t, name: str) -> int:
+    if t.dtype not in FP8_FORMATS:
+        raise ValueError(f"{name}: expected float8_e4m3fn or float8_e5m2, got {t.dtype}")
+    _req(t, t.dtype, name, 2)
+    return FP8_FORMATS[t.dtype][0]
+
+
+def gemm_mxfp8_dx(gq, wqt, out, scale_g, scale_w, *, epilogue: int = EPI_BIAS, residual: Optional[torch.Tensor] = None,
+                  pre_act_in: Optional[torch.Tensor] = None, tail=None, out_fp8=None):
+    """the input-gradient product of a Linear on the MX-scaled fp8 matrix cores: out bf16 [M, N] = epilogue((gq [M, K] @ wqt [N, K]^T)
+    * scale_g * scale_w [+ At @ Wt^T]).  gq: the quantised output gradient, float8_e5m2 or float8_e4m3fn; wqt: float8_e4m3fn, the
+    byte-transposed weight (row-strided slices allowed).  epilogue: EPI_BIAS (plain), EPI_DGELU (times gelu'(pre_act_in)) or
+    EPI_GATED_RES (+ residual).  tail as gemm_mxfp8.  out_fp8 = (Cq fp8 [M, N] of either format, scale, amax): EPI_DGELU only."""
+    fg = _fp8_code(gq, "gq")
+    _req(wqt, FP8, "wqt", 2); _req(out, BF16, "out", 2)
+    M, K, N = gq.shape[0], gq.shape[1], wqt.shape[0]
+    if wqt.shape[1] != K or out.shape[0] != M or out.shape[1] < N:
+        raise ValueError(f"gemm_mxfp8_dx: gq {tuple(gq.shape)}, wqt {tuple(wqt.shape)}, out {tuple(out.shape)}")
+    for t, name in ((residual, "residual"), (pre_act_in, "pre_act_in")):
+        if t is not None:
+            _req(t, BF16, name, 2)
+            if t.shape[0] < M or t.shape[1] < N:
+                raise ValueError(f"gemm_mxfp8_dx: {name} {tuple(t.shape)} for a [{M}, {N}] product")
+    At = Wt = None
+    Kt = 0
+    if tail is not None:
+        At, Wt = tail
+        _req(At, BF16, "tail A", 2); _req(Wt, BF16, "tail W", 2)
+        Kt = At.shape[1]
+        if Wt.shape[1] != Kt or At.shape[0] != M or Wt.shape[0] != N:
+            raise ValueError(f"gemm_mxfp8_dx: tail {tuple(At.shape)} x {tuple(Wt.shape)}^T for a [{M}, {N}] product")
+    cq = sq = am = None
+    fo = 0
+    if out_fp8 is not None:
+        cq, sq, am = out_fp8
+        fo = _fp8_code(cq, "out_fp8")
+        if cq.shape[0] != M or cq.shape[1] < N:
+            raise ValueError(f"gemm_mxfp8_dx: out_fp8 {tuple(cq.shape)} for a [{M}, {N}] product")
+        am = _amax_slot(am)
+    check(load_library().vt_gemm_mxfp8_dx(gq.data_ptr(), gq.stride(0), fg, wqt.data_ptr(), wqt.stride(0), out.data_ptr(), out.stride(0), M, N, K,
+                                          scale_g.data_ptr(), scale_w.data_ptr(), epilogue,
+                                          _p(residual), 0 if residual is None else residual.stride(0),
+                                          _p(pre_act_in), 0 if pre_act_in is None else pre_act_in.stride(0),
+                                          _p(At), 0 if At is None else At.stride(0), _p(Wt), 0 if Wt is None else Wt.stride(0), Kt,
+                                          _p(cq), 0 if cq is None else cq.stride(0), fo, _p(sq), am, _stream()), "vt_gemm_mxfp8_dx")
+    return out
+
+
+def cast_fp8_fmt(x, y, scale, amax, copy=None, rows=None):
+    """cast_fp8_scaled into y's format (float8_e4m3fn or float8_e5m2: satfinite at 448 / 57344)"""
+    _req(x, BF16, "x", 2)
+    fmt = _fp8_code(y, "y")
+    if copy is not None:
+        _req(copy, BF16, "copy", 2)
+    M, K = y.shape
+    L, Lj, off = rows if rows is not None else (0, 0, 0)
+    if x.shape[1] < K or (rows is None and x.shape[0] < M) or (rows is not None and (M % L or x.shape[0] < M // L * Lj)):
+        raise ValueError(f"cast_fp8_fmt: x {tuple(x.shape)} -> y {tuple(y.shape)}, rows {rows}")
+    check(load_library().vt_cast_fp8_fmt(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), _p(copy), 0 if copy is None else copy.stride(0),
+                                         M, K, L, Lj, off, fmt, scale.data_ptr(), _amax_slot(amax), _stream()), "vt_cast_fp8_fmt")
+    return y
+
+
+def gate_mul_fp8(x, y, g_txt, g_vid, bstride: int, D: int, S: int, St: int, q, scale, amax):
+    """gate_mul (y bit-equal to it) plus q fp8 [M, D] = satfinite(RNE(y / scale)) in q's format and max |y| into the amax slot"""
+    _req(x, BF16, "x", 2); _req(y, BF16, "y", 2)
+    fmt = _fp8_code(q, "q")
+    if x.shape[1] < D or y.shape[1] < D or q.shape[1] < D or y.shape[0] < x.shape[0] or q.shape[0] < x.shape[0]:
+        raise ValueError(f"gate_mul_fp8: x {tuple(x.shape)}, y {tuple(y.shape)}, q {tuple(q.shape)}, D {D}")
+    check(load_library().vt_gate_mul_fp8(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), g_txt.data_ptr(), g_vid.data_ptr(), bstride,
+                                         x.shape[0], D, S, St, q.data_ptr(), q.stride(0), fmt, scale.data_ptr(), _amax_slot(amax), _stream()),
+          "vt_gate_mul_fp8")
+
+
+def fp8_scale_update_fmax(amax, history, scale, fmax: float):
+    """fp8_scale_update with the format's largest finite value as the divisor: scale [n] = max(history) / fmax (448 e4m3, 57344 e5m2)"""
+    _req(history, torch.float32, "history", 2); _req(scale, torch.float32, "scale", 1)
+    n, H = history.shape
+    if amax.numel() != n or scale.numel() != n or not (amax.is_contiguous() and history.is_contiguous() and scale.is_contiguous()):
+        raise ValueError("fp8_scale_update_fmax: amax [n], history [n, H], scale [n], contiguous")
+    check(load_library().vt_fp8_scale_update_fmax(_amax_slot(amax), history.data_ptr(), scale.data_ptr(), n, H, float(fmax), _stream()),
+          "vt_fp8_scale_update_fmax")
+
+
 def qk_rmsnorm_rope128_fwd(qkv, out, gq, gk, rstd, H: int, L: int, Lout: int, row_off: int, rope=None, eps: float = 1e-6):
     """qkv bf16 [M, 3*H*128] -> out rows (m // L) * Lout + row_off + m % L: q^ | k^ | v.  rope = (cos, sin) fp32 [S_rope, 128] for the
     first S_rope positions of every sample"""

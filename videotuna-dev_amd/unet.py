@@ -636,11 +636,12 @@ def _trace_file():
 
 class _Var:
     """an activation [rows, C] (bf16, row stride may exceed C) and, during the backward pass, its gradient"""
-    __slots__ = ("d", "g", "ext", "shared", "g32")
+    __slots__ = ("d", "g", "ext", "shared", "g32", "gq")
 
     def __init__(self, d, ext=None, shared=False):
         self.d, self.g, self.ext = d, None, ext          # ext: the [rows, C + EXT] buffer d is the first C columns of (input of a LoRA'd Linear)
         self.g32 = None                                  # fp32 accumulator for a gradient summed over many layers (the image context)
+        self.gq = None                                   # fp8 copy of g left by its producer for an fp8 dX product (HunyuanVideo fp8_dgrad)
         self.shared = shared                             # several adapted Linears read this buffer (the text context): each keeps its own x A^T
 
 
