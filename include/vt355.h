@@ -251,6 +251,24 @@ int vt_diffusion_loss_bwd(const void* vpred, const void* noisy, const float* x0,
 int vt_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
              float beta2, float eps, float weight_decay, int step, float grad_scale, const int* guard, void* stream);
 
+/* Gradient clipping without a host round trip and without rewriting the gradients (Lightning's gradient_clip_val).
+ * vt_grad_sqnorm: read-only sweep over n fp32 values at any 4-byte aligned g; a FIXED grid of vt_grad_sqnorm_partials() (= 2048)
+ *   workgroups x 256 threads, workgroup b stores the sum of g^2 over its share to partials[slot * 2048 + b] (every workgroup
+ *   stores, zeros included).  No atomics: bit-identical from run to run.  Per thread one fp32 accumulator per 16-byte lane takes at
+ *   most ceil(ceil(n / 4) / (2048 * 256)) + 1 sequential additions, then 10 fp32 tree levels (4 lanes, 64-wide wave, 4 waves).
+ * vt_clip_finalize: sums partials[0 .. nslots * 2048) in double in a fixed order and stores record[0] = total_norm =
+ *   grad_scale * sqrt(sum), record[1] = clip_coef = min(1, max_norm / (total_norm + 1e-6))  (torch.nn.utils.clip_grad_norm_,
+ *   norm_type 2, error_if_nonfinite False: a NaN norm gives a NaN coefficient).
+ * vt_adamw_clip: vt_adamw on the gradient g * grad_scale * *clip_coef_dev (clip_coef_dev != NULL: the 'norm' algorithm) or
+ *   clamp(g * grad_scale, -clip_value, +clip_value) (clip_value > 0: the 'value' algorithm); neither: exactly vt_adamw; both:
+ *   VT_ERR_UNSUPPORTED. */
+int vt_grad_sqnorm_partials(void);
+int vt_grad_sqnorm(const float* g, long long n, float* partials, int slot, void* stream);
+int vt_clip_finalize(const float* partials, int nslots, float grad_scale, float max_norm, float* record, void* stream);
+int vt_adamw_clip(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
+                  float beta2, float eps, float weight_decay, int step, float grad_scale, const int* guard,
+                  const float* clip_coef_dev, float clip_value, void* stream);
+
 /* LoRA (peft LoraLayer, cogvideo_pl.py:143-149) */
 int vt_lora_down(const void* X, int ldx, const void* A, int lda, int R, void* T, int ldt, long long M, int K,
                  int zero_cols, void* stream);                   /* T[M,16] = X A^T ; T[:,16:16+zero_cols] = 0 */

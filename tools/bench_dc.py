@@ -9,9 +9,16 @@ kernel.  Prints one JSON line per part.
            img_cross_attention / fs_condition / 8 input channels / dropout 0.1 in train mode, v-MSE, backward through both modules, fused
            AdamW of both) at latents [4, 4, 16, 40, 64] -- the size and batch of ``bench.py --model vc2``.
   step72   the same at the recipe's own size, latents [2, 8, 16, 72, 128] (576 x 1024 video), batch 2, with the peak memory.
+  clip     gradient clipping's kernels alone on a 1.41 B-element fp32 buffer (the UNet's flat gradient) and on a 1.8 M-element one (CogVideoX
+           LoRA): the norm pass + finalise (vt_grad_sqnorm + vt_clip_finalize, 4 bytes per element read), the vt_adamw launch and the
+           vt_adamw_clip launch (30 bytes per element moved) -- HIP events, ms per launch, the three alternate inside every round; medians
+           and spreads as the kernel part reports them, and the norm pass as a fraction of the vt_adamw launch of the same run.
+  step40_ab  the step40 workload with and without gradient clipping (--clip, default 0.5 here) in ONE process: one flow, two joint
+           optimizers on its training state (their moments are separate), blocks of --steps steps alternating off / on for --rounds rounds.
+``--clip VAL`` runs step40 / step72 with gradient_clip_val VAL (default: off, so earlier lines stay comparable).
 The step parts each run in a child process (a fresh allocator, its own time limit).
 
-    python tools/bench_dc.py [--parts kernel,step40,step72] [--rounds 5] [--steps 4] [--warmup 2] [--timeout 500]
+    python tools/bench_dc.py [--parts kernel,step40,step72,clip,step40_ab] [--rounds 5] [--steps 4] [--warmup 2] [--timeout 500] [--clip VAL]
 """
 import argparse
 import json
@@ -101,7 +108,66 @@ def bench_kernel(rounds: int, iters: int):
     print(json.dumps(out), flush=True)
 
 
-def bench_step(latent_hw, B: int, steps: int, warmup: int):
+def bench_clip(rounds: int, iters: int):
+    sys.path.insert(0, ROOT)
+    import torch
+    from vt355 import ops
+    dev = torch.device("cuda:0")
+    P = ops.grad_sqnorm_partials()
+    out = {"metric": "gradient clipping kernels alone: norm pass + finalise, vt_adamw, vt_adamw_clip", "unit": "ms per launch", "rounds": rounds,
+           "iters_per_round": iters, "norm_pass_grid": [P, 256], "sizes": []}
+    for n in (1_410_000_000, 1_800_000):
+        g = torch.Generator(device=dev).manual_seed(n % 1000)
+        p = torch.randn(n, device=dev, generator=g)
+        gr = torch.randn(n, device=dev, generator=g).mul_(1e-3)
+        m, v, pb = torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.empty(n, dtype=torch.bfloat16, device=dev)
+        partials, record = torch.empty(P, device=dev), torch.zeros(2, device=dev)
+        step = {"n": 0}
+
+        def norm():
+            ops.grad_sqnorm(gr, partials, 0)
+            ops.clip_finalize(partials, 1, 1.0, 0.5, record)
+
+        def adamw(**kw):
+            step["n"] += 1
+            ops.adamw(p, gr, m, v, pb, 1e-5, 0.9, 0.999, 1e-8, 1e-2, step["n"], 1.0, None, **kw)
+
+        coef = record[1:2]
+        fns = {"norm_pass": norm, "adamw": adamw, "adamw_clip": lambda: adamw(clip_coef=coef)}
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            return e0.elapsed_time(e1) / iters
+
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                times[k].append(timed(fn))
+        sz = {"elements": n, "total_norm": float(record[0]), "clip_coef": float(record[1])}
+        for k, t in times.items():
+            med = statistics.median(t)
+            sz[k] = {"median_ms": round(med, 4), "spread_ms": round(max(t) - min(t), 4),
+                     "gbps": round((4.0 if k == "norm_pass" else 30.0) * n / 1e9 / (med / 1e3), 1)}
+        sz["norm_pass_over_adamw"] = round(sz["norm_pass"]["median_ms"] / sz["adamw"]["median_ms"], 4)
+        a, c = sz["adamw"], sz["adamw_clip"]
+        sz["adamw_clip_minus_adamw_ms"] = round(c["median_ms"] - a["median_ms"], 4)
+        sz["adamw_clip_separable_beyond_spread"] = bool(abs(c["median_ms"] - a["median_ms"]) > max(a["spread_ms"], c["spread_ms"]))
+        out["sizes"].append(sz)
+        del p, gr, m, v, pb
+        torch.cuda.empty_cache()
+    print(json.dumps(out), flush=True)
+
+
+def bench_step(latent_hw, B: int, steps: int, warmup: int, clip: float = 0.0, ab_rounds: int = 0):
     sys.path.insert(0, ROOT)
     import torch
     from vt355.lvdm import LatentVisualDiffusionFlow
@@ -124,13 +190,16 @@ def bench_step(latent_hw, B: int, steps: int, warmup: int):
     flow.image_proj_model.init_weights(4321)
     flow.to(dev)
     flow.train()
-    opt = flow.configure_optimizers()
+    opts = {"off": flow.configure_optimizers()} if (ab_rounds or not clip > 0.0) else {}
+    if clip > 0.0:
+        opts["clip"] = flow.configure_optimizers(gradient_clip_val=clip)
+    opt = next(iter(opts.values()))
     g = torch.Generator(device=dev).manual_seed(20230211)
     null_ctx = torch.randn(77, 1024, device=dev, generator=g).to(BF)            # stand for the encodings of "" and of an all-zero image
     null_tok = torch.randn(257, 1280, device=dev, generator=g).to(BF)
-    losses = []
+    losses, opt_events = [], {}
 
-    def step():
+    def step(opt=opt):
         opt.zero_grad()
         batch = {"latents": torch.randn(B, 4, T, H, W, device=dev, generator=g) * 0.18215 * 5.0,
                  "context": torch.randn(B, 77, 1024, device=dev, generator=g).to(BF),
@@ -138,9 +207,64 @@ def bench_step(latent_hw, B: int, steps: int, warmup: int):
                  "fps": torch.randint(1, 30, (B,), device=dev, generator=g), "null_context": null_ctx, "null_image_tokens": null_tok}
         loss = flow.training_step(batch)
         loss.backward()
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        h0 = time.perf_counter()
         opt.step()
+        host = 1000.0 * (time.perf_counter() - h0)
+        ev[1].record()
+        opt_events.setdefault(id(opt), []).append(ev + (host,))
         losses.append(loss.detach().reshape(1))
 
+    if ab_rounds:
+        for o in opts.values():
+            for _ in range(warmup):
+                step(o)
+        times = {k: [] for k in opts}
+        opt_events.clear()
+        # Pauses of Python's cyclic collector: the step synchronises with the host (condition dropout, dropout seeds), so a pause is device
+        # idle time, and their period (several steps) can alias with the alternation.  Counted per variant so that they are not read as the option's.
+        import gc
+        pauses, cur = {k: [] for k in opts}, {"k": None, "t": 0.0}
+
+        def on_gc(phase, info):
+            if phase == "start":
+                cur["t"] = time.perf_counter()
+            elif cur["k"] is not None and info["generation"] == 2:
+                pauses[cur["k"]].append(round(1000.0 * (time.perf_counter() - cur["t"]), 1))
+
+        gc.callbacks.append(on_gc)
+        for _ in range(ab_rounds):
+            for k, o in opts.items():
+                cur["k"] = k
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    step(o)
+                torch.cuda.synchronize()
+                times[k].append(1000.0 * (time.perf_counter() - t0) / steps)
+        gc.callbacks.remove(on_gc)
+        for o in opts.values():
+            o.check_errors()
+        res = {"metric": "DynamiCrafter I2V full-FT step with and without gradient clipping, same process, alternating", "unit": "ms per step",
+               "latents": [B, 4, T, H, W], "gradient_clip_val": clip, "rounds": ab_rounds, "steps_per_block": steps, "warmup_per_optimizer": warmup,
+               "grad_norm_last": float(opts["clip"].grad_norm), "loss_last": float(losses[-1])}
+        for k, t in times.items():
+            res[k] = {"median_ms": round(statistics.median(t), 3), "spread_ms": round(max(t) - min(t), 3), "rounds_ms": [round(x, 3) for x in t],
+                      # device time between the events around optimizer.step(): the norm passes, the finalise and the AdamW launches
+                      "optimizer_device_ms_median": round(statistics.median(a.elapsed_time(b) for a, b, _ in opt_events[id(opts[k])]), 3),
+                      "optimizer_device_ms_max": round(max(a.elapsed_time(b) for a, b, _ in opt_events[id(opts[k])]), 3),
+                      "optimizer_host_ms_median": round(statistics.median(h for _, _, h in opt_events[id(opts[k])]), 3),
+                      # device time from the end of one optimizer step to the end of the next, steps 2.. of every block
+                      "step_device_ms": [round(e[i][1].elapsed_time(e[i + 1][1]), 1) for e in [opt_events[id(opts[k])]]
+                                         for i in range(len(e) - 1) if (i + 1) % steps],
+                      "host_gc_gen2_pauses_ms": pauses[k]}
+            res[k]["step_device_ms_median"] = statistics.median(res[k]["step_device_ms"])
+        res["clip_minus_off_ms"] = round(res["clip"]["median_ms"] - res["off"]["median_ms"], 3)
+        res["inside_spread"] = bool(abs(res["clip_minus_off_ms"]) <= max(res["clip"]["spread_ms"], res["off"]["spread_ms"]))
+        res["clip_minus_off_step_device_median_ms"] = round(res["clip"]["step_device_ms_median"] - res["off"]["step_device_ms_median"], 2)
+        print(json.dumps(res), flush=True)
+        return
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
@@ -160,7 +284,7 @@ def bench_step(latent_hw, B: int, steps: int, warmup: int):
                                   f"use_scale, zero-terminal-SNR schedule, three-way condition dropout (p 0.05), random conditioning frame; {nu:.2f} B UNet + "
                                   f"{nr:.1f} M Resampler weights trained (fp32 masters + fused AdamW), no activation recompute, train mode: ResBlock + "
                                   "TemporalConvBlock dropout 0.1",
-                      "micro_batch": B, "latents": "pre-encoded (synthetic)", "text / image tokens": "pre-encoded OpenCLIP outputs (synthetic)"},
+                      "micro_batch": B, "gradient_clip_val": clip if clip > 0.0 else None, "latents": "pre-encoded (synthetic)", "text / image tokens": "pre-encoded OpenCLIP outputs (synthetic)"},
            "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 1), "loss_first": lv[0], "loss_last": lv[-1]}
     print(json.dumps(res), flush=True)
 
@@ -173,19 +297,25 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--timeout", type=int, default=500, help="seconds per child process")
+    ap.add_argument("--clip", type=float, default=None, help="gradient_clip_val of the step parts (default: off; step40_ab: 0.5)")
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child is not None:
         if args.child == "kernel":
             bench_kernel(args.rounds, args.iters)
+        elif args.child == "clip":
+            bench_clip(args.rounds, args.iters)
+        elif args.child == "step40_ab":
+            bench_step((40, 64), 4, args.steps, args.warmup, 0.5 if args.clip is None else args.clip, ab_rounds=args.rounds)
         elif args.child in ("step40", "step72"):
-            bench_step((40, 64) if args.child == "step40" else (72, 128), 4 if args.child == "step40" else 2, args.steps, args.warmup)
+            bench_step((40, 64) if args.child == "step40" else (72, 128), 4 if args.child == "step40" else 2, args.steps, args.warmup,
+                       args.clip or 0.0)
         else:
             raise SystemExit(f"unknown part {args.child!r}")
         return 0
     for part in args.parts.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", part, "--rounds", str(args.rounds), "--iters", str(args.iters),
-               "--steps", str(args.steps), "--warmup", str(args.warmup)]
+               "--steps", str(args.steps), "--warmup", str(args.warmup)] + ([] if args.clip is None else ["--clip", str(args.clip)])
         r = subprocess.run(cmd, timeout=args.timeout)
         if r.returncode != 0:             # a child that fails ends the run: nothing more is started on the device
             print(json.dumps({"part": part, "error": f"child exited with {r.returncode}"}), flush=True)

@@ -68,6 +68,10 @@ PROTOTYPES = {
     "vt_diffusion_loss": [_vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _ll, _i, _f, _vp],
     "vt_diffusion_loss_bwd": [_vp, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _ll, _i, _vp],
     "vt_adamw": [_fp, _fp, _fp, _fp, _vp, _ll, _f, _f, _f, _f, _f, _i, _f, _vp, _vp],
+    "vt_grad_sqnorm_partials": [],
+    "vt_grad_sqnorm": [_fp, _ll, _fp, _i, _vp],
+    "vt_clip_finalize": [_fp, _i, _f, _f, _fp, _vp],
+    "vt_adamw_clip": [_fp, _fp, _fp, _fp, _vp, _ll, _f, _f, _f, _f, _f, _i, _f, _vp, _fp, _f, _vp],
     "vt_lora_down": [_vp, _i, _vp, _i, _i, _vp, _i, _ll, _i, _i, _vp],
     "vt_skinny_tn": [_vp, _i, _vp, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _fp, _vp],
     "vt_skinny_tn_workspace_bytes": [_i],

@@ -69,6 +69,24 @@ def instantiate_from_config(config: Any, resolve=False):
     return cls(**params)
 
 
+def trainer_options(cfg: dict) -> dict:
+    """What this engine honours of ``lightning.trainer`` of a loaded reference YAML: ``accumulate_grad_batches`` (default 1; the caller's
+    loop steps every that many backward passes with ``grad_scale = 1 / accumulate_grad_batches``), ``gradient_clip_val`` (default None = off)
+    and ``gradient_clip_algorithm`` (default "norm").  Every other trainer key stays ignored.  To train a recipe as written::
+
+        opts = trainer_options(cfg)
+        optimizer = flow.configure_optimizers(**{k: v for k, v in opts.items() if k.startswith("gradient_clip")})
+    """
+    cfg = cfg or {}
+    if "lightning" not in cfg and "train" in cfg:          # flow-style recipes (vc2_t2v_320x512.yaml) keep the node under train:
+        cfg = cfg["train"] or {}
+    node = (cfg.get("lightning") or {}).get("trainer") or {}
+    val = node.get("gradient_clip_val")
+    return dict(accumulate_grad_batches=int(node.get("accumulate_grad_batches") or 1),
+                gradient_clip_val=None if val is None else float(val),
+                gradient_clip_algorithm=str(node.get("gradient_clip_algorithm") or "norm"))
+
+
 def load_yaml(path: str, env: dict = None) -> dict:
     """A reference config file as plain dicts.  ``${NAME}`` placeholders (the shipped YAMLs use them for user paths, e.g.
     ``csv_path: ${YOUR_DATA_CSV_PATH}``, resolved by OmegaConf in the reference) are filled from ``env`` / os.environ and

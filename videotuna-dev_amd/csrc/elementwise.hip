@@ -197,12 +197,18 @@ extern "C" int vt_diffusion_loss_bwd(const void* vpred, const void* noisy, const
 }
 
 // ---------------- fused AdamW over one flat fp32 buffer (+ bf16 compute copy) ----------------
+// CLIP 0: gradient = g * gscale (vt_adamw).  1: ... * *coef, the global-norm coefficient that vt_clip_finalize left in device memory
+// (torch.nn.utils.clip_grad_norm_).  2: clamp(g * gscale, -cval, +cval) (clip_grad_value_; a NaN stays a NaN, as torch.clamp).
+template <int CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_t* pb, long long n,
                                                     float lr, float b1, float b2, float eps, float wd, float bc1, float bc2,
-                                                    float gscale, const int* guard) {
+                                                    float gscale, const int* guard, const float* coef, float cval) {
     if (guard != nullptr && *guard != 0) return;      // a kernel of this step flagged its results invalid: refuse the update
+    const float cf = CLIP == 1 ? *coef : 1.0f;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float gr = g[i] * gscale;
+        float gr = g[i] * gscale;
+        if (CLIP == 1) gr *= cf;
+        if (CLIP == 2) gr = gr < -cval ? -cval : (gr > cval ? cval : gr);
         float pv = p[i] * (1.0f - lr * wd);
         const float mn = b1 * m[i] + (1.0f - b1) * gr;
         const float vn = b2 * v[i] + (1.0f - b2) * gr * gr;
@@ -212,13 +218,93 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
         if (pb != nullptr) pb[i] = f2bf(pv);
     }
 }
+extern "C" int vt_adamw_clip(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, int step, float grad_scale, const int* guard,
+                             const float* clip_coef_dev, float clip_value, void* stream) {
+    if (n <= 0 || step <= 0) return VT_ERR_BAD_SHAPE;
+    if (clip_coef_dev != nullptr && clip_value > 0.0f) return VT_ERR_UNSUPPORTED;      // one algorithm per step, as Lightning
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
+    long long b = (n + 255) / 256;
+    const dim3 grid((unsigned)(b > 16384 ? 16384 : b));
+#define VT_ADAMW_LAUNCH(C)                                                                                                        \
+    hipLaunchKernelGGL(adamw_kernel<C>, grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, \
+                       eps, weight_decay, bc1, bc2, grad_scale, guard, clip_coef_dev, clip_value)
+    if (clip_coef_dev != nullptr) VT_ADAMW_LAUNCH(1);
+    else if (clip_value > 0.0f) VT_ADAMW_LAUNCH(2);
+    else VT_ADAMW_LAUNCH(0);
+#undef VT_ADAMW_LAUNCH
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
 extern "C" int vt_adamw(float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1,
                         float beta2, float eps, float weight_decay, int step, float grad_scale, const int* guard,
                         void* stream) {
-    if (n <= 0 || step <= 0) return VT_ERR_BAD_SHAPE;
-    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-    long long b = (n + 255) / 256;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)(b > 16384 ? 16384 : b)), dim3(256), 0, (hipStream_t)stream, p, g, m, v,
-                       (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, guard);
+    return vt_adamw_clip(p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, guard, nullptr, 0.0f, stream);
+}
+
+// ---------------- global L2 norm of flat fp32 gradient buffers -> clip coefficient in device memory ----------------
+// torch.nn.utils.clip_grad_norm_(norm_type=2) without rewriting the gradients and without a host round trip:
+//   vt_grad_sqnorm  one read-only sweep per buffer; workgroup b writes sum g^2 of its share to partials[slot * GN_BLOCKS + b]
+//   vt_clip_finalize  one workgroup sums the partials of every slot in double, in a fixed order, and writes {total_norm, clip_coef}
+//   vt_adamw_clip  reads clip_coef
+// No atomics anywhere: the same buffer gives the same bits on every run and on every DDP rank.
+// The grid is FIXED (GN_BLOCKS x 256 threads = 8 workgroups on each of the 256 CUs) and sweeps the buffer in order: 16-byte loads,
+// four in flight per thread, one f32x4 accumulator per thread.  The elements before the first / after the last 16-byte boundary
+// (any 4-byte aligned pointer, any n) are added one each by the first threads of workgroup 0 / GN_BLOCKS - 1.
+#define GN_BLOCKS 2048
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float* g, long long n, float* partials) {
+    const int tid = threadIdx.x;
+    long long head = (long long)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    const f32x4* gv = (const f32x4*)(g + head);
+    const long long nvec = (n - head) >> 2;
+    const long long tail0 = head + (nvec << 2);              // first element after the vector body
+    const long long T = (long long)GN_BLOCKS * 256;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    long long i = (long long)blockIdx.x * 256 + tid;
+    for (; i + 3 * T < nvec; i += 4 * T) {
+        const f32x4 a = gv[i], b = gv[i + T], c = gv[i + 2 * T], d = gv[i + 3 * T];
+        acc += a * a; acc += b * b; acc += c * c; acc += d * d;
+    }
+    for (; i < nvec; i += T) { const f32x4 a = gv[i]; acc += a * a; }
+    if (blockIdx.x == 0 && tid < head) { const float x = g[tid]; acc[0] += x * x; }
+    if (blockIdx.x == GN_BLOCKS - 1 && tail0 + tid < n) { const float x = g[tail0 + tid]; acc[1] += x * x; }
+    float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    __shared__ float ws[4];
+    if ((tid & 63) == 0) ws[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) partials[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+extern "C" int vt_grad_sqnorm_partials(void) { return GN_BLOCKS; }
+extern "C" int vt_grad_sqnorm(const float* g, long long n, float* partials, int slot, void* stream) {
+    if (n <= 0 || slot < 0) return VT_ERR_BAD_SHAPE;
+    if (((uintptr_t)g | (uintptr_t)partials) & 3) return VT_ERR_BAD_ALIGN;
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(GN_BLOCKS), dim3(256), 0, (hipStream_t)stream, g, n,
+                       partials + (size_t)slot * GN_BLOCKS);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const float* partials, long long count, float gscale, float max_norm,
+                                                           float* record) {
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (long long i = tid; i < count; i += 256) s += (double)partials[i];
+    __shared__ double sh[256];
+    sh[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) sh[tid] += sh[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float total = (float)((double)gscale * sqrt(sh[0]));
+        const double coef = (double)max_norm / ((double)total + 1e-6);
+        record[0] = total;
+        record[1] = (float)(coef > 1.0 ? 1.0 : coef);      // a NaN norm gives a NaN coefficient, as torch.clamp(max=1.0)
+    }
+}
+extern "C" int vt_clip_finalize(const float* partials, int nslots, float grad_scale, float max_norm, float* record, void* stream) {
+    if (nslots <= 0) return VT_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long long)nslots * GN_BLOCKS,
+                       grad_scale, max_norm, record);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }

@@ -47,7 +47,12 @@ def sync_chain_guard(like: torch.Tensor, group=None):
 
 
 class FlatGradReducer:
-    """All-reduce (sum) of a flat gradient buffer; ``grad_scale`` = 1/world turns the sum into the DDP mean."""
+    """All-reduce (sum) of a flat gradient buffer; ``grad_scale`` = 1/world turns the sum into the DDP mean.
+
+    Gradient clipping needs no communication of its own, but it needs this ORDER: ``reduce()`` (or ``reduce_async()`` + ``wait()``)
+    first, then ``optimizer.step(grad_scale=reducer.grad_scale)``.  The optimizer's norm pass then reads the SUMMED gradient, identical
+    on every rank, and ``grad_scale * |sum|`` is the norm of the mean gradient that Lightning's DDP clips; every rank derives the same
+    coefficient, bit for bit (the norm kernels use no atomics).  A step issued before ``wait()`` would clip a partial sum."""
 
     def __init__(self, flat_grad: torch.Tensor, group=None):
         self.grad = flat_grad
@@ -91,7 +96,8 @@ class BucketedReducer:
     ``DDPStrategy``, without re-bucketing copies: the slices ARE the gradient storage).  xGMI is point-to-point: a few
     large slices keep every link busy; the 1/world mean is folded into the optimizer's ``grad_scale``.
     Install ``reducer.hook`` as ``FullFTState.on_grads_ready`` for the LAST micro-batch of an accumulation window only
-    (``no_sync`` semantics), then ``wait_all()`` before the optimizer step."""
+    (``no_sync`` semantics), then ``wait_all()`` before the optimizer step.  With gradient clipping that order is a requirement of
+    correctness, not only of completeness: the optimizer's norm pass must read the fully summed buffer (see FlatGradReducer)."""
 
     def __init__(self, flat_grad: torch.Tensor, group=None, wire_dtype: Optional[torch.dtype] = None):
         """wire_dtype torch.bfloat16: every slice travels as bf16 (3.4 GB instead of 6.8 GB per step for CogVideoX-2B -- SURVEY 8(e)'s

@@ -1354,10 +1354,12 @@ class HunyuanVideoFlow(torch.nn.Module):
         self.register_buffer("sigmas", flow_shift * s / (1.0 + (flow_shift - 1.0) * s), persistent=False)
         self._rope = {}
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's trainer options (config.trainer_options reads them from a recipe)"""
         from .optim import FusedAdamW
         ts = self.model.enable_lora_training()
-        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts)
+        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts, gradient_clip_val=gradient_clip_val,
+                          gradient_clip_algorithm=gradient_clip_algorithm)
 
     def loss_from(self, x0, prompt_embeds, mask, pooled, sigma, noise, guidance=None):
         dev = x0.device

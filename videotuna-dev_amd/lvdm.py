@@ -196,12 +196,13 @@ class LVDMFlow(nn.Module):
             checkpoint["state_dict"] = sd
         return checkpoint
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's trainer options (config.trainer_options reads them from a recipe)"""
         if isinstance(self.model, _PeftUNet):
             ts = self.unet.enable_lora_training()
         else:
             ts = self.model.enable_training()
-        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts)
+        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts, gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm)
 
     def p_losses(self, x_start, context, t, noise, fps=16):
         """x_start fp32 [B,C,T,H,W] (already multiplied by scale_arr[t] when use_scale -- done in forward(), ddpm3d.py:740-741)"""
@@ -269,19 +270,53 @@ VideocrafterFlow = LVDMFlow
 
 class _JointOptimizer:
     """the fused AdamW of every trained module of a flow (the UNet, the Resampler) behind one optimizer interface: each module keeps its own
-    flat master / gradient buffer, so a step is one fused launch per module"""
+    flat master / gradient buffer, so a step is one fused launch per module.
+
+    Gradient clipping by norm is over ALL parameters of the step, as Lightning's: every member's norm pass writes into one array of
+    partial sums, one finalise leaves the joint norm and its coefficient in device memory, and every member's AdamW launch reads that
+    same coefficient.  The members must have been built with the same clip settings."""
 
     def __init__(self, optimizers):
         self.optimizers = list(optimizers)
         self.param_groups = [g for o in self.optimizers for g in o.param_groups]
+        if len({(o.gradient_clip_val or None, o.gradient_clip_algorithm) for o in self.optimizers}) != 1:
+            raise ValueError("the optimizers of one step clip together: give every member the same gradient_clip_val / gradient_clip_algorithm, got "
+                             + ", ".join(f"({o.gradient_clip_val!r}, {o.gradient_clip_algorithm!r})" for o in self.optimizers))
+
+    @property
+    def gradient_clip_val(self):
+        return self.optimizers[0].gradient_clip_val
+
+    @property
+    def gradient_clip_algorithm(self):
+        return self.optimizers[0].gradient_clip_algorithm
+
+    @property
+    def grad_norm(self):
+        """0-dim device tensor: the joint pre-clip gradient norm of the last step (None unless 'norm' clipping is on)"""
+        return self.optimizers[0].grad_norm
 
     def zero_grad(self, set_to_none: bool = False):
         for o in self.optimizers:
             o.zero_grad(set_to_none)
 
-    def step(self, *a, **k):
+    def step(self, closure=None, grad_scale: float = 1.0):
+        first = self.optimizers[0]
+        if first._clip_mode() != "norm":
+            for o in self.optimizers:
+                o.step(closure, grad_scale)
+            return
+        if closure is not None:
+            closure()
+        self.check_errors()
+        partials, record = first._clip_buffers(sum(len(o._grad_buffers()) for o in self.optimizers))
+        slot = 0
         for o in self.optimizers:
-            o.step(*a, **k)
+            slot = o._norm_pass(partials, slot)
+        ops.clip_finalize(partials, slot, grad_scale, float(first.gradient_clip_val), record)
+        for o in self.optimizers:
+            o._clip_record = record            # every member's grad_norm is the joint one
+            o.step(grad_scale=grad_scale, clip_coef=record[1:2])
 
     def check_errors(self, wait: bool = True):
         for o in self.optimizers:
@@ -320,12 +355,15 @@ class LatentVisualDiffusionFlow(LVDMFlow):
         self.rand_cond_frame, self.fps_condition_type, self.conditioning_key = bool(rand_cond_frame), fps_condition_type, conditioning_key
         self.null_image_tokens = None if null_image_tokens is None else torch.as_tensor(null_image_tokens)
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's trainer options; the recipe (dc_i2v_1024.yaml) clips the joint
+        UNet + Resampler gradient norm at 0.5 (config.trainer_options reads them)"""
+        clip = dict(gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm)
         ts = self.model.enable_training()
-        opts = [FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts)]
+        opts = [FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts, **clip)]
         if self.image_proj_model_trainable:
             rs = self.image_proj_model.enable_training()
-            opts.append(FusedAdamW(rs.params, lr=self.learning_rate, fullft_state=rs))
+            opts.append(FusedAdamW(rs.params, lr=self.learning_rate, fullft_state=rs, **clip))
         return _JointOptimizer(opts)
 
     def condition_masks(self, random_num: torch.Tensor):

@@ -597,15 +597,46 @@ def diffusion_loss_bwd(vpred, noisy, x0, sa, sb, w, grad_out, dvpred):
                                                _stream()), "vt_diffusion_loss_bwd")
 
 
-def adamw(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step: int, grad_scale: float = 1.0, guard: Optional[torch.Tensor] = None):
-    """guard: device int32 [1]; a non-zero value at execution time makes the kernel skip the whole update"""
+def adamw(p, g, m, v, p_bf16, lr, beta1, beta2, eps, wd, step: int, grad_scale: float = 1.0, guard: Optional[torch.Tensor] = None,
+          clip_coef: Optional[torch.Tensor] = None, clip_value: float = 0.0):
+    """guard: device int32 [1]; a non-zero value at execution time makes the kernel skip the whole update.
+    clip_coef: device fp32 scalar written by clip_finalize (global-norm clipping); clip_value > 0: clamp(g * grad_scale, -v, +v)"""
     for n, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _req(t, torch.float32, n)
     if guard is not None:
         _req(guard, torch.int32, "guard")
     with _timed_hbm("adamw", p.numel(), (28.0 + (2.0 if p_bf16 is not None else 0.0)) * p.numel()):   # p, g, m, v read; p, m, v (+ bf16 copy) written
-        check(load_library().vt_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(),
-                                      lr, beta1, beta2, eps, wd, step, grad_scale, _p(guard), _stream()), "vt_adamw")
+        if clip_coef is None and not clip_value > 0.0:
+            check(load_library().vt_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(),
+                                          lr, beta1, beta2, eps, wd, step, grad_scale, _p(guard), _stream()), "vt_adamw")
+        else:
+            if clip_coef is not None:
+                _req(clip_coef, torch.float32, "clip_coef")
+            check(load_library().vt_adamw_clip(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), p.numel(),
+                                               lr, beta1, beta2, eps, wd, step, grad_scale, _p(guard), _p(clip_coef),
+                                               float(clip_value), _stream()), "vt_adamw_clip")
+
+
+def grad_sqnorm_partials() -> int:
+    """partial sums that one grad_sqnorm launch writes (the fixed grid of the kernel)"""
+    return int(load_library().vt_grad_sqnorm_partials())
+
+
+def grad_sqnorm(g, partials, slot: int = 0):
+    """sum of g^2 of one flat fp32 buffer (any 4-byte aligned view), as grad_sqnorm_partials() partial sums in slot ``slot`` of partials"""
+    _req(g, torch.float32, "g"); _req(partials, torch.float32, "partials")
+    if partials.numel() < (slot + 1) * grad_sqnorm_partials():
+        raise ValueError("partials holds fewer than slot + 1 slots")
+    check(load_library().vt_grad_sqnorm(g.data_ptr(), g.numel(), partials.data_ptr(), slot, _stream()), "vt_grad_sqnorm")
+
+
+def clip_finalize(partials, nslots: int, grad_scale: float, max_norm: float, record):
+    """record[0] = total_norm = grad_scale * sqrt(sum of the first nslots slots), record[1] = min(1, max_norm / (total_norm + 1e-6))"""
+    _req(partials, torch.float32, "partials"); _req(record, torch.float32, "record")
+    if partials.numel() < nslots * grad_sqnorm_partials() or record.numel() < 2:
+        raise ValueError("partials / record too small")
+    check(load_library().vt_clip_finalize(partials.data_ptr(), nslots, float(grad_scale), float(max_norm), record.data_ptr(),
+                                          _stream()), "vt_clip_finalize")
 
 
 def lora_down(x, a, R: int, t_out, K: int, zero_cols: int = 48):

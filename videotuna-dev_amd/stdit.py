@@ -733,10 +733,12 @@ class OpenSoraFlow(nn.Module):
     def device(self):
         return self.model.device
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's trainer options (config.trainer_options reads them from a recipe)"""
         from .optim import FusedAdamW
         ts = self.model.enable_training()
-        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts)
+        return FusedAdamW(ts.params, lr=self.learning_rate, fullft_state=ts, gradient_clip_val=gradient_clip_val,
+                          gradient_clip_algorithm=gradient_clip_algorithm)
 
     def loss_from(self, x0, y, mask, t, noise):
         x0 = x0.to(torch.float32).contiguous(); noise = noise.to(torch.float32).contiguous()

@@ -113,7 +113,8 @@ class CogVideoXWorkFlow(nn.Module):
         self.model = get_peft_model(self.model, cfg)
         self.model.print_trainable_parameters()
 
-    def configure_optimizers(self):
+    def configure_optimizers(self, gradient_clip_val=None, gradient_clip_algorithm="norm"):
+        """gradient_clip_val / gradient_clip_algorithm: Lightning's trainer options (config.trainer_options reads them from a recipe)"""
         params = [p for p in self.model.parameters() if p.requires_grad]
         st = getattr(self.model, "_lora_state", None)
         ft = getattr(self.model, "fullft", None)
@@ -121,7 +122,8 @@ class CogVideoXWorkFlow(nn.Module):
             from .fullft import enable_full_finetune        # reference `-fullft` recipes: no adapter_config, all weights train
             ft = enable_full_finetune(self.model)
             params = ft.params
-        return FusedAdamW(params, lr=self.learning_rate, lora_state=st, fullft_state=ft)
+        return FusedAdamW(params, lr=self.learning_rate, lora_state=st, fullft_state=ft, gradient_clip_val=gradient_clip_val,
+                          gradient_clip_algorithm=gradient_clip_algorithm)
 
     def on_save_checkpoint(self, checkpoint: Dict[str, Any]) -> Dict[str, Any]:
         sd = {k: v for k, v in checkpoint["state_dict"].items() if "lora" in k}
