@@ -283,6 +283,21 @@ int vt_lora_up_add(void* dX, int ldx, const void* dT, int ldt, const void* A, in
 int vt_lora_pack_b(const float* Bcat, void* Wext, int ldw, int n_adapters, int d_out, int r, float scale, void* stream);
 int vt_lora_pack_bt(const float* Bcat, void* WText, int ldwt, int n_adapters, int d_out, int r, float scale, void* stream);
 
+/* LoRA, ranks 17..128 ("wide" layout): adapter j of a fused projection owns the K-extension columns [j*rp, j*rp + r), rp = r rounded
+ * up to a multiple of 16, the extension is ext columns wide; all products on bf16 MFMA with fp32 sums */
+int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T, int ldt,
+                      long long M, int K, void* stream);         /* T[m, j*rp+i] = sum_k X[m,k] A[j*r+i, k]; 0 elsewhere in [0, ext) */
+int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                    float alpha, long long M, int P, void* stream);
+                                                                 /* out[p*osp+i*osr] += alpha*sum_m Big[m,p]*Small[m,i], R <= 128
+                                                                    (fp32 atomics across the row slices) */
+int vt_lora_up_add_wide(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                        long long M, int K, void* stream);       /* dX[m,k] += sum_j sum_i dT[m, j*rp+i] A[j*r+i, k] */
+int vt_lora_pack_b_wide(const float* Bcat, void* Wext, int ldw, int n_adapters, int d_out, int r, int rp, int ext, float scale,
+                        void* stream);
+int vt_lora_pack_bt_wide(const float* Bcat, void* WText, int ldwt, int n_adapters, int d_out, int r, int rp, int ext, float scale,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * VideoCrafter2 UNet path (BASELINE configs[3]): lvdm UNetModel.forward and its backward
  * (videotuna/models/lvdm/modules/networks/openaimodel3d.py:650-694) on ONE channels-last layout [B, T, H, W, C].

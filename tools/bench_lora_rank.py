@@ -1,0 +1,107 @@
+"""What a higher LoRA rank costs in the training step: the CogVideoX-2B LoRA step of ``bench.py``'s default line (49x480x720, bf16, one
+micro-batch of 4 samples, adapters on to_q / to_k / to_v / to_out.0, fused AdamW) at ranks 4, 16, 64 and 128 in ONE process on one box.
+Each rank has its own model (same seeded base weights); blocks of --steps steps alternate over the ranks for --rounds rounds, so drift
+of the box hits every rank alike.  Prints one JSON line: per rank the median ms per step with its spread over the rounds, the peak HBM
+of its blocks (the other ranks' idle models, ~3.4 GB of weights each, are resident and counted) and the step-time delta against rank 4
+of the same run.  Ranks <= 16 run the narrow rank-side kernels (csrc/lora.hip), 64 and 128 the MFMA ones (csrc/lora_wide.hip).
+
+    python tools/bench_lora_rank.py [--ranks 4,16,64,128] [--rounds 3] [--steps 2] [--warmup 1] [--micro-batch 4] > profiles/lora_rank_step.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ranks", default="4,16,64,128")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--micro-batch", type=int, default=4)
+    ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 is not the benchmark's model")
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import torch
+    from vt355 import ops
+    from vt355.dit import CogVideoXTransformer3DModel
+    from vt355.lora import LoraConfig, get_peft_model
+    from vt355.optim import FusedAdamW
+    from vt355.scheduler import CogVideoXDPMScheduler
+    from vt355.workflow import _LossFn
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_lora_rank needs the GPU: nothing is measured without one")
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(0)
+    ranks = [int(v) for v in args.ranks.split(",")]
+    B, Fr, C, Hh, Ww, St = args.micro_batch, 13, 16, 60, 90, 226
+    sched = CogVideoXDPMScheduler()
+    dgen = torch.Generator(device=dev).manual_seed(20230211)
+
+    runs = {}
+    for r in ranks:
+        model = CogVideoXTransformer3DModel(num_layers=args.layers).to(dev)
+        gen = torch.Generator(device=dev).manual_seed(1234)            # bench.py's weights
+        with torch.no_grad():
+            for name, p in model.named_parameters():
+                p.normal_(0.0, 0.02, generator=gen)
+                if name.endswith(("norm.weight", "norm_final.weight", "norm_q.weight", "norm_k.weight")):
+                    p.add_(1.0)
+        model.requires_grad_(False)
+        peft = get_peft_model(model, LoraConfig(r=r, lora_alpha=r / 4.0, target_modules=["to_k", "to_q", "to_v", "to_out.0"]))
+        st = peft._lora_state
+        runs[r] = dict(peft=peft, st=st, opt=FusedAdamW(st.params, lr=1.2e-5, lora_state=st), ms=[], peak=0.0, loss=None)
+
+    def step(run):
+        x0 = torch.randn(B, Fr, C, Hh, Ww, device=dev, generator=dgen)
+        text = (torch.randn(B, St, 4096, device=dev, generator=dgen) * 0.2).to(torch.bfloat16)
+        noise = torch.randn(B, Fr, C, Hh, Ww, device=dev, generator=dgen)
+        t = torch.randint(0, 1000, (B,), device=dev, generator=dgen)
+        run["opt"].zero_grad()
+        noisy = sched.add_noise(x0, noise, t)
+        out = run["peft"](hidden_states=noisy, encoder_hidden_states=text, timestep=t, return_dict=False)[0]
+        sa, sb, w = sched.coefficients(t)
+        loss = _LossFn.apply(out, noisy, x0, sa, sb, w)
+        loss.backward()
+        run["opt"].step()
+        run["loss"] = loss.detach()
+
+    for run in runs.values():
+        for _ in range(args.warmup):
+            step(run)
+    torch.cuda.synchronize()
+    for _ in range(args.rounds):
+        for r, run in runs.items():
+            torch.cuda.reset_peak_memory_stats(dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step(run)
+            torch.cuda.synchronize()
+            run["ms"].append(1000.0 * (time.perf_counter() - t0) / args.steps)
+            run["peak"] = max(run["peak"], torch.cuda.max_memory_allocated(dev) / 1e9)
+    assert ops.attn_bwd_chain_errors() == 0, "a dQ hand-off wait of the attention backward timed out: results invalid"
+    res = {"metric": "CogVideoX-2B T2V LoRA step 49x480x720 bf16 by adapter rank, same process, alternating", "unit": "ms per step",
+           "micro_batch": B, "layers": args.layers, "rounds": args.rounds, "steps_per_block": args.steps, "warmup_per_rank": args.warmup,
+           "device": torch.cuda.get_device_name(0), "ranks": {}}
+    base = statistics.median(runs[ranks[0]]["ms"])
+    for r, run in runs.items():
+        st = run["st"]
+        med = statistics.median(run["ms"])
+        res["ranks"][str(r)] = {"median_ms": round(med, 2), "spread_ms": round(max(run["ms"]) - min(run["ms"]), 2),
+                                "rounds_ms": [round(v, 2) for v in run["ms"]], "samples_per_s": round(B / (med / 1e3), 3),
+                                "peak_hbm_gb_all_models_resident": round(run["peak"], 1),
+                                "layout": {"wide": st.wide, "rp": st.rp, "ext_qkv": st.ext_qkv, "ext_o": st.ext_o},
+                                "trainable_params": st.flat.numel(), "loss_last": float(run["loss"]),
+                                f"delta_vs_r{ranks[0]}_ms": round(med - base, 2), f"delta_vs_r{ranks[0]}_pct": round(100.0 * (med - base) / base, 2)}
+    print(json.dumps(res), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

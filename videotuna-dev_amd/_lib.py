@@ -78,6 +78,11 @@ PROTOTYPES = {
     "vt_lora_up_add": [_vp, _i, _vp, _i, _vp, _i, _i, _ll, _i, _vp],
     "vt_lora_pack_b": [_fp, _vp, _i, _i, _i, _i, _f, _vp],
     "vt_lora_pack_bt": [_fp, _vp, _i, _i, _i, _i, _f, _vp],
+    "vt_lora_down_wide": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _ll, _i, _vp],
+    "vt_lora_tn_wide": [_vp, _i, _vp, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _vp],
+    "vt_lora_up_add_wide": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _vp],
+    "vt_lora_pack_b_wide": [_fp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "vt_lora_pack_bt_wide": [_fp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     # ---- VideoCrafter2 UNet path ----
     "vt_conv_cl": [_vp, _ll, _vp, _vp, _fp, _i, _vp, _ll, _vp, _ll] + [_i] * 13 + [_vp],
     "vt_conv_dw_cl": [_vp, _ll, _vp, _ll, _fp] + [_i] * 13 + [_i, _vp],

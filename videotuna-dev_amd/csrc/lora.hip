@@ -1,8 +1,9 @@
-// LoRA side-path kernels (rank <= 16).  Semantics follow peft 0.12 LoraLayer as injected by the
+// LoRA side-path kernels of the narrow K-extension layout (at most 16 rank columns per call: ranks 1..16; the kernels of ranks
+// 17..128 are in lora_wide.hip).  Semantics follow peft 0.12 LoraLayer as injected by the
 // reference at videotuna/models/cogvideo_hf/cogvideo_pl.py:143-149 with configs/004_cogvideox/cogvideo2b.yaml:32-38:
 //     y = W x + b + (alpha/r) * B (A x)
 // The engine folds the up-projection into the base GEMM by extending K: the activation buffer carries
-// T = x A^T in 16 extra columns and the weight carries (alpha/r) * B there, so forward and dX need no
+// T = x A^T in extra columns and the weight carries (alpha/r) * B there, so forward and dX need no
 // special GEMM; these kernels produce T, the rank-r gradients, and the rank-r correction of dX.
 #include "common.h"
 #include <cstdlib>

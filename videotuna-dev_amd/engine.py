@@ -16,7 +16,7 @@ import torch
 from . import ops
 from .ops import BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_GATED_RES
 
-EXT = 64
+EXT = 64          # K-extension width without adapters and for LoRA ranks <= 16; wider ranks: LoraState.ext_qkv / ext_o
 # q_hat is stored pre-multiplied by softmax_scale * log2(e) (head_dim 64) so the attention kernels exponentiate raw scores
 Q_PRESCALE = 1.4426950408889634 / 8.0
 
@@ -30,16 +30,22 @@ def _lin(mod):
 # ---------------------------------------------------------------------------------------------------
 # operand packing
 # ---------------------------------------------------------------------------------------------------
-def _ext_rows(w: torch.Tensor) -> torch.Tensor:
-    """[N,K] -> [N,K+EXT] with a zero K-extension."""
-    out = torch.zeros(w.shape[0], w.shape[1] + EXT, dtype=BF16, device=w.device)
+def _ext_widths(model):
+    """(ext_qkv, ext_o): K-extension columns of the fused qkv / out operands (a property of the LoRA state's layout)"""
+    st = model.lora
+    return (st.ext_qkv, st.ext_o) if st is not None else (EXT, EXT)
+
+
+def _ext_rows(w: torch.Tensor, ext: int) -> torch.Tensor:
+    """[N,K] -> [N,K+ext] with a zero K-extension."""
+    out = torch.zeros(w.shape[0], w.shape[1] + ext, dtype=BF16, device=w.device)
     out[:, :w.shape[1]] = w
     return out
 
 
-def _ext_t(w: torch.Tensor) -> torch.Tensor:
-    """[N,K] -> transposed [K+EXT,N] with zero extension rows."""
-    out = torch.zeros(w.shape[1] + EXT, w.shape[0], dtype=BF16, device=w.device)
+def _ext_t(w: torch.Tensor, ext: int) -> torch.Tensor:
+    """[N,K] -> transposed [K+ext,N] with zero extension rows."""
+    out = torch.zeros(w.shape[1] + ext, w.shape[0], dtype=BF16, device=w.device)
     out[:w.shape[1]] = w.t()
     return out
 
@@ -52,7 +58,8 @@ def pack(model) -> SimpleNamespace:
     for n, p in model.named_parameters():
         if "lora" not in n and p.dtype != BF16:
             raise TypeError(f"parameter {n} is {p.dtype}; the MI355X engine computes in bf16 -- call .bfloat16()")
-    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version)
+    eq, eo = _ext_widths(model)
+    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version, ext=(eq, eo))
     d = model.inner_dim
     with torch.no_grad():
         for i, blk in enumerate(model.transformer_blocks):
@@ -68,8 +75,8 @@ def pack(model) -> SimpleNamespace:
                 L.w_o, L.b_o, L.w_o_t = wo, bo, wo.t().contiguous()
             else:
                 wqkv = torch.cat([wq, wk, wv], 0)
-                L.w_qkv = _ext_rows(wqkv); L.b_qkv = torch.cat([bq, bk, bv]).contiguous(); L.w_qkv_t = _ext_t(wqkv)
-                L.w_o = _ext_rows(wo); L.b_o = bo; L.w_o_t = _ext_t(wo)
+                L.w_qkv = _ext_rows(wqkv, eq); L.b_qkv = torch.cat([bq, bk, bv]).contiguous(); L.w_qkv_t = _ext_t(wqkv, eq)
+                L.w_o = _ext_rows(wo, eo); L.b_o = bo; L.w_o_t = _ext_t(wo, eo)
             w1, b1 = _lin(blk.ff.net[0].proj); w2, b2 = _lin(blk.ff.net[2])
             L.w1, L.b1, L.w1_t = w1, b1, w1.t().contiguous()
             L.w2, L.b2, L.w2_t = w2, b2, w2.t().contiguous()
@@ -101,16 +108,23 @@ def pack(model) -> SimpleNamespace:
 
 def packed(model) -> SimpleNamespace:
     ft = getattr(model, "fullft", None)
-    if model._packed is None or (ft is not None and model._packed.ft_version != ft.version):
+    if (model._packed is None or (ft is not None and model._packed.ft_version != ft.version)
+            or model._packed.ext != _ext_widths(model)):
         model._packed = pack(model)          # full fine-tune: the transposed operand copies follow the updated weights
     P = model._packed
     st = model.lora
     if st is not None and P.lora_version != st.version:
-        d, r = model.inner_dim, st.r
+        d, r, rp, eq, eo = model.inner_dim, st.r, st.rp, st.ext_qkv, st.ext_o
         for i, L in enumerate(P.layers):
-            ops.lora_pack_b(st.b_qkv(st.flat, i), L.w_qkv[:, d:], d + EXT, 3, d, r, st.scaling)
+            if st.wide:
+                ops.lora_pack_b_wide(st.b_qkv(st.flat, i), L.w_qkv[:, d:], d + eq, 3, d, r, rp, eq, st.scaling)
+                ops.lora_pack_bt_wide(st.b_qkv(st.flat, i), L.w_qkv_t[d:], 3 * d, 3, d, r, rp, eq, st.scaling)
+                ops.lora_pack_b_wide(st.b_out(st.flat, i), L.w_o[:, d:], d + eo, 1, d, r, rp, eo, st.scaling)
+                ops.lora_pack_bt_wide(st.b_out(st.flat, i), L.w_o_t[d:], d, 1, d, r, rp, eo, st.scaling)
+                continue
+            ops.lora_pack_b(st.b_qkv(st.flat, i), L.w_qkv[:, d:], d + eq, 3, d, r, st.scaling)
             ops.lora_pack_bt(st.b_qkv(st.flat, i), L.w_qkv_t[d:], 3 * d, 3, d, r, st.scaling)
-            ops.lora_pack_b(st.b_out(st.flat, i), L.w_o[:, d:], d + EXT, 1, d, r, st.scaling)
+            ops.lora_pack_b(st.b_out(st.flat, i), L.w_o[:, d:], d + eo, 1, d, r, st.scaling)
             ops.lora_pack_bt(st.b_out(st.flat, i), L.w_o_t[d:], d, 1, d, r, st.scaling)
         P.lora_version = st.version
     return P
@@ -118,9 +132,13 @@ def packed(model) -> SimpleNamespace:
 
 # The rank-r side kernels (csrc/lora.hip) take at most 16 rank columns per call.  The three q / k / v adapters of a fused projection fit one
 # call up to rank 5 (3 r <= 16: the shipped recipes, r = 4); above that (r <= 16) each adapter gets its own call on its r columns.
+# Ranks 17..128 (st.wide) take the MFMA kernels of csrc/lora_wide.hip: every adapter of a projection in one pass over the activation.
 def _lora_down_qkv(x1, st, i, d):
     r = st.r
     a = st.a_qkv(st.flat_bf16, i)
+    if st.wide:
+        ops.lora_down_wide(x1, a, 3, r, st.rp, st.ext_qkv, x1[:, d:], d)
+        return
     if 3 * r <= 16:
         ops.lora_down(x1, a, 3 * r, x1[:, d:], d)
         return
@@ -131,6 +149,12 @@ def _lora_down_qkv(x1, st, i, d):
 def _lora_qkv_input_grads(x1, dx1, st, i, d, need_dx=True):
     """dA_qkv += dT^T x1 and (need_dx) dx1 += dT A_qkv for the fused projection's three adapters (dT = the extension columns of dx1)"""
     r = st.r
+    if st.wide:
+        for j in range(3):
+            ops.lora_tn_wide(x1, dx1[:, d + j * st.rp:], r, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d)
+        if need_dx:
+            ops.lora_up_add_wide(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3, r, st.rp, d)
+        return
     if 3 * r <= 16:
         ops.skinny_tn(x1, dx1[:, d:], 3 * r, st.a_qkv(st.grad, i), 1, d, 1.0, d)
         if need_dx:
@@ -154,8 +178,8 @@ def _mod(mod: torch.Tensor, idx: int, d: int):
 def saved_bytes_per_block(model, M: int) -> int:
     """activation bytes one block keeps for its backward pass (bf16 rows of width d unless noted)"""
     d = model.inner_dim
-    ext = EXT if model.lora is not None else 0
-    cols = 2 * (d + ext) + 3 * d + 2 * d + d + model.config.ff_mult * d + d         # x1, o | qkv | qkh | h1 | u | h_in
+    ext2 = sum(_ext_widths(model)) if model.lora is not None else 0         # x1 carries ext_qkv extra columns, o ext_o
+    cols = 2 * d + ext2 + 3 * d + 2 * d + d + model.config.ff_mult * d + d         # x1, o | qkv | qkh | h1 | u | h_in
     if getattr(model, "fullft", None) is not None:
         cols += d + model.config.ff_mult * d + 2 * d                                  # x2 | g | ao, fo
     return M * cols * 2
@@ -188,35 +212,37 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch):
     d, H = model.inner_dim, c.num_attention_heads
     B, Fr, C, Hh, Ww, S, St, Sv, M = dims
     dev = h.device
-    KE = d + EXT if st is not None else d        # GEMM reduction length on the LoRA-extended operands
-    r3 = 3 * st.r if st is not None else 0
+    eq, eo = _ext_widths(model)
+    KEq, KEo = (d + eq, d + eo) if st is not None else (d, d)        # GEMM reduction lengths on the LoRA-extended operands
     E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
     xg, gbuf = scratch.xg, scratch.gbuf
     Lw = P.layers[i]
     m1, m2 = _mod(mod, 2 * i, d), _mod(mod, 2 * i + 1, d)
     a = SimpleNamespace(h_in=h)
     # --- attention branch ---
-    x1 = E(M, d + EXT)
+    x1 = E(M, d + eq)
     a.mean1, a.rstd1 = E(M, dt=torch.float32), E(M, dt=torch.float32)
     ops.ln_modulate_fwd(h, x1, Lw.n1g, Lw.n1b, (m1.shift_txt, m1.scale_txt, m1.shift_vid, m1.scale_vid, m1.bs),
                         a.mean1, a.rstd1, d, S, St, c.norm_eps)
     if st is not None:
         _lora_down_qkv(x1, st, i, d)
     qkv = E(M, 3 * d)
-    ops.gemm(x1, Lw.w_qkv, qkv, Lw.b_qkv, K=KE)
+    ops.gemm(x1, Lw.w_qkv, qkv, Lw.b_qkv, K=KEq)
     qkh = E(M, 2 * d)
     a.qmean, a.qrstd = E(M, 2 * H, dt=torch.float32), E(M, 2 * H, dt=torch.float32)
     ops.qk_layernorm_fwd(qkv, qkh, Lw.gq, Lw.bq, Lw.gk, Lw.bk, a.qmean, a.qrstd, H, 1e-6, q_scale=Q_PRESCALE, rope=rope)
-    o = E(M, d + EXT)
+    o = E(M, d + eo)
     lse = E(B, H, S, dt=torch.float32)
-    qk3, qkv3, o3 = qkh.view(B, S, 2 * d), qkv.view(B, S, 3 * d), o.view(B, S, d + EXT)
+    qk3, qkv3, o3 = qkh.view(B, S, 2 * d), qkv.view(B, S, 3 * d), o.view(B, S, d + eo)
     ops.attn_fwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], o3[:, :, :d], lse, B, H, S, q_prescaled=True)
-    if st is not None:
+    if st is not None and st.wide:
+        ops.lora_down_wide(o, st.a_out(st.flat_bf16, i), 1, st.r, st.rp, eo, o[:, d:], d)
+    elif st is not None:
         ops.lora_down(o, st.a_out(st.flat_bf16, i), st.r, o[:, d:], d)
     h1 = E(M, d)
     ao = E(M, d) if (save and ft is not None) else None           # branch output before gating (gate gradient)
     ops.gemm(o, Lw.w_o, h1, Lw.b_o, epilogue=EPI_GATED_RES, residual=h, gate_txt=m1.gate_txt, gate_vid=m1.gate_vid,
-             gate_bstride=m1.bs, S=S, St=St, K=KE, pre_act_out=ao)
+             gate_bstride=m1.bs, S=S, St=St, K=KEo, pre_act_out=ao)
     # --- feed-forward branch ---
     a.mean2, a.rstd2 = E(M, dt=torch.float32), E(M, dt=torch.float32)
     keep_ff = save and ft is not None                              # dW1 / dW2 need the FF inputs
@@ -321,7 +347,10 @@ def run_backward(model, ctx, dout: torch.Tensor):
     B, Fr, C, Hh, Ww, S, St, Sv, M = ctx.dims
     p = c.patch_size
     dev = dout.device
-    r = st.r
+    r, rp = st.r, st.rp
+    eq, eo = st.ext_qkv, st.ext_o
+    wide = st.wide
+    tn = ops.lora_tn_wide if wide else ops.skinny_tn          # rank gradients: MFMA kernel above rank 16
     E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
     mod = ctx.mod
 
@@ -342,11 +371,11 @@ def run_backward(model, ctx, dout: torch.Tensor):
     du = E(M, c.ff_mult * d)
     dx2 = E(M, d)
     dh1 = E(M, d)
-    dO = E(M, d + EXT)
+    dO = E(M, d + eo)
     dq = E(B, S, d, dt=torch.float32)
     dkh = E(M, d)
     dqkv = E(M, 3 * d)
-    dx1 = E(M, d + EXT)
+    dx1 = E(M, d + eq)
     delta = E(B * H * S, dt=torch.float32)
     chain_ws = ops.attn_bwd_chain_workspace(B, H, S, dev)
     dh_in = E(M, d)
@@ -362,22 +391,25 @@ def run_backward(model, ctx, dout: torch.Tensor):
         ops.ln_modulate_bwd(dx2, a.h1, a.mean2, a.rstd2, Lw.n2g, (m2.scale_txt, m2.scale_vid, m2.bs), dh, dh1, d, S, St)
         # --- attention branch:  h1 = h + gate_msa * (Wo' [O | T2]) ---
         ops.gate_mul(dh1, tg, m1.gate_txt, m1.gate_vid, m1.bs, d, S, St)
-        ops.gemm(tg, Lw.w_o_t, dO, None)                                  # [M, d+EXT]: dO | dT2
-        ops.skinny_tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o
-        ops.skinny_tn(a.o, dO[:, d:], r, st.a_out(st.grad, i), 1, d, 1.0, d)                   # dA_o
-        ops.lora_up_add(dO, dO[:, d:], st.a_out(st.flat_bf16, i), r, d)
+        ops.gemm(tg, Lw.w_o_t, dO, None)                                  # [M, d+ext_o]: dO | dT2
+        tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o
+        tn(a.o, dO[:, d:], r, st.a_out(st.grad, i), 1, d, 1.0, d)                   # dA_o
+        if wide:
+            ops.lora_up_add_wide(dO, dO[:, d:], st.a_out(st.flat_bf16, i), 1, r, rp, d)
+        else:
+            ops.lora_up_add(dO, dO[:, d:], st.a_out(st.flat_bf16, i), r, d)
         dq.zero_()
         qk3, qkv3 = a.qkh.view(B, S, 2 * d), a.qkv.view(B, S, 3 * d)
-        ops.attn_bwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], a.o.view(B, S, d + EXT)[:, :, :d],
-                     dO.view(B, S, d + EXT)[:, :, :d], a.lse, delta, dq, dkh.view(B, S, d),
+        ops.attn_bwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], a.o.view(B, S, d + eo)[:, :, :d],
+                     dO.view(B, S, d + eo)[:, :, :d], a.lse, delta, dq, dkh.view(B, S, d),
                      dqkv.view(B, S, 3 * d)[:, :, 2 * d:], B, H, S, q_prescaled=True, chain_ws=chain_ws)
         ops.qk_layernorm_bwd(dq.view(M, d), dkh, a.qkv, a.qmean, a.qrstd, Lw.gq, Lw.gk, dqkv, H, rope=ctx.rope)
         if i > 0:
-            ops.gemm(dqkv, Lw.w_qkv_t, dx1, None)                         # [M, d+EXT]: dx1 | dT1
+            ops.gemm(dqkv, Lw.w_qkv_t, dx1, None)                         # [M, d+ext_qkv]: dx1 | dT1
         else:
             ops.gemm(dqkv, Lw.w_qkv_t[d:], dx1[:, d:], None)              # the first block's input (frozen embeddings) needs no gradient: dT1 only
         for j in range(3):
-            ops.skinny_tn(dqkv[:, j * d:], a.x1[:, d + j * r:], r, st.b_qkv(st.grad, i)[j * d:], r, 1, st.scaling, d)
+            tn(dqkv[:, j * d:], a.x1[:, d + j * rp:], r, st.b_qkv(st.grad, i)[j * d:], r, 1, st.scaling, d)
         _lora_qkv_input_grads(a.x1, dx1, st, i, d, need_dx=i > 0)
         if i > 0:
             ops.ln_modulate_bwd(dx1, a.h_in, a.mean1, a.rstd1, Lw.n1g, (m1.scale_txt, m1.scale_vid, m1.bs), dh1, dh_in,

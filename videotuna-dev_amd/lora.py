@@ -14,6 +14,7 @@ copy) so the optimizer is one fused kernel launch and data-parallel training nee
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
@@ -21,6 +22,25 @@ import torch
 import torch.nn as nn
 
 TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
+NARROW_MAX_R = 16      # up to here the adapters ride in a fixed 64-column K-extension (csrc/lora.hip)
+MAX_R = 128            # above NARROW_MAX_R: the wide layout on the MFMA rank-side kernels (csrc/lora_wide.hip)
+
+
+def _ceil_to(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def extension_layout(r: int, wide: bool = None):
+    """(rp, ext_qkv, ext_o, wide) of the K-extension for rank r: adapter j of a fused projection owns the extension columns
+    [j*rp, j*rp + r).  r <= 16: rp = r inside a fixed 64-column extension; above (or for any rank with VT355_LORA_WIDE=1, a
+    test / A-B knob): rp = r rounded up to a multiple of 16, so that every adapter's column block starts 16-byte aligned, and
+    the extensions are 3 rp / rp columns rounded up to the GEMMs' 64-deep K step."""
+    if wide is None:
+        wide = r > NARROW_MAX_R or os.environ.get("VT355_LORA_WIDE", "0") not in ("", "0")
+    if not wide:
+        return r, 64, 64, False
+    rp = _ceil_to(r, 16)
+    return rp, _ceil_to(3 * rp, 64), _ceil_to(rp, 64), True
 
 
 @dataclass
@@ -39,8 +59,9 @@ class LoraConfig:
             raise NotImplementedError("lora_dropout > 0 is not supported (the reference config uses 0)")
         if self.bias != "none":
             raise NotImplementedError("bias != 'none' is not supported")
-        if self.r <= 0 or self.r > 16:
-            raise NotImplementedError("the K-extension carries 64 columns: rank <= 16 per adapter (3 adapters x r <= 48); peft itself takes any rank")
+        if self.r <= 0 or self.r > MAX_R:
+            raise NotImplementedError(f"rank 1..{MAX_R} per adapter: the rank-side kernels hold at most 3 adapters x {MAX_R} rank columns "
+                                      f"of the K-extension; peft itself takes any rank")
 
 
 class _W(nn.Module):
@@ -75,6 +96,8 @@ class LoraState:
     def __init__(self, model, cfg: LoraConfig):
         self.cfg = cfg
         self.r = cfg.r
+        # K-extension layout: per-adapter column stride and the extension widths of the fused qkv / out operands
+        self.rp, self.ext_qkv, self.ext_o, self.wide = extension_layout(cfg.r)
         self.scaling = float(cfg.lora_alpha) / cfg.r
         self.d = model.inner_dim
         self.L = model.config.num_layers

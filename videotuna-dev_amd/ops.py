@@ -680,6 +680,38 @@ def lora_pack_bt(bcat_f32, wtext, ldwt: int, n_adapters: int, d_out: int, r: int
           "vt_lora_pack_bt")
 
 
+# ---- ranks 17..128: the wide K-extension layout (csrc/lora_wide.hip); adapter j owns extension columns [j*rp, j*rp + r) ----
+def lora_down_wide(x, a, n_adapters: int, r: int, rp: int, ext: int, t_out, K: int):
+    """t_out[:, j*rp + i] = x[:, :K] @ a[j*r + i]^T for every adapter in one pass over x; every other column of t_out[:, :ext] = 0."""
+    _req(x, BF16, "x", 2); _req(a, BF16, "a", 2); _req(t_out, BF16, "t", 2)
+    check(load_library().vt_lora_down_wide(x.data_ptr(), x.stride(0), a.data_ptr(), a.stride(0), n_adapters, r, rp, ext,
+                                           t_out.data_ptr(), t_out.stride(0), x.shape[0], K, _stream()), "vt_lora_down_wide")
+
+
+def lora_tn_wide(big, small, R: int, out, osp: int, osr: int, alpha: float, P: int):
+    """out[p*osp + i*osr] += alpha * sum_m big[m,p] * small[m,i] for R <= 128 on MFMA (fp32 atomics across row slices)."""
+    _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
+    check(load_library().vt_lora_tn_wide(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, out.data_ptr(),
+                                         osp, osr, alpha, big.shape[0], P, _stream()), "vt_lora_tn_wide")
+
+
+def lora_up_add_wide(dx, dt, a, n_adapters: int, r: int, rp: int, K: int):
+    """dx[:, :K] += sum_j dt[:, j*rp : j*rp + r] @ a[j*r : (j+1)*r] in place, all adapters in one pass over dx."""
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    check(load_library().vt_lora_up_add_wide(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(), a.stride(0),
+                                             n_adapters, r, rp, dx.shape[0], K, _stream()), "vt_lora_up_add_wide")
+
+
+def lora_pack_b_wide(bcat_f32, wext, ldw: int, n_adapters: int, d_out: int, r: int, rp: int, ext: int, scale: float):
+    check(load_library().vt_lora_pack_b_wide(bcat_f32.data_ptr(), wext.data_ptr(), ldw, n_adapters, d_out, r, rp, ext, scale,
+                                             _stream()), "vt_lora_pack_b_wide")
+
+
+def lora_pack_bt_wide(bcat_f32, wtext, ldwt: int, n_adapters: int, d_out: int, r: int, rp: int, ext: int, scale: float):
+    check(load_library().vt_lora_pack_bt_wide(bcat_f32.data_ptr(), wtext.data_ptr(), ldwt, n_adapters, d_out, r, rp, ext, scale,
+                                              _stream()), "vt_lora_pack_bt_wide")
+
+
 # =====================================================================================================================
 # VideoCrafter2 UNet path (include/vt355.h, second half): channels-last [N, T, H, W, C] activations
 # =====================================================================================================================
