@@ -3,6 +3,8 @@ import math
 
 import torch
 
+from parity import close  # noqa: F401  (the comparison of the gradient-clip tests: NaN and Inf are out of tolerance)
+
 TREE_LEVELS = 10      # fp32 tree levels of vt_grad_sqnorm before the double stage: 4 lanes (2) + 64-wide wave (6) + 4 waves (2)
 THREADS = 256
 
@@ -14,15 +16,6 @@ def sqnorm_rel_bound(n: int, blocks: int) -> float:
     and t = 10 tree levels follow; the double stage adds nothing at this scale.  (m + t + 1) * 2^-24 for the sum, half of it for the norm."""
     m = math.ceil(math.ceil(n / 4) / (blocks * THREADS)) + 1
     return (m + TREE_LEVELS + 1) * 2.0 ** -24
-
-
-def close(a, b, rtol, atol, what=""):
-    """tests/test_kernels_gpu.py's comparison"""
-    a = a.detach().float().cpu(); b = b.detach().float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    bad = (err > tol).float().mean().item()
-    assert bad == 0.0, f"{what}: {bad*100:.4f}% out of tol, max err {err.max().item():.4g}, ref absmax {b.abs().max().item():.4g}"
 
 
 def tiny_dc_flow():

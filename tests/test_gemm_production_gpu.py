@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 import torch
 
+from parity import SENT, SENT8, poisoned
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 F8 = torch.float8_e4m3fn
@@ -30,8 +32,6 @@ U32 = 2.0 ** -24                     # unit roundoff of fp32
 SIG_ERR = 2.0 ** -20                 # absolute error bound of the kernels' GELU sigmoid (see _bound)
 FP8_GROUP_ERR = 2.0 ** -9            # fp8 MFMA: loss of one in-instruction product group, relative to its largest product (see _fp8_group_term)
 K0, K1 = 0.7978845608028654, 0.044715
-SENT = 0x7FA5                        # sentinel bf16 bits (a NaN payload no kernel writes); also an unwritten element fails the bound
-SENT8 = 0x5A                         # sentinel e4m3 byte
 TILE = {1: (128, 128), 2: (256, 256), 3: (256, 128), 4: (128, 128)}
 KNAME = {1: "128x128", 2: "256x256", 3: "pc 256x128", 4: "pc 128x128"}
 
@@ -341,12 +341,7 @@ GUARD_ROWS = 3
 
 
 def _guarded(M, ld, dev, dtype=BF):
-    buf = torch.empty(M + GUARD_ROWS, ld, dtype=dtype, device=dev)
-    if dtype == BF:
-        buf.view(torch.int16).fill_(SENT)
-    else:
-        buf.view(torch.uint8).fill_(SENT8)
-    return buf
+    return poisoned((M + GUARD_ROWS, ld), dtype, dev)          # SENT in every bf16 element, SENT8 in every fp8 byte
 
 
 def _guards_intact(buf, M, c0, c1, what):

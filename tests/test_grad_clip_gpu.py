@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from grad_clip_common import close, sqnorm_rel_bound, tiny_dc_flow
+from parity import poisoned
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -145,7 +146,7 @@ def test_clipped_adamw_matches_torch(dev, algo):
     cv = 0.05
     pt = p.clone().requires_grad_(True)
     opt = torch.optim.AdamW([pt], lr=1e-2)
-    P = p.to(dev); Mo = torch.zeros(n, device=dev); Vo = torch.zeros(n, device=dev); Pb = torch.empty(n, dtype=BF, device=dev)
+    P = p.to(dev); Mo = torch.zeros(n, device=dev); Vo = torch.zeros(n, device=dev); Pb = poisoned((n,), BF, dev)
     coefs = []
     for i in range(3):
         pt.grad = gr[i].clone()

@@ -4,21 +4,13 @@ operands, then the mode in HunyuanBlocks / HYVideoDiffusionTransformer against f
 import pytest
 import torch
 
+from parity import all_written, cosine, poisoned, rel_l2
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 E4, E5 = torch.float8_e4m3fn, torch.float8_e5m2
 FMAX = {E4: 448.0, E5: 57344.0}
 FMTS = [pytest.param(E5, id="e5m2"), pytest.param(E4, id="e4m3")]
-
-
-def _rel(a, b):
-    a = a.detach().double().cpu(); b = b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def _cos(a, b):
-    a = a.detach().double().cpu().flatten(); b = b.detach().double().cpu().flatten()
-    return (a @ b / (a.norm() * b.norm()).clamp_min(1e-300)).item()
 
 
 def _fp8_cpu(x_bf16, scale, dt):
@@ -121,7 +113,7 @@ def test_gemm_mxfp8_dx_random_vs_fp64(dev, epi, tail, M, N, K, gfmt):
         At = (torch.randn(M, 64, generator=gen) * 0.5).to(BF); Wt = (torch.randn(N, 64, generator=gen) * 0.1).to(BF)
         ref = ref + At.double() @ Wt.double().t()
         kw["tail"] = (At.to(dev), Wt.to(dev))
-    out = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev)
     if epi == "plain":
         ops.gemm_mxfp8_dx(gq, wq, out, sg, sw, **kw)
     elif epi == "dgelu":
@@ -132,7 +124,7 @@ def test_gemm_mxfp8_dx_random_vs_fp64(dev, epi, tail, M, N, K, gfmt):
         R = torch.randn(M, N, generator=gen).to(BF)
         ops.gemm_mxfp8_dx(gq, wq, out, sg, sw, epilogue=EPI_GATED_RES, residual=R.to(dev), **kw)
         ref = ref + R.double()
-    e = _rel(out, ref)
+    e = rel_l2(out, ref)
     print(f"[mxfp8 dx] {epi} tail={tail} {M}x{N}x{K} {gfmt}: rel-L2 {e:.3e}")
     assert e < 5e-3
 
@@ -149,16 +141,17 @@ def test_gemm_mxfp8_dx_fp8_output_copy_exact(dev, gfmt, ofmt):
     gq, sg, _ = _quant_g(torch.randn(M, K, generator=gen), gfmt, dev)
     wq, sw, _ = _quant_w(torch.randn(N, K, generator=gen) * K ** -0.5, dev)
     u = torch.randn(M, N, generator=gen).to(BF).to(dev)
-    out = torch.empty(M, N, dtype=BF, device=dev)
-    cq = torch.empty(M, N, dtype=ofmt, device=dev)
+    out = poisoned((M, N), BF, dev)
+    cq = poisoned((M, N), ofmt, dev)
     sq = torch.tensor([2.0 / FMAX[ofmt]], device=dev)                    # |out| above 2 saturates
     amax = torch.zeros(1, device=dev)
     ops.gemm_mxfp8_dx(gq, wq, out, sg, sw, epilogue=EPI_DGELU, pre_act_in=u, out_fp8=(cq, sq, amax))
+    all_written(cq, "fp8 output copy", expect=_fp8_cpu(out, sq, ofmt).to(dev))
     assert torch.equal(_bytes(cq), _bytes(_fp8_cpu(out, sq, ofmt)))
     assert amax.item() == out.float().abs().max().item()
     assert (out.float().abs() > 2.0).any()
     assert bool(torch.isfinite(cq.float()).all()) and cq.float().abs().max().item() == FMAX[ofmt]
-    plain = torch.empty(M, N, dtype=BF, device=dev)
+    plain = poisoned((M, N), BF, dev)
     ops.gemm_mxfp8_dx(gq, wq, plain, sg, sw, epilogue=EPI_DGELU, pre_act_in=u)
     assert torch.equal(plain, out)                                       # the copy does not change the bf16 output
 
@@ -174,7 +167,7 @@ def test_gate_mul_fp8_exact(dev, fmt):
     x = (torch.randn(M, D, generator=gen) * 2).to(BF).to(dev)
     gate = torch.randn(B, 3 * D, generator=gen).to(dev)
     g = gate[:, D:2 * D]
-    y0 = torch.empty(M, D, dtype=BF, device=dev)
+    y0 = poisoned((M, D), BF, dev)
     ops.gate_mul(x, y0, g, g, 3 * D, D, L, 0)
     y1 = torch.full((M, D + 64), 5.0, dtype=BF, device=dev)
     q = torch.zeros(M, D + 128, dtype=fmt, device=dev)
@@ -197,23 +190,25 @@ def test_cast_fp8_fmt_exact(dev, fmt):
     x = (torch.randn(B * Lj, K, generator=gen) * 3).to(BF).to(dev)
     x[7, 5] = 1e6                                                        # far above FMAX * scale in both formats
     scale = torch.tensor([2.5 / FMAX[fmt]], device=dev)
-    y = torch.empty(B * Lj, K, dtype=fmt, device=dev)
+    y = poisoned((B * Lj, K), fmt, dev)
     amax = torch.zeros(1, device=dev)
     ops.cast_fp8_fmt(x, y, scale, amax)
+    all_written(y, "fp8 cast", expect=_fp8_cpu(x, scale, fmt).to(dev))
     assert torch.equal(_bytes(y), _bytes(_fp8_cpu(x, scale, fmt)))
     assert bool(torch.isfinite(y.float()).all()) and y.float()[7, 5].item() == FMAX[fmt]
     assert amax.item() == x.float().abs().max().item()
     assert (x.float().abs() > 2.5).sum().item() > 100
-    y2 = torch.empty(B * L, K, dtype=fmt, device=dev)
+    y2 = poisoned((B * L, K), fmt, dev)
     cp = torch.full((B * L, K + 64), 5.0, dtype=BF, device=dev)
     amax2 = torch.zeros(1, device=dev)
     ops.cast_fp8_fmt(x, y2, scale, amax2, copy=cp[:, :K], rows=(L, Lj, off))
     rows = x.view(B, Lj, K)[:, off:off + L].reshape(B * L, K)
     assert torch.equal(cp[:, :K], rows) and bool((cp[:, K:] == 5.0).all())
+    all_written(y2, "fp8 cast through the row map", expect=_fp8_cpu(rows, scale, fmt).to(dev))
     assert torch.equal(_bytes(y2), _bytes(_fp8_cpu(rows, scale, fmt)))
     assert amax2.item() == rows.float().abs().max().item()
     if fmt == E4:
-        y3 = torch.empty(B * Lj, K, dtype=E4, device=dev)
+        y3 = poisoned((B * Lj, K), E4, dev)
         ops.cast_fp8_scaled(x, y3, scale, torch.zeros(1, device=dev))
         assert torch.equal(_bytes(y3), _bytes(y))
 
@@ -355,7 +350,7 @@ def test_gradients_vs_mfma(dev, lora):
     for fmt in ("e4m3", "e5m2"):                       # measure and print everything before the first assertion
         got = _grads(dev, fmt, lora)
         assert set(got) == set(ref)
-        rows = sorted(((_rel(got[n], ref[n]), _cos(got[n], ref[n]), n) for n in ref), reverse=True)
+        rows = sorted(((rel_l2(got[n], ref[n]), cosine(got[n], ref[n]), n) for n in ref), reverse=True)
         num = sum((got[n].double() - ref[n].double()).pow(2).sum().item() for n in ref)
         den = sum(ref[n].double().pow(2).sum().item() for n in ref)
         tot[fmt] = (num / den) ** 0.5

@@ -4,14 +4,11 @@ fp8="weights" runs of the same weights."""
 import pytest
 import torch
 
+from parity import all_written, poisoned, rel_l2
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 F8 = torch.float8_e4m3fn
-
-
-def _rel(a, b):
-    a = a.detach().double().cpu(); b = b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 def _e4m3_cpu(x_bf16, scale):
@@ -71,27 +68,27 @@ def test_gemm_mxfp8_random_vs_fp64(dev, epi, tail, M, N, K):
         At = (torch.randn(M, 64, generator=gen) * 0.5).to(BF); Wt = (torch.randn(N, 64, generator=gen) * 0.1).to(BF)
         ref = ref + At.double() @ Wt.double().t()
         kw["tail"] = (At.to(dev), Wt.to(dev))
-    out = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev)
     if epi == "bias":
         ops.gemm_mxfp8(aq, wq, out, sa, sw, bias.to(dev), **kw)
-        assert _rel(out, ref) < 5e-3
+        assert rel_l2(out, ref) < 5e-3
     elif epi == "gelu":
-        u = torch.empty(M, N, dtype=BF, device=dev)
+        u = poisoned((M, N), BF, dev)
         ops.gemm_mxfp8(aq, wq, out, sa, sw, bias.to(dev), epilogue=EPI_BIAS_GELU, pre_act_out=u, **kw)
-        assert _rel(u, ref) < 5e-3
-        assert _rel(out, _gelu_tanh(ref)) < 5e-3
+        assert rel_l2(u, ref) < 5e-3
+        assert rel_l2(out, _gelu_tanh(ref)) < 5e-3
     else:
         S = M // 2
         R = torch.randn(M, N, generator=gen).to(BF)
         gate = torch.randn(2, 3 * N, generator=gen)                  # two samples' gates, bstride 3 N (as a modulation vector slice)
-        branch = torch.empty(M, N, dtype=BF, device=dev)
+        branch = poisoned((M, N), BF, dev)
         gd = gate.to(dev)[:, :N]
         ops.gemm_mxfp8(aq, wq, out, sa, sw, bias.to(dev), epilogue=EPI_GATED_RES, residual=R.to(dev), gate_txt=gd, gate_vid=gd,
                        gate_bstride=3 * N, S=S, St=0, pre_act_out=branch, **kw)
         b_of = torch.arange(M) // S
         g = gate[:, :N].double()[b_of.clamp_max(1)]
-        assert _rel(branch, ref) < 5e-3
-        assert _rel(out, R.double() + g * ref) < 5e-3
+        assert rel_l2(branch, ref) < 5e-3
+        assert rel_l2(out, R.double() + g * ref) < 5e-3
 
 
 @pytest.mark.parametrize("epi", ["bias", "gelu"])
@@ -103,12 +100,13 @@ def test_gemm_mxfp8_fp8_output_copy_exact(dev, epi):
     M, N, K = 333, 512, 256
     aq, sa, _ = _quant(torch.randn(M, K, generator=gen), dev)
     wq, sw, _ = _quant(torch.randn(N, K, generator=gen) * K ** -0.5, dev)
-    out = torch.empty(M, N, dtype=BF, device=dev)
-    cq = torch.empty(M, N, dtype=F8, device=dev)
+    out = poisoned((M, N), BF, dev)
+    cq = poisoned((M, N), F8, dev)
     sq = torch.tensor([0.0031], device=dev)
     amax = torch.zeros(1, device=dev)
-    kw = dict(epilogue=EPI_BIAS_GELU, pre_act_out=torch.empty(M, N, dtype=BF, device=dev)) if epi == "gelu" else {}
+    kw = dict(epilogue=EPI_BIAS_GELU, pre_act_out=poisoned((M, N), BF, dev)) if epi == "gelu" else {}
     ops.gemm_mxfp8(aq, wq, out, sa, sw, None, out_fp8=(cq, sq, amax), **kw)
+    all_written(cq, "fp8 output copy", expect=_e4m3_cpu(out, sq).to(dev))
     assert torch.equal(_bytes(cq), _bytes(_e4m3_cpu(out, sq)))
     assert amax.item() == out.float().abs().max().item()
     assert (out.float().abs() > 448 * 0.0031).any()                 # some values saturate
@@ -121,12 +119,13 @@ def test_cast_fp8_scaled_exact(dev):
     B, Lj, L, off, K = 3, 50, 17, 29, 384
     x = (torch.randn(B * Lj, K, generator=gen) * 3).to(BF).to(dev)
     scale = torch.tensor([0.0057], device=dev)
-    y = torch.empty(B * L, K, dtype=F8, device=dev)
+    y = poisoned((B * L, K), F8, dev)
     cp = torch.full((B * L, K + 64), 5.0, dtype=BF, device=dev)
     amax = torch.zeros(1, device=dev)
     ops.cast_fp8_scaled(x, y, scale, amax, copy=cp[:, :K], rows=(L, Lj, off))
     rows = x.view(B, Lj, K)[:, off:off + L].reshape(B * L, K)
     assert torch.equal(cp[:, :K], rows) and bool((cp[:, K:] == 5.0).all())
+    all_written(y, "fp8 cast", expect=_e4m3_cpu(rows, scale).to(dev))
     assert torch.equal(_bytes(y), _bytes(_e4m3_cpu(rows, scale)))
     assert amax.item() == rows.float().abs().max().item()
     assert (rows.float().abs() > 448 * 0.0057).any()
@@ -148,15 +147,16 @@ def test_ln_modulate_fwd_fp8_exact(dev):
     modv = torch.randn(B, 6 * D, generator=gen).to(dev) * 0.3
     sh, sc = modv[:, :D], modv[:, D:2 * D]
     mod = (sh, sc, sh, sc, 6 * D)
-    y0 = torch.empty(M, D, dtype=BF, device=dev); y1 = torch.empty(M, D, dtype=BF, device=dev)
-    mean0, rstd0 = torch.empty(M, device=dev), torch.empty(M, device=dev)
-    mean1, rstd1 = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    y0 = poisoned((M, D), BF, dev); y1 = poisoned((M, D), BF, dev)
+    mean0, rstd0 = poisoned((M,), torch.float32, dev), poisoned((M,), torch.float32, dev)
+    mean1, rstd1 = poisoned((M,), torch.float32, dev), poisoned((M,), torch.float32, dev)
     ops.ln_modulate_fwd(x, y0, None, None, mod, mean0, rstd0, D, L, 0, 1e-6)
-    q = torch.empty(M, D, dtype=F8, device=dev)
+    q = poisoned((M, D), F8, dev)
     qs = torch.tensor([0.0123], device=dev)
     amax = torch.zeros(1, device=dev)
     ops.ln_modulate_fwd_fp8(x, y1, None, None, mod, mean1, rstd1, D, L, 0, 1e-6, q, qs, amax)
     assert torch.equal(y0, y1) and torch.equal(mean0, mean1) and torch.equal(rstd0, rstd1)
+    all_written(q, "fp8 copy of the modulated LayerNorm", expect=_e4m3_cpu(y1, qs).to(dev))
     assert torch.equal(_bytes(q), _bytes(_e4m3_cpu(y1, qs)))
     assert amax.item() == y1.float().abs().max().item()
 
@@ -234,12 +234,12 @@ def test_blocks_delayed_scaling_full_finetune(dev):
         assert torch.equal(h[:, 0], a2.cpu())
         assert torch.equal(st.scale.cpu(), h.max(1).values / 448.0)
     ob, ow, oq = res[False][0], res["weights"][0], res["mfma"][0]
-    e = _rel(oq, ob)
-    errs = sorted(((_rel(res["mfma"][1][n], res["weights"][1][n]), _rel(res["weights"][1][n], res[False][1][n]), n) for n in res["weights"][1]),
+    e = rel_l2(oq, ob)
+    errs = sorted(((rel_l2(res["mfma"][1][n], res["weights"][1][n]), rel_l2(res["weights"][1][n], res[False][1][n]), n) for n in res["weights"][1]),
                   reverse=True)
     lin = [x for x in errs if not x[2].endswith("norm.weight")]
     norms = [x for x in errs if x[2].endswith("norm.weight")]
-    print(f"[hunyuan mxfp8] output vs bf16 rel-L2 {e:.3e} (weights mode {_rel(ow, ob):.3e}); worst Linear gradient vs weights mode "
+    print(f"[hunyuan mxfp8] output vs bf16 rel-L2 {e:.3e} (weights mode {rel_l2(ow, ob):.3e}); worst Linear gradient vs weights mode "
           f"{lin[0][2]} {lin[0][0]:.2e}; q / k norm gradients (vs weights mode, weights mode vs bf16): "
           f"{[(n, f'{a:.2e}', f'{b:.2e}') for a, b, n in norms[:4]]}")
     assert not torch.equal(oq, ow)
@@ -279,13 +279,13 @@ def test_blocks_lora_tail(dev):
         out = m(img, txt, vec, tv, (cos, sin))
         out.backward(dout)
         res[mode] = (o_b - o_0, {n: m.lora._view(ts.grad, n).detach().clone() for n in m.lora.shapes}, o_b)
-    contrib = _rel(res["mfma"][0], res["weights"][0])
-    errs = sorted(((_rel(res["mfma"][1][n], res["weights"][1][n]), _rel(res["weights"][1][n], res[False][1][n]), n) for n in res["weights"][1]),
+    contrib = rel_l2(res["mfma"][0], res["weights"][0])
+    errs = sorted(((rel_l2(res["mfma"][1][n], res["weights"][1][n]), rel_l2(res["weights"][1][n], res[False][1][n]), n) for n in res["weights"][1]),
                   reverse=True)
     worst = errs[0][0]
-    print(f"[hunyuan mxfp8 lora] adapter contribution vs weights mode rel-L2 {contrib:.3e} (weights vs bf16 {_rel(res['weights'][0], res[False][0]):.3e}; "
+    print(f"[hunyuan mxfp8 lora] adapter contribution vs weights mode rel-L2 {contrib:.3e} (weights vs bf16 {rel_l2(res['weights'][0], res[False][0]):.3e}; "
           f"|contribution| / |out| {res['weights'][0].norm().item() / res['weights'][2].norm().item():.3e}; out mfma vs weights "
-          f"{_rel(res['mfma'][2], res['weights'][2]):.3e}); worst adapter gradients (vs weights, weights vs bf16) {[(n, f'{a:.2e}', f'{b:.2e}') for a, b, n in errs[:4]]}")
+          f"{rel_l2(res['mfma'][2], res['weights'][2]):.3e}); worst adapter gradients (vs weights, weights vs bf16) {[(n, f'{a:.2e}', f'{b:.2e}') for a, b, n in errs[:4]]}")
     assert res["weights"][0].norm().item() > 0.05 * res["weights"][2].norm().item()
     assert contrib < 0.25 and worst < 8e-2
     assert all(a < b for a, b, _ in errs)

@@ -12,17 +12,14 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from parity import rel_l2
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 
 
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
-
-
-def _rel(a, b):
-    a, b = a.detach().double().cpu(), b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
 
 
 def _worker(rank, world, port, lora, res):
@@ -67,18 +64,18 @@ def _worker(rank, world, port, lora, res):
         part = run(sl, dist.group.WORLD)
         m.set_sequence_parallel(None)
         valid = torch.ones(B, Lt, 1); valid[1, 7:] = 0
-        errs = {"out_img": _rel(part[0][:, :n], full[0][:, sl]), "out_txt": _rel(part[0][:, n:] * valid, full[0][:, Li:] * valid),
-                "dimg": _rel(part[1], full[1][:, sl])}
+        errs = {"out_img": rel_l2(part[0][:, :n], full[0][:, sl]), "out_txt": rel_l2(part[0][:, n:] * valid, full[0][:, Li:] * valid),
+                "dimg": rel_l2(part[1], full[1][:, sl])}
         for name, idx in (("dtxt", 2), ("dvec", 3)):
             tot = part[idx].to(dev); dist.all_reduce(tot)
-            errs[name] = _rel(tot.cpu() * (valid if idx == 2 else 1), full[idx] * (valid if idx == 2 else 1))
+            errs[name] = rel_l2(tot.cpu() * (valid if idx == 2 else 1), full[idx] * (valid if idx == 2 else 1))
         gsum = part[4].clone(); dist.all_reduce(gsum)
-        errs["params"] = _rel(gsum, full[4])
+        errs["params"] = rel_l2(gsum, full[4])
         worst = 0.0
         for name in owner.shapes:
             a, b = owner._view(gsum, name), owner._view(full[4], name)
             if b.norm().item() > 0:
-                worst = max(worst, _rel(a, b))
+                worst = max(worst, rel_l2(a, b))
         errs["worst_param"] = worst
         res[rank] = errs
         dist.barrier()
@@ -129,7 +126,7 @@ def _worker_model(rank, world, port, res):
         l_part, g_part = run(dist.group.WORLD)
         dist.all_reduce(l_part); dist.all_reduce(g_part)                             # what the data-parallel reducer does: the average over ranks
         l_part /= world; g_part /= world
-        errs = {"loss": abs(l_part.item() - l_full.item()) / l_full.item(), "adapter_grads": _rel(g_part, g_full)}
+        errs = {"loss": abs(l_part.item() - l_full.item()) / l_full.item(), "adapter_grads": rel_l2(g_part, g_full)}
         # training_step: the ranks of a group draw ONE sigma and ONE noise
         torch.manual_seed(100 + rank)
         batch = {"latents": x0, "prompt_embeds": text, "prompt_attention_mask": mask.to(dev), "pooled_prompt_embeds": pooled}

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 import cogvideox_oracle as O
+from parity import close, poisoned, poisoned_like, untouched
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -17,14 +18,6 @@ BF = torch.bfloat16
 
 def rb(x):      # bf16-round but keep fp32 (what the device kernel actually sees)
     return x.to(BF).float()
-
-
-def close(a, b, rtol, atol, what=""):
-    a = a.detach().float().cpu(); b = b.detach().float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    bad = (err > tol).float().mean().item()
-    assert bad == 0.0, f"{what}: {bad*100:.4f}% out of tol, max err {err.max().item():.4g}, ref absmax {b.abs().max().item():.4g}"
 
 
 # ------------------------------------------------------------------ GEMM
@@ -44,10 +37,10 @@ def test_gemm_bias(dev, M, N, K, gemm_tile):
     g = torch.Generator().manual_seed(M + N + K)
     a = rb(torch.randn(M, K, generator=g)); w = rb(torch.randn(N, K, generator=g) * 0.05); b = rb(torch.randn(N, generator=g))
     ref = a @ w.T + b
-    out = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev)
     ops.gemm(a.to(dev, BF), w.to(dev, BF), out, b.to(dev, BF))
     close(out, ref, 1e-2, 1e-2, "gemm bf16 out")
-    out32 = torch.empty(M, N, dtype=torch.float32, device=dev)
+    out32 = poisoned((M, N), torch.float32, dev)
     ops.gemm(a.to(dev, BF), w.to(dev, BF), out32, b.to(dev, BF))
     close(out32, ref, 1e-4, 2e-3, "gemm fp32 out")
 
@@ -65,7 +58,7 @@ def test_gemm_strided_and_epilogues(dev, gemm_tile, N, B, S, St):
     A = abig.to(dev, BF); W = w.to(dev, BF); Bi = bias.to(dev, BF)
     # GELU epilogue: two outputs
     u_ref = a @ w.T + bias
-    out = torch.empty(M, N, dtype=BF, device=dev); pre = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev); pre = poisoned((M, N), BF, dev)
     ops.gemm(A, W, out, Bi, epilogue=ops.EPI_BIAS_GELU, pre_act_out=pre, K=K)
     close(pre, u_ref, 1e-2, 1e-2, "pre-activation")
     close(out, F.gelu(u_ref, approximate="tanh"), 1e-2, 1e-2, "gelu")
@@ -74,17 +67,20 @@ def test_gemm_strided_and_epilogues(dev, gemm_tile, N, B, S, St):
     gate_rows = torch.stack([gates[m // S, 0 if (m % S) < St else 1] for m in range(M)])
     ref = R + gate_rows * u_ref
     G = gates.to(dev)
+    out = poisoned((M, N), BF, dev)            # a fresh poisoned output per epilogue: the previous one's values are not evidence
     ops.gemm(A, W, out, Bi, epilogue=ops.EPI_GATED_RES, residual=R.to(dev, BF), gate_txt=G[:, 0], gate_vid=G[:, 1],
              gate_bstride=2 * N, S=S, St=St, K=K)
     close(out, ref, 1e-2, 2e-2, "gated residual")
     # positional-table add (gate None, r_mod)
     tab = rb(torch.randn(S, N, generator=g))
+    out = poisoned((M, N), BF, dev)
     ops.gemm(A, W, out, Bi, epilogue=ops.EPI_GATED_RES, residual=tab.to(dev, BF), r_mod=S, K=K)
     close(out, tab.repeat(B, 1) + u_ref, 1e-2, 2e-2, "pos add")
     # dGELU
     U = rb(torch.randn(M, N, generator=g))
     uu = U.clone().requires_grad_(True)
     F.gelu(uu, approximate="tanh").sum().backward()
+    out = poisoned((M, N), BF, dev)
     ops.gemm(A, W, out, None, epilogue=ops.EPI_DGELU, pre_act_in=U.to(dev, BF), K=K)
     close(out, (a @ w.T) * uu.grad, 1e-2, 2e-2, "dgelu")
 
@@ -125,8 +121,8 @@ def test_attn_fwd(dev, B, S, H, spike, pre):
     q, k, v = [qkv_ref[:, :, i].permute(0, 2, 1, 3).double() for i in range(3)]
     o_ref, lse_ref = O.attention(q, k, v)
     d = qkv_dev.to(dev, BF).view(B, S, 3 * H * 64)
-    o = torch.empty(B, S, H * 64, dtype=BF, device=dev)
-    lse2 = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    o = poisoned((B, S, H * 64), BF, dev)
+    lse2 = poisoned((B, H, S), torch.float32, dev)
     ops.attn_fwd(d[:, :, :H * 64], d[:, :, H * 64:2 * H * 64], d[:, :, 2 * H * 64:], o, lse2, B, H, S, q_prescaled=pre, tiles16=tiles16)
     close(o.view(B, S, H, 64).permute(0, 2, 1, 3), o_ref, 2e-2, 1e-2, "attn out")
     close(lse2 * math.log(2.0), lse_ref, 1e-4, 2e-3, "lse")
@@ -159,11 +155,11 @@ def test_attn_bwd(dev, B, S, H, spike, pre, chain):
     d = qkv.to(dev, BF).view(B, S, 3 * H * 64)
     D = H * 64
     qd, kd, vd = d[:, :, :D], d[:, :, D:2 * D], d[:, :, 2 * D:]
-    o = torch.empty(B, S, D, dtype=BF, device=dev); lse2 = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    o = poisoned((B, S, D), BF, dev); lse2 = poisoned((B, H, S), torch.float32, dev)
     ops.attn_fwd(qd, kd, vd, o, lse2, B, H, S, q_prescaled=pre)
-    dq = torch.zeros(B, S, D, dtype=torch.float32, device=dev)
-    dk = torch.empty(B, S, D, dtype=BF, device=dev); dv = torch.empty(B, S, D, dtype=BF, device=dev)
-    delta = torch.empty(B * H * S, dtype=torch.float32, device=dev)
+    dq = torch.zeros(B, S, D, dtype=torch.float32, device=dev)               # in/out: fp32 atomics accumulate into it
+    dk = poisoned((B, S, D), BF, dev); dv = poisoned((B, S, D), BF, dev)      # written whole
+    delta = poisoned((B * H * S,), torch.float32, dev)             # scratch: written by the first pass before it is read
     ws = ops.attn_bwd_chain_workspace(B, H, S, dev) if chain else None
     assert (ws is not None) == bool(chain)
     try:
@@ -198,12 +194,12 @@ def test_attn_bwd_timeout_is_sticky_and_the_optimizer_refuses_the_step(dev):
     g = torch.Generator().manual_seed(5)
     d = rb(torch.randn(B, S, 3 * D, generator=g)).to(dev, BF)
     qd, kd, vd = d[:, :, :D], d[:, :, D:2 * D], d[:, :, 2 * D:]
-    o = torch.empty(B, S, D, dtype=BF, device=dev); lse2 = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    o = poisoned((B, S, D), BF, dev); lse2 = poisoned((B, H, S), torch.float32, dev)
     ops.attn_fwd(qd, kd, vd, o, lse2, B, H, S)
     do = rb(torch.randn(B, S, D, generator=g)).to(dev, BF)
-    dq = torch.zeros(B, S, D, dtype=torch.float32, device=dev)
-    dk = torch.empty(B, S, D, dtype=BF, device=dev); dv = torch.empty(B, S, D, dtype=BF, device=dev)
-    delta = torch.empty(B * H * S, dtype=torch.float32, device=dev)
+    dq = torch.zeros(B, S, D, dtype=torch.float32, device=dev)      # in/out: fp32 atomics accumulate into it
+    dk = poisoned((B, S, D), BF, dev); dv = poisoned((B, S, D), BF, dev)
+    delta = poisoned((B * H * S,), torch.float32, dev)
     ws = ops.attn_bwd_chain_workspace(B, H, S, dev)
     assert ws is not None
     ops.attn_bwd_chain_errors_clear()
@@ -253,11 +249,12 @@ def test_attn_bwd_timeout_is_repaired_by_redoing_the_launch_without_chains(dev):
     g = torch.Generator().manual_seed(6)
     d = rb(torch.randn(B, S, 3 * D, generator=g)).to(dev, BF)
     qd, kd, vd = d[:, :, :D], d[:, :, D:2 * D], d[:, :, 2 * D:]
-    o = torch.empty(B, S, D, dtype=BF, device=dev); lse2 = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+    o = poisoned((B, S, D), BF, dev); lse2 = poisoned((B, H, S), torch.float32, dev)
     ops.attn_fwd(qd, kd, vd, o, lse2, B, H, S)
     do = rb(torch.randn(B, S, D, generator=g)).to(dev, BF)
-    delta = torch.empty(B * H * S, dtype=torch.float32, device=dev)
-    mk = lambda: (torch.zeros(B, S, D, dtype=torch.float32, device=dev), torch.empty(B, S, D, dtype=BF, device=dev), torch.empty(B, S, D, dtype=BF, device=dev))
+    delta = poisoned((B * H * S,), torch.float32, dev)
+    # dq is in/out (fp32 atomics accumulate into zeros); dk, dv are written whole
+    mk = lambda: (torch.zeros(B, S, D, dtype=torch.float32, device=dev), poisoned((B, S, D), BF, dev), poisoned((B, S, D), BF, dev))
     dq0, dk0, dv0 = mk()
     ops.attn_bwd(qd, kd, vd, o, do, lse2, delta, dq0, dk0, dv0, B, H, S, chain_ws=None)          # atomics only: the reference
     ws = ops.attn_bwd_chain_workspace(B, H, S, dev)
@@ -283,11 +280,11 @@ def test_attn_bwd_timeout_is_repaired_by_redoing_the_launch_without_chains(dev):
 
 
 # ------------------------------------------------------------------ norms
-@pytest.mark.parametrize("D", [128, 1920, 3072])
-def test_ln_modulate(dev, D):
+def _ln_modulate_case(dev, D, B=2, S=37, St=5, affine=True):
+    """vt_ln_modulate_fwd / _bwd on a strided [M, D + 64] pair of buffers: y, mean, rstd and dx are written whole (poisoned before the
+    launch), the 64 pad columns of y are never written; then the plain LayerNorm call (no modulation) when there is an affine part"""
     from vt355 import ops
     g = torch.Generator().manual_seed(D)
-    B, S, St = 2, 37, 5
     M = B * S
     x = rb(torch.randn(M, D, generator=g) * 2 + 0.5)
     ga = rb(1 + 0.1 * torch.randn(D, generator=g)); be = rb(0.1 * torch.randn(D, generator=g))
@@ -297,24 +294,58 @@ def test_ln_modulate(dev, D):
     shift = torch.where(is_txt[:, None], mod[rows_b, 3 * D:4 * D], mod[rows_b, 0:D])
     scale = torch.where(is_txt[:, None], mod[rows_b, 4 * D:5 * D], mod[rows_b, D:2 * D])
     xx = x.clone().requires_grad_(True)
-    ref = O.ln_modulate(xx, ga, be, scale, shift, 1e-5)
+    ref = O.ln_modulate(xx, ga, be, scale, shift, 1e-5) if affine else F.layer_norm(xx, (D,), None, None, 1e-5) * (1 + scale) + shift
     dy = rb(torch.randn(M, D, generator=g)); dres = rb(torch.randn(M, D, generator=g))
     ref.backward(dy)
     X = torch.zeros(M, D + 64, dtype=BF, device=dev); X[:, :D] = x.to(dev, BF)      # strided input
-    Y = torch.empty(M, D + 64, dtype=BF, device=dev)
-    mean = torch.empty(M, device=dev); rstd = torch.empty(M, device=dev)
+    Y = poisoned((M, D + 64), BF, dev)
+    mean = poisoned((M,), torch.float32, dev); rstd = poisoned((M,), torch.float32, dev)
     Md = mod.to(dev)
-    ops.ln_modulate_fwd(X, Y, ga.to(dev, BF), be.to(dev, BF),
-                        (Md[:, 3 * D:], Md[:, 4 * D:], Md[:, 0:], Md[:, D:], 6 * D), mean, rstd, D, S, St, 1e-5)
+    gad, bed = (ga.to(dev, BF), be.to(dev, BF)) if affine else (None, None)
+    ops.ln_modulate_fwd(X, Y, gad, bed, (Md[:, 3 * D:], Md[:, 4 * D:], Md[:, 0:], Md[:, D:], 6 * D), mean, rstd, D, S, St, 1e-5)
     close(Y[:, :D], ref, 1e-2, 2e-2, "ln_modulate fwd")
+    untouched(Y, (slice(None), slice(0, D)), "ln_modulate fwd pad columns")
     close(mean, x.mean(1), 1e-4, 1e-4, "mean")
-    dx = torch.empty(M, D, dtype=BF, device=dev)
-    ops.ln_modulate_bwd(dy.to(dev, BF), X, mean, rstd, ga.to(dev, BF), (Md[:, 4 * D:], Md[:, D:], 6 * D),
-                        dres.to(dev, BF), dx, D, S, St)
+    close(rstd, 1.0 / (x.double().var(1, unbiased=False) + 1e-5).sqrt(), 1e-4, 1e-4, "rstd")
+    dx = poisoned((M, D), BF, dev)
+    ops.ln_modulate_bwd(dy.to(dev, BF), X, mean, rstd, gad, (Md[:, 4 * D:], Md[:, D:], 6 * D), dres.to(dev, BF), dx, D, S, St)
     close(dx, xx.grad + dres, 2e-2, 2e-2, "ln_modulate bwd")
-    # plain LayerNorm (no modulation, affine) == norm_final
-    ops.ln_modulate_fwd(X, Y, ga.to(dev, BF), be.to(dev, BF), None, None, None, D, S, St, 1e-5)
-    close(Y[:, :D], F.layer_norm(x, (D,), ga, be, 1e-5), 1e-2, 2e-2, "plain LN")
+    if affine:
+        # plain LayerNorm (no modulation, affine) == norm_final
+        Y = poisoned((M, D + 64), BF, dev)
+        ops.ln_modulate_fwd(X, Y, gad, bed, None, None, None, D, S, St, 1e-5)
+        close(Y[:, :D], F.layer_norm(x, (D,), ga, be, 1e-5), 1e-2, 2e-2, "plain LN")
+        untouched(Y, (slice(None), slice(0, D)), "plain LN pad columns")
+
+
+@pytest.mark.parametrize("D", [128, 1920, 3072, 8, 512, 4096])
+def test_ln_modulate(dev, D):
+    """the three template branches (1 / 4 / 8 chunks of 8 elements per lane): D = 128, 1920, 3072; one chunk in one lane (D = 8), exactly
+    64 chunks (D = 512, the last size of the first branch) and the limit D = 4096"""
+    _ln_modulate_case(dev, D)
+
+
+@pytest.mark.parametrize("D,B,S,St,affine", [(128, 1, 1, 0, True), (1920, 1, 1, 1, True), (128, 2, 37, 0, True), (1920, 2, 37, 37, True),
+                                            (128, 2, 37, 5, False), (3072, 2, 37, 5, False)],
+                         ids=["M1_video_row", "M1_text_row", "St0", "StS", "no_affine_D128", "no_affine_D3072"])
+def test_ln_modulate_edges(dev, D, B, S, St, affine):
+    """a single row (one wave of a four-row block), no text rows, only text rows, and modulation without the affine part (gamma = beta =
+    None with shift / scale: the norm1 / norm2 of a block whose LayerNorm has no parameters), forward and backward"""
+    _ln_modulate_case(dev, D, B, S, St, affine)
+
+
+def test_ln_modulate_refuses_rows_wider_than_4096(dev):
+    """D = 4104 is a multiple of 8 past the 8 chunks per lane the kernels hold in registers: refused on the host, nothing is written"""
+    from vt355 import ops
+    from vt355._lib import VtError
+    M, D = 4, 4104
+    X = torch.zeros(M, D, dtype=BF, device=dev); Y = poisoned((M, D), BF, dev)
+    mean = poisoned((M,), torch.float32, dev); rstd = poisoned((M,), torch.float32, dev)
+    with pytest.raises(VtError, match="vt_ln_modulate_fwd"):
+        ops.ln_modulate_fwd(X, Y, None, None, None, mean, rstd, D, M, 0, 1e-5)
+    with pytest.raises(VtError, match="vt_ln_modulate_bwd"):
+        ops.ln_modulate_bwd(X, X, mean, rstd, None, None, None, Y, D, M, 0)
+    untouched(Y, [], "refused ln_modulate: y"); untouched(mean, [], "refused ln_modulate: mean")
 
 
 def test_qk_layernorm(dev):
@@ -330,14 +361,16 @@ def test_qk_layernorm(dev):
     kh = F.layer_norm(x[:, D:2 * D].view(M, H, 64), (64,), gk, bk, 1e-6).reshape(M, D)
     dqh = torch.randn(M, D, generator=g); dkh = rb(torch.randn(M, D, generator=g))
     (qh * dqh).sum().add((kh * dkh).sum()).backward()
-    Q = qkv.to(dev, BF); out = torch.empty(M, 2 * D, dtype=BF, device=dev)
-    mean = torch.empty(M, 2 * H, device=dev); rstd = torch.empty(M, 2 * H, device=dev)
+    Q = qkv.to(dev, BF); out = poisoned((M, 2 * D), BF, dev)
+    mean = poisoned((M, 2 * H), torch.float32, dev); rstd = poisoned((M, 2 * H), torch.float32, dev)
     dv = [t.to(dev, BF) for t in (gq, bq, gk, bk)]
     ops.qk_layernorm_fwd(Q, out, dv[0], dv[1], dv[2], dv[3], mean, rstd, H, 1e-6)
     close(out[:, :D], qh, 1e-2, 2e-2, "q_hat"); close(out[:, D:], kh, 1e-2, 2e-2, "k_hat")
-    dqkv = torch.zeros(M, 3 * D, dtype=BF, device=dev)
+    dqkv = poisoned((M, 3 * D), BF, dev)              # the q and k thirds are written whole, the v third is not this kernel's
     ops.qk_layernorm_bwd(dqh.to(dev), dkh.to(dev, BF), Q, mean, rstd, dv[0], dv[2], dqkv, H)
     close(dqkv[:, :2 * D], x.grad[:, :2 * D], 2e-2, 2e-2, "qk-LN bwd")
+    untouched(dqkv, (slice(None), slice(0, 2 * D)), "qk-LN bwd: the v third")
+    out = poisoned((M, 2 * D), BF, dev); mean = poisoned((M, 2 * H), torch.float32, dev); rstd = poisoned((M, 2 * H), torch.float32, dev)
     ops.qk_layernorm_fwd(Q, out, dv[0], dv[1], dv[2], dv[3], mean, rstd, H, 1e-6, q_scale=SC2)
     close(out[:, :D], qh * SC2, 1e-2, 5e-3, "q_hat prescaled"); close(out[:, D:], kh, 1e-2, 2e-2, "k_hat untouched")
 
@@ -368,21 +401,22 @@ def test_qk_layernorm_rope(dev):
     qh, kh = ref(x[:, :D], prm[0], prm[1]), ref(x[:, D:2 * D], prm[2], prm[3])
     dqh = torch.randn(M, D, generator=g); dkh = rb(torch.randn(M, D, generator=g))
     (qh * dqh.double()).sum().add((kh * dkh.double()).sum()).backward()
-    Q = qkv.to(dev, BF); out = torch.empty(M, 2 * D, dtype=BF, device=dev)
-    mean = torch.empty(M, 2 * H, device=dev); rstd = torch.empty(M, 2 * H, device=dev)
+    Q = qkv.to(dev, BF); out = poisoned((M, 2 * D), BF, dev)
+    mean = poisoned((M, 2 * H), torch.float32, dev); rstd = poisoned((M, 2 * H), torch.float32, dev)
     dv = [t.to(dev, BF) for t in (gq, bq, gk, bk)]
     rope = (cos.to(dev).contiguous(), sin.to(dev).contiguous(), S, St)
     ops.qk_layernorm_fwd(Q, out, dv[0], dv[1], dv[2], dv[3], mean, rstd, H, 1e-6, rope=rope)
     close(out[:, :D], qh.float(), 1e-2, 2e-2, "rope q_hat"); close(out[:, D:], kh.float(), 1e-2, 2e-2, "rope k_hat")
     # text rows are untouched by the rotation: identical bits to the rope-free kernel
-    out0 = torch.empty_like(out)
+    out0 = poisoned_like(out)
     ops.qk_layernorm_fwd(Q, out0, dv[0], dv[1], dv[2], dv[3], mean, rstd, H, 1e-6)
     o3, o03 = out.view(B, S, 2 * D), out0.view(B, S, 2 * D)
     assert torch.equal(o3[:, :St], o03[:, :St]) and not torch.equal(o3[:, St:], o03[:, St:])
-    dqkv = torch.zeros(M, 3 * D, dtype=BF, device=dev)
+    dqkv = poisoned((M, 3 * D), BF, dev)              # the q and k thirds are written whole, the v third is not this kernel's
     ops.qk_layernorm_bwd(dqh.to(dev), dkh.to(dev, BF), Q, mean, rstd, dv[0], dv[2], dqkv, H, rope=rope)
     close(dqkv[:, :2 * D], x.grad[:, :2 * D].float(), 2e-2, 2e-2, "rope qk-LN bwd")
-    pg = torch.zeros(2, 2, 64, device=dev)
+    untouched(dqkv, (slice(None), slice(0, 2 * D)), "rope qk-LN bwd: the v third")
+    pg = torch.zeros(2, 2, 64, device=dev)                        # in/out: the parameter gradients accumulate
     ops.qk_ln_param_grads(dqh.to(dev), dkh.to(dev, BF), Q, mean, rstd, pg, H, rope=rope)
     for w in range(2):
         for gb in range(2):
@@ -397,7 +431,7 @@ def test_timestep_embedding_golden(dev):
     from vt355 import ops
     gold = np.load(__import__("os").path.join(__import__("os").path.dirname(__file__), "golden", "timestep_embedding.npz"))
     t = torch.from_numpy(gold["t"]).to(dev)
-    out = torch.empty(len(t), 1920, dtype=BF, device=dev)
+    out = poisoned((len(t), 1920), BF, dev)
     ops.timestep_embedding(t, out)
     close(out, torch.from_numpy(gold["emb1920"]), 8e-3, 8e-3, "sinusoid vs reference golden")
 
@@ -407,12 +441,12 @@ def test_patchify_roundtrip_and_order(dev):
     g = torch.Generator().manual_seed(3)
     B, Fr, C, H, W, P = 2, 3, 16, 6, 8, 2
     img = rb(torch.randn(B, Fr, C, H, W, generator=g))
-    tok = torch.empty(B * Fr * (H // P) * (W // P), C * P * P, dtype=BF, device=dev)
+    tok = poisoned((B * Fr * (H // P) * (W // P), C * P * P), BF, dev)
     ops.patchify(img.to(dev, BF), tok, P)
     # oracle order: conv2d weight flattened (c p q); tokens (t h w)
     ref = img.reshape(B, Fr, C, H // P, P, W // P, P).permute(0, 1, 3, 5, 2, 4, 6).reshape(-1, C * P * P)
     close(tok, ref, 0, 0, "patchify")
-    back = torch.empty(B, Fr, C, H, W, dtype=BF, device=dev)
+    back = poisoned((B, Fr, C, H, W), BF, dev)
     ops.unpatchify(tok, back, P)
     close(back, img, 0, 0, "unpatchify roundtrip")
 
@@ -425,7 +459,7 @@ def test_noise_loss_adamw(dev):
     t = torch.tensor([10, 500, 990])
     x0 = torch.randn(B, per, generator=g); nz = torch.randn(B, per, generator=g)
     sa = abar[t].sqrt().float(); sb = (1 - abar[t]).sqrt().float(); w = (1 / (1 - abar[t])).float()
-    noisy = torch.empty(B, per, dtype=BF, device=dev)
+    noisy = poisoned((B, per), BF, dev)
     ops.add_noise(x0.to(dev), nz.to(dev), sa.to(dev), sb.to(dev), noisy)
     close(noisy, O.add_noise(x0, nz, t, abar.float()), 1e-2, 1e-2, "add_noise")
     v = rb(torch.randn(B, per, generator=g)).requires_grad_(True)
@@ -433,7 +467,7 @@ def test_noise_loss_adamw(dev):
     pred = O.get_velocity(v, nb, t, abar.float())
     loss_ref = torch.mean((w[:, None] * (pred - x0) ** 2), dim=1).mean()
     loss_ref.backward()
-    loss = torch.zeros(1, device=dev); part = torch.empty(512, device=dev); dvp = torch.empty(B, per, dtype=BF, device=dev)
+    loss = poisoned((1,), torch.float32, dev); part = poisoned((512,), torch.float32, dev); dvp = poisoned((B, per), BF, dev)
     ops.diffusion_loss(v.detach().to(dev, BF), noisy, x0.to(dev), sa.to(dev), sb.to(dev), w.to(dev), loss, part, dvp, 1.0)
     close(loss, loss_ref.reshape(1), 1e-4, 1e-5, "loss")
     close(dvp, v.grad, 1e-2, 1e-2 * v.grad.abs().max().item(), "dloss/dv")
@@ -442,7 +476,8 @@ def test_noise_loss_adamw(dev):
     p = torch.randn(n, generator=g); gr = [torch.randn(n, generator=g) * 0.1 for _ in range(3)]
     pt = p.clone().requires_grad_(True)
     opt = torch.optim.AdamW([pt], lr=1e-2)
-    P = p.to(dev); Mo = torch.zeros(n, device=dev); Vo = torch.zeros(n, device=dev); Pb = torch.empty(n, dtype=BF, device=dev)
+    # in/out: the parameter and AdamW's two moments; the bf16 copy is written whole
+    P = p.to(dev); Mo = torch.zeros(n, device=dev); Vo = torch.zeros(n, device=dev); Pb = poisoned((n,), BF, dev)
     for i in range(3):
         pt.grad = gr[i].clone(); opt.step()
         ops.adamw(P, gr[i].to(dev), Mo, Vo, Pb, 1e-2, 0.9, 0.999, 1e-8, 1e-2, i + 1)
@@ -461,27 +496,27 @@ def test_lora_kernels(dev):
     close(X[:, K:K + 12], x @ A.T, 1e-2, 1e-2, "lora_down")
     assert X[:, K + 12:].abs().max().item() == 0.0
     dy = rb(torch.randn(M, N, generator=g)); T = X[:, K:K + 16].float().cpu()
-    out = torch.zeros(N, r, device=dev)
+    out = torch.zeros(N, r, device=dev)      # in/out: the kernel adds into it
     ops.skinny_tn(dy.to(dev, BF), X[:, K + 4:], r, out, r, 1, 0.25, N)
     close(out, 0.25 * dy.T @ T[:, 4:8], 1e-3, 1e-2, "skinny_tn R=4")
-    out16 = torch.zeros(12, K, device=dev)
+    out16 = torch.zeros(12, K, device=dev)      # in/out: the kernel adds into it
     dT = rb(torch.randn(M, 16, generator=g)); dT[:, 12:] = 0
     ops.skinny_tn(X, dT.to(dev, BF), 12, out16, 1, K, 1.0, K)
     close(out16, dT[:, :12].T @ x, 1e-3, 1e-2, "skinny_tn R=12")
-    out16b = torch.zeros(12, K, device=dev)
+    out16b = torch.zeros(12, K, device=dev)      # in/out: the kernel adds into it
     ops.skinny_tn(X, dT.to(dev, BF), 12, out16b, 1, K, 1.0, K, use_workspace=True)        # two-stage path
     close(out16b, dT[:, :12].T @ x, 1e-3, 1e-2, "skinny_tn R=12 (two-stage)")
     dx = rb(torch.randn(M, K, generator=g)); DX = dx.to(dev, BF).clone()
     ops.lora_up_add(DX, dT.to(dev, BF), A.to(dev, BF), 12, K)
     close(DX, dx + dT[:, :12] @ A, 1e-2, 2e-2, "lora_up_add")
     Bc = torch.randn(3 * N, r, generator=g)
-    W = torch.full((3 * N, K + 64), 7.0, dtype=BF, device=dev)
+    W = torch.full((3 * N, K + 64), 7.0, dtype=BF, device=dev)      # sentinel: the columns left of the packed slice are asserted below
     ops.lora_pack_b(Bc.to(dev), W[:, K:], K + 64, 3, N, r, 0.25)
     ref = torch.zeros(3 * N, 64)
     for j in range(3):
         ref[j * N:(j + 1) * N, j * r:(j + 1) * r] = 0.25 * Bc[j * N:(j + 1) * N]
     close(W[:, K:], ref, 1e-2, 1e-3, "pack_b"); assert (W[:, :K] == 7).all()
-    WT = torch.full((K + 64, 3 * N), 7.0, dtype=BF, device=dev)
+    WT = torch.full((K + 64, 3 * N), 7.0, dtype=BF, device=dev)      # sentinel: the rows above the packed slice
     ops.lora_pack_bt(Bc.to(dev), WT[K:], 3 * N, 3, N, r, 0.25)
     close(WT[K:], ref.T, 1e-2, 1e-3, "pack_bt")
 
@@ -493,7 +528,7 @@ def test_gemm_nt(dev, M, P, Q):
     g = torch.Generator().manual_seed(M + P)
     a = rb(torch.randn(M, P + 64, generator=g)); b = rb(torch.randn(M, Q + 8, generator=g))     # strided operands
     ref = a[:, :P].T @ b[:, :Q]
-    c = torch.full((P, Q), 3.0, device=dev)
+    c = torch.full((P, Q), 3.0, device=dev)      # in/out: accumulate=True adds to the 3.0s; the overwrite call then writes it whole
     ops.gemm_nt(a.to(dev, BF), b.to(dev, BF), c, P=P, Q=Q, alpha=0.5, accumulate=True)
     close(c, 3.0 + 0.5 * ref, 2e-3, 2e-3 * ref.abs().max().item(), "gemm_nt accumulate")
     ops.gemm_nt(a.to(dev, BF), b.to(dev, BF), c, P=P, Q=Q, alpha=1.0, accumulate=False)
@@ -534,10 +569,10 @@ def test_group_colsum(dev):
     M = B * S
     x = rb(torch.randn(M, D, generator=g)); y = rb(torch.randn(M, D, generator=g) * 2 + 1)
     mean = y.mean(1); rstd = 1.0 / (y.var(1, unbiased=False) + 1e-5).sqrt()
-    o1 = torch.zeros(1, D, device=dev)
+    o1 = torch.zeros(1, D, device=dev)      # in/out: the kernel adds into it
     ops.group_colsum(x.to(dev, BF), o1)
     close(o1[0], x.sum(0), 1e-4, 1e-3, "colsum")
-    o1 = torch.zeros(2 * B, D, device=dev); o2 = torch.zeros(2 * B, D, device=dev)
+    o1 = torch.zeros(2 * B, D, device=dev); o2 = torch.zeros(2 * B, D, device=dev)      # in/out: the kernel adds into it
     ops.group_colsum(x.to(dev, BF), o1, y=y.to(dev, BF), out2=o2, mean=mean.to(dev), rstd=rstd.to(dev), S=S, St=St, grouped=True)
     yn = (y - mean[:, None]) * rstd[:, None]
     for b in range(B):
@@ -555,7 +590,7 @@ def test_group_colsum_per_sample_groups_whole_rows(dev):
     M = B * S
     x = rb(torch.randn(M, D, generator=g)); y = rb(torch.randn(M, D, generator=g) * 2 + 1)
     mean = y.mean(1); rstd = 1.0 / (y.var(1, unbiased=False) + 1e-5).sqrt()
-    o1 = torch.zeros(B, 6 * D, device=dev); o2 = torch.zeros(B, 6 * D, device=dev)
+    o1 = torch.zeros(B, 6 * D, device=dev); o2 = torch.zeros(B, 6 * D, device=dev)      # in/out: the kernel adds into it; the columns outside the two slices must stay 0
     ops.group_colsum(x.to(dev, BF), o1[:, 3 * D:], y=y.to(dev, BF), out2=o2[:, 4 * D:], mean=mean.to(dev), rstd=rstd.to(dev), D=D, S=S, St=0,
                      grouped=True, o_bstride=6 * D, o_segstride=0)
     yn = (y.double() - mean[:, None].double()) * rstd[:, None].double()
@@ -574,7 +609,7 @@ def test_group_colsum_single_sample_group(dev):
     S, D = 4104, 384
     x = rb(torch.randn(S, D, generator=g)); y = rb(torch.randn(S, D, generator=g) * 2 + 1)
     mean = y.mean(1); rstd = 1.0 / (y.var(1, unbiased=False) + 1e-5).sqrt()
-    o1 = torch.zeros(1, 3 * D, device=dev); o2 = torch.zeros(1, 3 * D, device=dev)
+    o1 = torch.zeros(1, 3 * D, device=dev); o2 = torch.zeros(1, 3 * D, device=dev)      # in/out: the kernel adds into it; the columns outside the two slices must stay 0
     ops.group_colsum(x.to(dev, BF), o1[:, D:], y=y.to(dev, BF), out2=o2[:, 2 * D:], mean=mean.to(dev), rstd=rstd.to(dev), D=D, S=S, St=0, grouped=True,
                      o_bstride=3 * D, o_segstride=0)
     yn = (y.double() - mean[:, None].double()) * rstd[:, None].double()
@@ -595,11 +630,11 @@ def test_group_colsum_narrow_matrices(dev, M, D):
     g = torch.Generator().manual_seed(M + D)
     x = rb(torch.randn(M, D, generator=g))
     ref = x.double().sum(0)
-    o = torch.full((1, D), 3.0, device=dev)
+    o = torch.full((1, D), 3.0, device=dev)      # in/out: the kernel adds into it (3.0 + sums)
     ops.group_colsum(x.to(dev, BF), o)
     close(o[0] - 3.0, ref.float(), 1e-4, 2e-3 * ref.abs().max().item(), "narrow colsum")
     wide = torch.zeros(M, D + 8, dtype=BF, device=dev); wide[:, :D] = x.to(dev, BF)
-    o2 = torch.zeros(1, D, device=dev)
+    o2 = torch.zeros(1, D, device=dev)      # in/out: the kernel adds into it
     ops.group_colsum(wide[:, :D], o2, D=D)
     close(o2[0], ref.float(), 1e-4, 2e-3 * ref.abs().max().item(), "strided colsum")
     y = rb(torch.randn(M, D, generator=g) * 2 + 1)
@@ -607,7 +642,7 @@ def test_group_colsum_narrow_matrices(dev, M, D):
     for stats in (False, True):
         yn = ((y - mean[:, None]) * rstd[:, None]) if stats else y
         ref2 = (x.double() * yn.double()).sum(0)
-        a = torch.zeros(1, D, device=dev); b2 = torch.full((1, D), -1.0, device=dev)
+        a = torch.zeros(1, D, device=dev); b2 = torch.full((1, D), -1.0, device=dev)      # in/out: the kernel adds into it (b2: -1.0 + sums)
         ops.group_colsum(wide[:, :D], a, y=y.to(dev, BF), out2=b2, mean=mean.to(dev) if stats else None, rstd=rstd.to(dev) if stats else None, D=D)
         close(a[0], ref.float(), 1e-4, 2e-3 * ref.abs().max().item(), "colsum next to the product sums")
         close(b2[0] + 1.0, ref2.float(), 1e-4, 3e-3 * ref2.abs().max().item(), "column sums of x * y")
@@ -650,7 +685,7 @@ def test_rmsnorm(dev, M, D):
     x = xb[:, :D]
     ref = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6) * w
     X = xb.to(dev, BF)
-    y = torch.full((M, D + 16), 9.0, dtype=BF, device=dev)
+    y = torch.full((M, D + 16), 9.0, dtype=BF, device=dev)      # sentinel: the pad columns are asserted below
     ops.rmsnorm(X[:, :D], w.to(dev, BF), y[:, :D], 1e-6)
     close(y[:, :D], ref, 1e-2, 1e-2, "rmsnorm"); assert (y[:, D:] == 9).all()
 
@@ -661,7 +696,7 @@ def test_gated_gelu(dev):
     M, Fd = 123, 264
     u = rb(torch.randn(M, 2 * Fd + 8, generator=g) * 2.0)
     ref = F.gelu(u[:, :Fd], approximate="tanh") * u[:, Fd:2 * Fd]
-    y = torch.empty(M, Fd, dtype=BF, device=dev)
+    y = poisoned((M, Fd), BF, dev)
     ops.gated_gelu(u.to(dev, BF), y)
     close(y, ref, 1e-2, 1e-2, "gated gelu")
 
@@ -680,7 +715,7 @@ def test_attn_fwd_bias(dev, B, H, S, scale):
     ref = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B, S, d)
     lse_ref = torch.logsumexp(s, -1) * 1.4426950408889634
     dqkv = qkv.to(dev, BF)
-    o = torch.empty(B, S, d, dtype=BF, device=dev); lse = torch.empty(B, H, S, device=dev)
+    o = poisoned((B, S, d), BF, dev); lse = poisoned((B, H, S), torch.float32, dev)
     bias_t = bias.transpose(1, 2).contiguous().to(dev)
     ops.attn_fwd_bias(dqkv[:, :, :d], dqkv[:, :, d:2 * d], dqkv[:, :, 2 * d:], bias_t, o, lse, B, H, S, scale)
     close(o, ref, 2e-2, 2e-2, "attention with bias")
@@ -697,12 +732,13 @@ def test_gemm_splitk_and_residual_cast(dev, M, N, K, splits):
     g = torch.Generator().manual_seed(M + N + K)
     a = rb(torch.randn(M, K + 64, generator=g)); w = rb(torch.randn(N, K, generator=g) * 0.05); r = rb(torch.randn(M, N, generator=g))
     ref = a[:, :K] @ w.T
-    acc = torch.full((M, N), 7.0, device=dev)
+    acc = poisoned((M, N), torch.float32, dev)               # overwritten: the library clears it before the split-K atomics
     ops.gemm_splitk(a.to(dev, BF)[:, :K], w.to(dev, BF), acc, splits)
     close(acc, ref, 2e-3, 2e-3 * ref.abs().max().item(), "split-K accumulate")
-    out = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev)
     ops.residual_cast(acc, r.to(dev, BF), out)
     close(out, ref + r, 1e-2, 1e-2 * ref.abs().max().item(), "residual + cast")
+    out = poisoned((M, N), BF, dev)
     ops.residual_cast(acc, None, out)
     close(out, ref, 1e-2, 1e-2 * ref.abs().max().item(), "cast")
     with pytest.raises(VtError, match="vt_gemm_splitk_f32"):         # splits must divide K / 64
@@ -725,10 +761,10 @@ def test_groupnorm_silu_channels_last(dev, N, P, C, G, silu):
         ref = F.silu(ref)
     ref = ref.transpose(1, 2)
     X = xb.to(dev, BF)
-    y = torch.full((N, P, C + 16), 5.0, dtype=BF, device=dev)
+    y = torch.full((N, P, C + 16), 5.0, dtype=BF, device=dev)      # sentinel: the pad columns are asserted below
     ops.groupnorm_silu(X[:, :, :C], gamma.to(dev, BF), beta.to(dev, BF), y[:, :, :C], G, 1e-6, silu)
     close(y[:, :, :C], ref, 1e-2, 1.5e-2, "groupnorm+silu"); assert (y[:, :, C:] == 5).all()
-    y2 = torch.empty(N, P, C, dtype=BF, device=dev)
+    y2 = poisoned((N, P, C), BF, dev)
     ops.groupnorm_silu(X[:, :, :C], None, None, y2, G, 1e-6, False)
     close(y2, F.group_norm(x.transpose(1, 2).contiguous(), G, None, None, 1e-6).transpose(1, 2), 1e-2, 1.5e-2, "groupnorm, no affine")
 
@@ -747,13 +783,14 @@ def test_causal_conv3d_channels_last(dev, N, T, H, W, Cin, Cout):
     xpad = torch.cat([xin[:, :, :1]] * 2 + [xin], dim=2)
     ref = F.conv3d(xpad, w, b, padding=(0, 1, 1)).permute(0, 2, 3, 4, 1)
     X = xb.to(dev, BF)
-    y = torch.full((N, T, H, W, Cout + 4), 3.0, dtype=BF, device=dev)
+    y = torch.full((N, T, H, W, Cout + 4), 3.0, dtype=BF, device=dev)      # sentinel: the pad channels are asserted below
     ops.causal_conv3d(X[..., :Cin], ops.pack_conv3d_weight(w).to(dev, BF), b.to(dev, BF), y[..., :Cout])
     close(y[..., :Cout], ref, 1e-2, 1e-2 * ref.abs().max().item(), "causal conv3d"); assert (y[..., Cout:] == 3).all()
-    y2 = torch.empty(N, T, H, W, Cout, dtype=BF, device=dev)
+    y2 = poisoned((N, T, H, W, Cout), BF, dev)
     ops.causal_conv3d(X[..., :Cin], ops.pack_conv3d_weight(w).to(dev, BF), None, y2)
     close(y2, ref - b, 1e-2, 1e-2 * ref.abs().max().item(), "causal conv3d, no bias")
     r = rb(torch.randn(N, T, H, W, Cout, generator=g))                      # the ResNet block's skip, added in the epilogue
+    y2 = poisoned((N, T, H, W, Cout), BF, dev)
     ops.causal_conv3d(X[..., :Cin], ops.pack_conv3d_weight(w).to(dev, BF), b.to(dev, BF), y2, residual=r.to(dev, BF))
     close(y2, ref + r, 1e-2, 1e-2 * (ref + r).abs().max().item(), "causal conv3d + residual")
 
@@ -767,7 +804,7 @@ def test_downsample_conv2d_channels_last(dev, N, T, H, W, Cin, Cout):
     w = rb(torch.randn(Cout, Cin, 3, 3, generator=g) * (1.0 / (9 * Cin) ** 0.5)); b = rb(torch.randn(Cout, generator=g))
     xin = x.permute(0, 1, 4, 2, 3).reshape(N * T, Cin, H, W)
     ref = F.conv2d(F.pad(xin, (0, 1, 0, 1)), w, b, stride=2).reshape(N, T, Cout, H // 2, W // 2).permute(0, 1, 3, 4, 2)
-    y = torch.empty(N, T, H // 2, W // 2, Cout, dtype=BF, device=dev)
+    y = poisoned((N, T, H // 2, W // 2, Cout), BF, dev)
     ops.downsample_conv2d(x.to(dev, BF), ops.pack_conv_weight(w).to(dev, BF), b.to(dev, BF), y)
     close(y, ref, 1e-2, 1e-2 * ref.abs().max().item(), "downsample conv2d")
 
@@ -782,7 +819,7 @@ def test_temporal_pool_all_pairs(dev, T):
     xt = x.permute(0, 2, 3, 4, 1).reshape(N * H * W, C, T)
     ref = F.avg_pool1d(xt, kernel_size=2, stride=2)
     ref = ref.reshape(N, H, W, C, T // 2).permute(0, 4, 1, 2, 3)
-    y = torch.empty(N, T // 2, H, W, C, dtype=BF, device=dev)
+    y = poisoned((N, T // 2, H, W, C), BF, dev)
     ops.temporal_pool(x.to(dev, BF), y, keep_first=False)
     close(y, ref, 1e-2, 1e-2, "temporal pool (all pairs)")
 
@@ -803,7 +840,7 @@ def test_temporal_pool(dev, T):
     else:
         ref, To = x, 1
     assert To == 1 + (T - 1) // 2
-    y = torch.empty(N, To, H, W, C, dtype=BF, device=dev)
+    y = poisoned((N, To, H, W, C), BF, dev)
     ops.temporal_pool(x.to(dev, BF), y)
     close(y, ref, 1e-2, 1e-2, "temporal pool")
 
@@ -819,6 +856,6 @@ def test_causal_conv3d_rgb_input(dev, N, T, H, W, Cin, Cout):
     ref = F.conv3d(torch.cat([xin[:, :, :1]] * 2 + [xin], dim=2), w, b, padding=(0, 1, 1)).permute(0, 2, 3, 4, 1)
     x8 = torch.zeros(N, T, H, W, 8, dtype=BF, device=dev)
     x8[..., :Cin] = x.to(dev, BF)
-    y = torch.empty(N, T, H, W, Cout, dtype=BF, device=dev)
+    y = poisoned((N, T, H, W, Cout), BF, dev)
     ops.causal_conv3d_in8(x8, ops.pack_conv_in8_weight(w).to(dev, BF), b.to(dev, BF), y)
     close(y, ref, 1e-2, 1e-2 * ref.abs().max().item(), "first conv (8-channel input)")

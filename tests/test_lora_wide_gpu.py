@@ -7,20 +7,14 @@ assertion is made for it."""
 import pytest
 import torch
 
+from parity import close, rel_l2
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 
 
 def rb(x):      # bf16-round but keep fp32 (what the device kernel actually sees)
     return x.to(BF).float()
-
-
-def close(a, b, rtol, atol, what=""):
-    a = a.detach().float().cpu(); b = b.detach().float().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    bad = (err > tol).float().mean().item()
-    assert bad == 0.0, f"{what}: {bad*100:.4f}% out of tol, max err {err.max().item():.4g}, ref absmax {b.abs().max().item():.4g}"
 
 
 def layout(n, r):
@@ -191,7 +185,7 @@ def test_block_recompute_gives_the_same_gradients_rank32(dev):
     l1, g1 = step("always")
     assert l0 == l1
     assert g0.abs().max().item() > 0
-    rel = (g1 - g0).norm().item() / g0.norm().item()
+    rel = rel_l2(g1, g0)
     assert rel < 1e-3, rel
 
 

@@ -22,6 +22,7 @@ import pytest
 import torch
 
 import cogvideox_oracle as O
+from parity import close, poisoned
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -31,14 +32,6 @@ SENT = 768.0          # sentinel of elements a kernel must not write (exact in b
 
 def rb(x):      # bf16-round but keep fp32 (what the device kernel actually sees)
     return x.to(BF).float()
-
-
-def close(a, b, rtol, atol, what=""):
-    a = a.detach().double().cpu(); b = b.detach().double().cpu()
-    err = (a - b).abs()
-    tol = atol + rtol * b.abs()
-    bad = (~(err <= tol)).float().mean().item()          # a NaN counts as out of tolerance
-    assert bad == 0.0, f"{what}: {bad*100:.4f}% out of tol, max err {err.max().item():.4g}, ref absmax {b.abs().max().item():.4g}"
 
 
 def ints(g, lo, hi, *shape):
@@ -474,8 +467,8 @@ def test_ln_param_chain_vs_autograd(dev):
     scale = torch.where(is_txt, mo[rows_b, 4 * D:5 * D], mo[rows_b, D:2 * D])
     O.ln_modulate(x.double(), ga, be, scale, shift, 1e-5).backward(dy.double())
 
-    X, DY, Y = x.to(dev, BF), dy.to(dev, BF), torch.empty(M, D, dtype=BF, device=dev)
-    mean, rstd = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    X, DY, Y = x.to(dev, BF), dy.to(dev, BF), poisoned((M, D), BF, dev)
+    mean, rstd = poisoned((M,), torch.float32, dev), poisoned((M,), torch.float32, dev)
     modd = mod.to(dev); m = engine._mod(modd, 0, D)
     gd, bd = gam.to(dev, BF), bet.to(dev, BF)
     ops.ln_modulate_fwd(X, Y, gd, bd, (m.shift_txt, m.scale_txt, m.shift_vid, m.scale_vid, m.bs), mean, rstd, D, S, St, 1e-5)
@@ -518,8 +511,8 @@ def test_qk_ln_param_grads(dev, with_rope):
         cos, sin = torch.from_numpy(gold["small_cos"]), torch.from_numpy(gold["small_sin"])     # [60, 64]
         S, St = 100, 40
         rope = (cos.to(dev).contiguous(), sin.to(dev).contiguous(), S, St)
-    Q = qkv.to(dev, BF); qk_hat = torch.empty(M, 2 * D, dtype=BF, device=dev)
-    mean = torch.empty(M, 2 * H, device=dev); rstd = torch.empty(M, 2 * H, device=dev)
+    Q = qkv.to(dev, BF); qk_hat = poisoned((M, 2 * D), BF, dev)
+    mean = poisoned((M, 2 * H), torch.float32, dev); rstd = poisoned((M, 2 * H), torch.float32, dev)
     pd = [t.to(dev, BF) for t in prm]
     ops.qk_layernorm_fwd(Q, qk_hat, pd[0], pd[1], pd[2], pd[3], mean, rstd, H, 1e-6, rope=rope)
     DQ = torch.full((M, D + 8), NAN, device=dev); DQ[:, :D] = dq.to(dev).float()
@@ -575,7 +568,7 @@ def test_diffusion_loss_and_bwd(dev, grad_out):
     n = B * per
     dv_ref = dv_ref * grad_out
     args = (v.to(dev, BF), noisy.to(dev, BF), x0.to(dev), sa.to(dev), sb.to(dev), w.to(dev))
-    loss = torch.zeros(1, device=dev); part = torch.empty(512, device=dev)
+    loss = poisoned((1,), torch.float32, dev); part = poisoned((512,), torch.float32, dev)
     dv1 = torch.full((n + 3,), SENT, dtype=BF, device=dev); dv2 = dv1.clone()
     ops.diffusion_loss(*args, loss, part, dv1[:n].view(B, per), grad_out)
     ops.diffusion_loss_bwd(*args, torch.tensor([grad_out], device=dev), dv2[:n].view(B, per))

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from parity import grad_report, poisoned, rel_l2
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,11 +28,6 @@ def _tiny(dev, cfg=None):
     return SO, cfg, m, Pr
 
 
-def _rel(a, b):
-    a = a.detach().double().cpu(); b = b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
 def test_tiny_stdit_forward_matches_golden_and_oracle(dev):
     SO, cfg, m, Pr = _tiny(dev)
     g = np.load(os.path.join(G, "stdit_tiny.npz"))
@@ -38,7 +35,7 @@ def test_tiny_stdit_forward_matches_golden_and_oracle(dev):
     with torch.no_grad():
         out = m(x.to(dev, BF), t.to(dev), y.to(dev, BF), mask.to(dev))
     ref = SO.stdit_forward(Pr, cfg, x.to(BF).double(), t, y.to(BF).double(), mask)
-    e1, e2 = _rel(out, ref), _rel(out, torch.from_numpy(g["out"]))
+    e1, e2 = rel_l2(out, ref), rel_l2(out, torch.from_numpy(g["out"]))
     print(f"[stdit tiny fwd] rel-L2 vs oracle {e1:.3e}, vs reference golden (fp32 weights) {e2:.3e}")
     assert out.dtype == torch.float32 and e1 < 3e-2 and e2 < 5e-2
 
@@ -59,7 +56,7 @@ def test_tiny_stdit_train_step_matches_oracle(dev):
     t = torch.tensor([0, 250, 999])
     sch = OpenSoraScheduler()
     coef = sch.coef(t.to(dev))
-    x_t = torch.empty(x0.shape, dtype=BF, device=dev)
+    x_t = poisoned(x0.shape, BF, dev)
     ops.q_sample(x0.to(dev), noise.to(dev), coef[:, 0].float().contiguous(), coef[:, 1].float().contiguous(), None, x_t)
     out = m(x_t, t.to(dev), y.to(dev, BF), mask.to(dev))
     loss = _OpenSoraLoss.apply(out, x0.to(dev), noise.to(dev), coef)
@@ -73,17 +70,8 @@ def test_tiny_stdit_train_step_matches_oracle(dev):
     lref.backward()
     print(f"[stdit tiny train] loss dev {loss.item():.5f} oracle {lref.item():.5f} (mse {mse.item():.4f} vb {vb.item():.4f})")
     assert abs(loss.item() - lref.item()) < 2e-2 * abs(lref.item())
-    worst, bad, tn, td = 0.0, [], 0.0, 0.0
-    for n in m.shapes:
-        gd = m._view(ts.grad, n).detach().double().cpu()
-        gr = Pr[n].grad
-        e, d = (gd - gr).norm().item(), gr.norm().item()
-        tn += e * e; td += d * d
-        cos = torch.nn.functional.cosine_similarity(gd.flatten(), gr.flatten(), dim=0).item()
-        if cos < 0.98 or e / max(d, 1e-12) > 0.2:
-            bad.append((n, e / max(d, 1e-12), cos))
-        worst = max(worst, e / max(d, 1e-12))
-    print(f"[stdit tiny train] grads: overall rel-L2 {(tn / td) ** 0.5:.3e}, worst per-parameter {worst:.3e}")
+    overall, worst, bad = grad_report(((n, m._view(ts.grad, n), Pr[n].grad) for n in m.shapes), 0.98, 0.2)
+    print(f"[stdit tiny train] grads: overall rel-L2 {overall:.3e}, worst per-parameter {worst:.3e}")
     assert not bad, bad[:8]
     opt = FusedAdamW(ts.params, lr=1e-3, fullft_state=ts)
     before = ts.flat.clone()
@@ -150,23 +138,13 @@ def test_stdit_xl2_blocks_at_the_recipes_full_size(dev):
     for v in Pr.values():
         v.requires_grad_(True)
     ref = SO.stdit_forward(Pr, cfg, x_t.double(), t, y.double(), mask)
-    e_out = _rel(out, ref)
+    e_out = rel_l2(out, ref)
     osch = SO.schedule(1000)
     lref, _, _ = SO.opensora_loss(ref, x0.double(), noise.double(), t, {k: (v.double() if v.is_floating_point() else v) for k, v in osch.items()})
     lref.backward()
-    tn = td = 0.0
-    worst, bad = 0.0, []
-    for n in m.shapes:
-        gd = m._view(ts.grad, n).detach().double().cpu()
-        gr = Pr[n].grad
-        e, d = (gd - gr).norm().item(), gr.norm().item()
-        tn += e * e; td += d * d
-        cos = torch.nn.functional.cosine_similarity(gd.flatten(), gr.flatten(), dim=0).item()
-        worst = max(worst, e / max(d, 1e-12))
-        if cos < 0.98 or e / max(d, 1e-12) > 0.2:
-            bad.append((n, e / max(d, 1e-12), cos))
+    overall, worst, bad = grad_report(((n, m._view(ts.grad, n), Pr[n].grad) for n in m.shapes), 0.98, 0.2)
     print(f"[stdit XL/2 width, depth 2, 2 x 4096 tokens] out rel-L2 {e_out:.3e}; loss dev {loss.item():.5f} oracle {lref.item():.5f}; "
-          f"grads overall rel-L2 {(tn / td) ** 0.5:.3e}, worst per-parameter {worst:.3e}")
+          f"grads overall rel-L2 {overall:.3e}, worst per-parameter {worst:.3e}")
     assert e_out < 3e-2 and abs(loss.item() - lref.item()) < 2e-2 * abs(lref.item())
     assert not bad, bad[:8]
 
@@ -178,8 +156,8 @@ def test_opensora_loss_kernel_matches_golden(dev):
     g = np.load(os.path.join(G, "stdit_loss.npz"))
     T = lambda k: torch.from_numpy(g[k]).to(dev)
     coef = OpenSoraScheduler().coef(T("t"))
-    loss3 = torch.empty(3, dtype=torch.float64, device=dev)
-    dout = torch.empty(g["model_out"].shape, device=dev)
+    loss3 = poisoned((3,), torch.float64, dev)
+    dout = poisoned(g["model_out"].shape, torch.float32, dev)
     ops.opensora_loss(T("model_out"), T("x0"), T("noise"), coef, loss3, dout)
     l = loss3.cpu()
     assert abs(l[0].item() - float(g["loss"])) < 1e-6 * float(g["loss"])
@@ -211,14 +189,14 @@ def test_stdit_caption_dropout_follows_the_reference_rule(dev):
         out = m(x.to(dev), t.to(dev), y.to(dev), mask.to(dev))
     ref = SO.stdit_forward(Pr, cfg, x.double(), t, y_ref.double(), mask)
     nodrop = SO.stdit_forward(Pr, cfg, x.double(), t, y.double(), mask)
-    e = _rel(out, ref)
-    print(f"[stdit caption dropout] dropped {want.tolist()}; rel-L2 vs oracle with replaced captions {e:.3e}, vs undropped {_rel(out, nodrop):.3e}")
-    assert e < 3e-2 and _rel(out, nodrop) > 10 * e
+    e = rel_l2(out, ref)
+    print(f"[stdit caption dropout] dropped {want.tolist()}; rel-L2 vs oracle with replaced captions {e:.3e}, vs undropped {rel_l2(out, nodrop):.3e}")
+    assert e < 3e-2 and rel_l2(out, nodrop) > 10 * e
     m.eval()
     with torch.no_grad():
         out_f = m(x.to(dev), t.to(dev), y.to(dev), mask.to(dev), force_drop_ids=want.to(torch.int64))
         out_e = m(x.to(dev), t.to(dev), y.to(dev), mask.to(dev))
-    assert torch.equal(out_f, out) and _rel(out_e, nodrop) < 3e-2
+    assert torch.equal(out_f, out) and rel_l2(out_e, nodrop) < 3e-2
 
 
 def test_whole_stdit_xl2_full_size_backward_predicts_its_own_forward(dev):

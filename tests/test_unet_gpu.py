@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import golden_io
+from parity import grad_report, poisoned, rel_l2
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -32,9 +33,9 @@ def _tiny(dev, seed=11, cfg=None):
     return U, cfg, m, Pr
 
 
-def _relerr(a, b):
-    a = a.detach().double().cpu(); b = b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+def _model_grads(m, ts, Pr, names=None):
+    """(overall rel-L2, worst per-parameter rel-L2, parameters not above cosine 0.98 and below rel-L2 0.2); every gradient finite"""
+    return grad_report(((n, m._view(ts.grad, n), Pr[n].grad) for n in (names or m.shapes)), 0.98, 0.2)
 
 
 def test_tiny_unet_forward_matches_golden_and_oracle(dev):
@@ -46,7 +47,7 @@ def test_tiny_unet_forward_matches_golden_and_oracle(dev):
     with torch.no_grad():
         out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
     ref = U.unet_forward(Pr, cfg, x.to(BF).double(), t, ctx.to(BF).double(), fps=fps)
-    e_or, e_gold = _relerr(out, ref), _relerr(out, torch.from_numpy(g["out"]))
+    e_or, e_gold = rel_l2(out, ref), rel_l2(out, torch.from_numpy(g["out"]))
     print(f"[unet tiny fwd] rel-L2 vs oracle {e_or:.3e}, vs reference golden (fp32 weights) {e_gold:.3e}")
     assert e_or < 3e-2 and e_gold < 5e-2
 
@@ -61,7 +62,7 @@ def test_tiny_unet_train_step_matches_oracle(dev):
     x = torch.from_numpy(g["x"]); ctx = torch.from_numpy(g["context"]); t = torch.from_numpy(g["t"]); fps = torch.from_numpy(g["fps"])
     noise = torch.from_numpy(g["noise"])
     out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
-    loss = torch.empty(1, device=dev); dp = torch.empty(out.shape, dtype=BF, device=dev)
+    loss = poisoned((1,), torch.float32, dev); dp = poisoned(out.shape, BF, dev)
     ops.mse_loss(out.detach().contiguous(), noise.to(dev), loss, dp)
     out.backward(dp)
     for v in Pr.values():
@@ -70,19 +71,7 @@ def test_tiny_unet_train_step_matches_oracle(dev):
     lref = U.lvdm_loss(ref, noise.double())
     lref.backward()
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
-    worst, bad = 0.0, []
-    tot_n = tot_d = 0.0
-    for n in m.shapes:
-        gd = m._view(ts.grad, n).detach().double().cpu()
-        gr = Pr[n].grad
-        e = (gd - gr).norm().item(); d = gr.norm().item()
-        tot_n += e * e; tot_d += d * d
-        rel = e / max(d, 1e-12)
-        cos = torch.nn.functional.cosine_similarity(gd.flatten(), gr.flatten(), dim=0).item()
-        if cos < 0.98 or rel > 0.2:
-            bad.append((n, rel, cos))
-        worst = max(worst, rel)
-    overall = (tot_n / tot_d) ** 0.5
+    overall, worst, bad = _model_grads(m, ts, Pr)
     print(f"[unet tiny train] loss dev {loss.item():.6f} oracle {lref.item():.6f}; grads: overall rel-L2 {overall:.3e}, worst per-parameter {worst:.3e}")
     assert not bad, bad[:10]
     assert overall < 5e-2
@@ -91,21 +80,6 @@ def test_tiny_unet_train_step_matches_oracle(dev):
     opt.step()
     assert torch.isfinite(ts.flat).all() and (ts.flat - before).abs().max().item() > 0
     assert torch.equal(ts.flat_bf16.float(), ts.flat.to(BF).float())
-
-
-def _grad_report(m, ts, Pr, names=None):
-    worst, bad, tot_n, tot_d = 0.0, [], 0.0, 0.0
-    for n in (names or m.shapes):
-        gd = m._view(ts.grad, n).detach().double().cpu()
-        gr = Pr[n].grad
-        e = (gd - gr).norm().item(); d = gr.norm().item()
-        tot_n += e * e; tot_d += d * d
-        rel = e / max(d, 1e-12)
-        cos = torch.nn.functional.cosine_similarity(gd.flatten(), gr.flatten(), dim=0).item()
-        if cos < 0.98 or rel > 0.2:
-            bad.append((n, rel, cos))
-        worst = max(worst, rel)
-    return (tot_n / max(tot_d, 1e-300)) ** 0.5, worst, bad
 
 
 def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
@@ -124,7 +98,7 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
     noise = torch.from_numpy(g["noise"])
     B, _, T, H, W = x.shape
     out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
-    loss = torch.empty(1, device=dev); dp = torch.empty(out.shape, dtype=BF, device=dev)
+    loss = poisoned((1,), torch.float32, dev); dp = poisoned(out.shape, BF, dev)
     ops.mse_loss(out.detach().contiguous(), noise.to(dev), loss, dp)
     out.backward(dp)
     sites = m.last_dropout_sites
@@ -144,8 +118,8 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
         leval = U.lvdm_loss(U.unet_forward(Pr, cfg, x.to(BF).double(), t, ctx.to(BF).double(), fps=fps), noise.double())
     assert abs(lref.item() - leval.item()) > 1e-4 * leval.item()                   # the masks change the result ...
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
-    e_out = _relerr(out, ref)
-    overall, worst, bad = _grad_report(m, ts, Pr)
+    e_out = rel_l2(out, ref)
+    overall, worst, bad = _model_grads(m, ts, Pr)
     print(f"[unet tiny train-mode dropout] loss dev {loss.item():.6f} oracle {lref.item():.6f} (eval {leval.item():.6f}); out rel-L2 {e_out:.3e}; "
           f"grads overall {overall:.3e}, worst {worst:.3e}")
     assert e_out < 3e-2 and not bad and overall < 5e-2, bad[:8]
@@ -155,7 +129,7 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
         pass
     m.eval()
     out_e = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
-    assert m.last_dropout_sites == [] and _relerr(out_e, out) > 1e-3
+    assert m.last_dropout_sites == [] and rel_l2(out_e, out) > 1e-3
 
 
 def test_tiny_unet_lora_train_step_matches_oracle(dev):
@@ -178,27 +152,16 @@ def test_tiny_unet_lora_train_step_matches_oracle(dev):
     x = torch.from_numpy(g["net.x"]); ctx = torch.from_numpy(g["net.context"]); t = torch.from_numpy(g["net.t"]); fps = torch.from_numpy(g["net.fps"])
     noise = torch.from_numpy(g["net.noise"])
     out = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
-    loss = torch.empty(1, device=dev); dp = torch.empty(out.shape, dtype=BF, device=dev)
+    loss = poisoned((1,), torch.float32, dev); dp = poisoned(out.shape, BF, dev)
     ops.mse_loss(out.detach().contiguous(), noise.to(dev), loss, dp)
     out.backward(dp)
     ref = U.unet_forward({**Pr, **Lr}, cfg, x.to(BF).double(), t, ctx.to(BF).double(), fps=fps)
     lref = U.lvdm_loss(ref, noise.double())
     lref.backward()
-    e_out, e_gold = _relerr(out, ref), _relerr(out, torch.from_numpy(g["lora.out"]))
+    e_out, e_gold = rel_l2(out, ref), rel_l2(out, torch.from_numpy(g["lora.out"]))
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
     lo = m.lora
-    tot_n = tot_d = 0.0; worst = 0.0; bad = []
-    for n in lo.shapes:
-        gd = lo._view(ts.grad, n).detach().double().cpu()
-        gr = Lr[n].grad
-        e = (gd - gr).norm().item(); d = gr.norm().item()
-        tot_n += e * e; tot_d += d * d
-        rel = e / max(d, 1e-12)
-        cos = torch.nn.functional.cosine_similarity(gd.flatten(), gr.flatten(), dim=0).item()
-        if cos < 0.98 or rel > 0.2:
-            bad.append((n, rel, cos))
-        worst = max(worst, rel)
-    overall = (tot_n / tot_d) ** 0.5
+    overall, worst, bad = grad_report(((n, lo._view(ts.grad, n), Lr[n].grad) for n in lo.shapes), 0.98, 0.2)
     print(f"[unet tiny LoRA] out rel-L2 vs oracle {e_out:.3e}, vs reference golden {e_gold:.3e}; loss dev {loss.item():.6f} oracle {lref.item():.6f}; "
           f"adapter grads overall {overall:.3e}, worst {worst:.3e} over {len(lo.shapes)} tensors")
     assert e_out < 3e-2 and e_gold < 5e-2 and not bad and overall < 5e-2, bad[:8]
@@ -211,7 +174,7 @@ def test_tiny_unet_lora_train_step_matches_oracle(dev):
     # the packed operands follow the optimizer step: a second forward differs
     with torch.no_grad():
         out2 = m(x.to(dev, BF), t.to(dev), context=ctx.to(dev, BF), fps=fps.to(dev))
-    assert _relerr(out2, out) > 1e-5
+    assert rel_l2(out2, out) > 1e-5
 
 
 # ------------------------------------------------------------------------------------------------ each block alone
@@ -285,22 +248,18 @@ def _block_case(dev, kind, full=False):
     ref5 = ref5 if kind in ("tt", "init_tt") else ref4.reshape(B, T, cout, ref4.shape[2], ref4.shape[3]).permute(0, 2, 1, 3, 4)
     gy = torch.randn(ref5.shape, generator=g).to(BF).float()
     (ref5 * gy.to(dt_)).sum().backward()
-    e_out = _relerr(yv.d, _cl(ref5))
+    e_out = rel_l2(yv.d, _cl(ref5))
     yv.g = _cl(gy).to(dev, BF).contiguous()
     while run.tape:
         run.tape.pop()()
-    e_dx = _relerr(xv.g, _cl(xr.grad))
-    worst = 0.0
+    e_dx = rel_l2(xv.g, _cl(xr.grad))
     names = [n for n in m.shapes if n.startswith(layer.pre + ".")]
-    for n in names:
-        gd = m._view(ts.grad, n).detach().double().cpu()
-        rel = (gd - Pr[n].grad).norm().item() / max(Pr[n].grad.norm().item(), 1e-12)
-        worst = max(worst, rel)
+    worst = max(rel_l2(m._view(ts.grad, n), Pr[n].grad) for n in names)              # rel_l2 refuses a non-finite gradient
     print(f"[unet block {kind}{' FULL SIZE ' + str([B, T, H, W, cin]) if full else ''}] out rel-L2 {e_out:.3e}, dx {e_dx:.3e}, worst parameter gradient {worst:.3e} over {len(names)} tensors")
     assert e_out < 2e-2 and e_dx < 4e-2 and worst < 6e-2
     if kind in ("res", "res_same"):
         dse = er.grad.view(B, T, -1).sum(1)
-        assert _relerr(demb, dse) < 4e-2
+        assert rel_l2(demb, dse) < 4e-2
 
 
 @pytest.mark.parametrize("kind", ["res", "res_same", "st", "tt", "init_tt"])

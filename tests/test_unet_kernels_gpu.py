@@ -6,20 +6,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from parity import close, poisoned, poisoned_like, untouched, all_written
+
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 
 
 def rb(t):
     return t.to(BF).float()
-
-
-def close(got, ref, rtol, atol, what):
-    got = got.detach().float().cpu()
-    ref = ref.detach().float()
-    err = (got - ref).abs()
-    lim = atol + rtol * ref.abs()
-    assert bool((err <= lim).all()), f"{what}: max err {err.max().item():.3e} (ref max {ref.abs().max().item():.3e}) at {int((err - lim).argmax())}"
 
 
 # ------------------------------------------------------------------------------------------------ convolutions
@@ -67,12 +61,12 @@ def test_conv_cl_forward_input_grad_weight_grad(dev, N, T, H, W, Cin, Cout, kern
     # ---- forward (+ bias, per-sample bias, residual), input slice of a wider buffer ----
     xb = torch.zeros(N, T, H, W, Cin + 64, dtype=BF, device=dev)
     xb[..., :Cin] = x.to(dev, BF)
-    y = torch.empty(N, T, Ho, Wo, Cout, dtype=BF, device=dev)
+    y = poisoned((N, T, Ho, Wo, Cout), BF, dev)
     ops.conv_cl(xb[..., :Cin], ops.pack_conv_weight_nd(w).to(dev, BF), y, kernel, padding, stride, bias=b.to(dev, BF), sbias=sb.to(dev),
                 residual=res.to(dev, BF))
     close(y, ref.detach() + res, 2e-2, 2e-2 * ref.abs().max().item(), "conv forward")
     # ---- weight gradient ----
-    dw = torch.zeros(Cout, KT * KH * KW * Cin, device=dev)
+    dw = poisoned((Cout, KT * KH * KW * Cin), torch.float32, dev)           # accumulate=False writes it whole; the second call adds to it
     dyd = torch.zeros(N, T, Ho, Wo, (Cout + 7) // 8 * 8, dtype=BF, device=dev)[..., :Cout]       # rows are 16-byte multiples
     dyd.copy_(dy.to(dev, BF))
     db = torch.full((Cout,), 0.5, device=dev)                  # the bias gradient rides along (+=): column sums of dy
@@ -88,11 +82,11 @@ def test_conv_cl_forward_input_grad_weight_grad(dev, N, T, H, W, Cin, Cout, kern
     if Cout % 64:
         return
     wdx = ops.pack_conv_weight_dx(w if w.dim() == 5 else w[:, :, None]).to(dev, BF)
-    dx = torch.empty(N, T, H, W, Cin, dtype=BF, device=dev)
+    dx = poisoned((N, T, H, W, Cin), BF, dev)
     if stride == 1:
         ops.conv_cl(dy.to(dev, BF), wdx, dx, kernel, padding, 1)
     else:
-        z = torch.empty(N, T, H, W, Cout, dtype=BF, device=dev)
+        z = poisoned((N, T, H, W, Cout), BF, dev)
         ops.row_map(dy.to(dev, BF).view(-1, Cout), z.view(-1, Cout), 2, N * T, Ho, Wo)
         ops.conv_cl(z, wdx, dx, kernel, padding, 1)
     close(dx, xr.grad, 2e-2, 2e-2 * xr.grad.abs().max().item(), "conv input gradient")
@@ -129,9 +123,9 @@ def test_conv_320_wide_kernel_at_a_chip_filling_size(dev):
     for mode in (1, 0):
         ops.conv_set_tile(mode)
         try:
-            y = torch.empty(N, T, H, W, C, dtype=BF, device=dev)
+            y = poisoned((N, T, H, W, C), BF, dev)
             ops.conv_cl(x, wk, y, (1, 3, 3), (0, 1, 1), 1, bias=b, sbias=sb, residual=res)
-            dw = torch.zeros(C, 9 * C, device=dev)
+            dw = poisoned((C, 9 * C), torch.float32, dev)
             ops.conv_dw_cl(dy, x, dw, (1, 3, 3), (0, 1, 1), 1, accumulate=False)
             out[mode] = (y.float(), dw.clone())
         finally:
@@ -189,15 +183,15 @@ def test_conv_on_trailing_column_slices_stays_inside_the_allocation(dev, N, T, H
     xr = x.clone().requires_grad_(True); wr = w.clone().requires_grad_(True)
     ref = _conv_ref(xr, wr, None, kernel, padding, 1)
     (ref * dy).sum().backward()
-    y = torch.empty(N, T, Ho, Wo, Cout, dtype=BF, device=dev)
+    y = poisoned((N, T, Ho, Wo, Cout), BF, dev)
     ops.conv_cl(xs, ops.pack_conv_weight_nd(w).to(dev, BF), y, kernel, padding, 1)
     close(y, ref.detach(), 2e-2, 2e-2 * ref.abs().max().item(), "conv forward on a trailing slice")
-    dw = torch.zeros(Cout, KT * KH * KW * Cin, device=dev)
+    dw = poisoned((Cout, KT * KH * KW * Cin), torch.float32, dev)
     ops.conv_dw_cl(dys, xs, dw, kernel, padding, 1, accumulate=False)
     dwr = ops.pack_conv_weight_nd(wr.grad)
     close(dw, dwr, 2e-2, 2e-2 * dwr.abs().max().item(), "conv weight gradient, dy and x trailing slices")
     wdx = ops.pack_conv_weight_dx(w if w.dim() == 5 else w[:, :, None]).to(dev, BF)
-    dx = torch.empty(N, T, H, W, Cin, dtype=BF, device=dev)
+    dx = poisoned((N, T, H, W, Cin), BF, dev)
     ops.conv_cl(dys, wdx, dx, kernel, padding, 1)
     close(dx, xr.grad, 2e-2, 2e-2 * xr.grad.abs().max().item(), "conv input gradient from a trailing dy slice")
     torch.cuda.synchronize()
@@ -209,7 +203,7 @@ def test_linear_dw_any_size(dev, M, P, Q):
     g = torch.Generator().manual_seed(M + P)
     dy = rb(torch.randn(M, P, generator=g)); x = rb(torch.randn(M, Q, generator=g))
     ref = dy.double().t() @ x.double()
-    dw = torch.full((P, Q), 7.0, device=dev)
+    dw = poisoned((P, Q), torch.float32, dev)
     ops.linear_dw(dy.to(dev, BF), x.to(dev, BF), dw, accumulate=False)
     close(dw, ref, 1e-2, 1e-2 * ref.abs().max().item(), "linear dW")
 
@@ -223,23 +217,23 @@ def test_weight_gradients_over_rows_spanning_more_than_2_gib(dev):
     g = torch.Generator().manual_seed(11)
     dy = rb(torch.randn(M, P, generator=g)); x = rb(torch.randn(M, Q, generator=g))
     ref = dy.double().t() @ x.double()
-    wide = torch.empty(M, W, dtype=BF, device=dev)
+    wide = poisoned((M, W), BF, dev)             # input staging: only the two column slices filled below may be read
     assert M * W * 2 > 2 ** 31 + 2 ** 30
     wide[:, :P] = dy.to(dev, BF); wide[:, 1024:1024 + Q] = x.to(dev, BF)
     dyw, xw = wide[:, :P], wide[:, 1024:1024 + Q]
     tol = 1e-2 * ref.abs().max().item()
-    dw = torch.full((P, Q), 7.0, device=dev); db = torch.zeros(P, device=dev)
+    dw = poisoned((P, Q), torch.float32, dev); db = torch.zeros(P, device=dev)       # db is in/out: the bias gradient accumulates
     ops.linear_dw(dyw, xw, dw, accumulate=False, dbias=db)
     close(dw, ref, 1e-2, tol, "chunked linear dW")
     close(db, dy.double().sum(0), 1e-2, 1e-2 * M ** 0.5, "chunked bias gradient")
     ops.linear_dw(dyw, xw, dw, accumulate=True)
     close(dw, 2 * ref, 1e-2, 2 * tol, "chunked linear dW, accumulated")
-    c = torch.full((P, Q), 7.0, device=dev)
+    c = poisoned((P, Q), torch.float32, dev)
     ops.gemm_nt(dyw, xw, c, accumulate=False)
     close(c, ref, 1e-2, tol, "chunked gemm_nt")
     ops.gemm_nt(dyw, xw, c, alpha=0.5, accumulate=True)
     close(c, 1.5 * ref, 1e-2, 2 * tol, "chunked gemm_nt, accumulated")
-    c2 = torch.empty(P, Q, device=dev)
+    c2 = poisoned((P, Q), torch.float32, dev)
     ops.gemm_nt(dy.to(dev, BF), x.to(dev, BF), c2, accumulate=False)
     close(c2, ref, 1e-2, tol, "compact gemm_nt")
     torch.cuda.synchronize()
@@ -257,15 +251,16 @@ def test_dropout_mask_is_philox_and_backward_reuses_it(dev, M, C, ld, p, seed, o
     x = rb(torch.randn(M, C, generator=g))
     xb = torch.zeros(M, ld, dtype=BF, device=dev)[:, :C]
     xb.copy_(x.to(dev, BF))
-    y = torch.empty(M, C, dtype=BF, device=dev)
-    mask = torch.empty(M, C, dtype=torch.uint8, device=dev)
+    y = poisoned((M, C), BF, dev)
+    mask = poisoned((M, C), torch.uint8, dev)
     ops.dropout(xb, y, p, seed, off, mask_out=mask)
     want = torch.from_numpy(philox.dropout_keep_mask(M, C, p, seed, off))
+    all_written(mask, "dropout keep mask")
     assert torch.equal(mask.cpu(), want)
     ref = (x * want.float() / (1.0 - p)).to(BF).float()
     assert torch.equal(y.float().cpu(), ref)
     dy = rb(torch.randn(M, C, generator=g))
-    dx = torch.empty(M, C, dtype=BF, device=dev)
+    dx = poisoned((M, C), BF, dev)
     ops.dropout(dy.to(dev, BF), dx, p, seed, off)
     assert torch.equal(dx.float().cpu(), (dy * want.float() / (1.0 - p)).to(BF).float())
     assert abs(want.float().mean().item() - (1 - p)) < 0.02
@@ -284,11 +279,11 @@ def test_groupnorm_forward_backward(dev, N, P, C, silu, eps):
     if silu:
         y = F.silu(y)
     (y * dy.double()).sum().backward()
-    xd = x.to(dev, BF); yd = torch.empty_like(xd)
+    xd = x.to(dev, BF); yd = poisoned_like(xd)
     ws = ops.groupnorm_fwd(xd, ga.to(dev, BF), be.to(dev, BF), yd, 32, eps, silu)
     close(yd, y, 2e-2, 2e-2, "groupnorm forward")
-    dx = torch.empty_like(xd)
-    dga = torch.zeros(C, device=dev); dbe = torch.zeros(C, device=dev)
+    dx = poisoned_like(xd)
+    dga = torch.zeros(C, device=dev); dbe = torch.zeros(C, device=dev)          # in/out: the parameter gradients accumulate
     ops.groupnorm_bwd(dy.to(dev, BF), xd, ga.to(dev, BF), ws, dx, dga, dbe, 32, silu)
     close(dx, xr.grad, 3e-2, 2e-2 * xr.grad.abs().max().item(), "groupnorm dx")
     close(dga, gr.grad, 2e-2, 2e-2 * gr.grad.abs().max().item(), "groupnorm dgamma")
@@ -309,10 +304,10 @@ def test_geglu_forward_backward(dev):
     a, gate = hr.chunk(2, dim=-1)
     y = a * F.gelu(gate)
     (y * dy.double()).sum().backward()
-    yd = torch.empty(M, Fd, dtype=BF, device=dev)
+    yd = poisoned((M, Fd), BF, dev)
     ops.geglu_fwd(h.to(dev, BF), yd)
     close(yd, y, 1e-2, 1e-2, "geglu")
-    dh = torch.empty(M, 2 * Fd, dtype=BF, device=dev)
+    dh = poisoned((M, 2 * Fd), BF, dev)
     ops.geglu_bwd(dy.to(dev, BF), h.to(dev, BF), dh)
     close(dh, hr.grad, 1e-2, 2e-2, "geglu backward")
 
@@ -323,39 +318,40 @@ def test_row_maps_add_and_loss(dev):
     B, T, HW, C = 2, 4, 6, 64
     x = rb(torch.randn(B, T, HW, C, generator=g))
     xd = x.to(dev, BF).view(-1, C)
-    out = torch.empty(B * HW * T, C, dtype=BF, device=dev)
+    out = poisoned((B * HW * T, C), BF, dev)
     ops.row_map(xd, out, 0, B, T, HW)
     assert torch.equal(out.float().cpu().view(B, HW, T, C), x.permute(0, 2, 1, 3))
-    back = torch.empty_like(xd)
+    back = poisoned_like(xd)
     ops.row_map(out, back, 0, B, HW, T)
     assert torch.equal(back, xd)
     N, H, W = 3, 2, 3
     s = rb(torch.randn(N, H, W, C, generator=g))
-    up = torch.empty(N * 4 * H * W, C, dtype=BF, device=dev)
+    up = poisoned((N * 4 * H * W, C), BF, dev)
     ops.row_map(s.to(dev, BF).view(-1, C), up, 1, N, H, W)
     ref = s.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
     assert torch.equal(up.float().cpu().view(N, 2 * H, 2 * W, C), ref)
+    up = poisoned((N * 4 * H * W, C), BF, dev)      # fresh: mode 1 left the same values at the even positions
     ops.row_map(s.to(dev, BF).view(-1, C), up, 2, N, H, W)
     z = torch.zeros(N, 2 * H, 2 * W, C); z[:, ::2, ::2] = s
     assert torch.equal(up.float().cpu().view(N, 2 * H, 2 * W, C), z)
     big = rb(torch.randn(N, 2 * H, 2 * W, C, generator=g))
-    dn = torch.empty(N * H * W, C, dtype=BF, device=dev)
+    dn = poisoned((N * H * W, C), BF, dev)
     ops.row_map(big.to(dev, BF).view(-1, C), dn, 3, N, H, W)
     close(dn.view(N, H, W, C), big.view(N, H, 2, W, 2, C).sum(dim=(2, 4)), 1e-2, 1e-2, "2x2 block sum")
     ops.row_map(big.to(dev, BF).view(-1, C), dn, 3, N, H, W, accumulate=True)
     close(dn.view(N, H, W, C), 2 * big.view(N, H, 2, W, 2, C).sum(dim=(2, 4)), 1e-2, 2e-2, "2x2 block sum (accumulate)")
     a = rb(torch.randn(10, C, generator=g)); b = rb(torch.randn(10, C, generator=g))
-    o = torch.empty(10, C, dtype=BF, device=dev)
+    o = poisoned((10, C), BF, dev)
     ops.add_rows(a.to(dev, BF), b.to(dev, BF), o)
     close(o, a + b, 1e-2, 1e-2, "add rows")
     # q_sample + eps-MSE loss
     x0 = torch.randn(2, 4, 4, 8, 8, generator=g); nz = torch.randn(x0.shape, generator=g)
     sa = torch.tensor([0.9, 0.3]); sb = torch.tensor([0.4, 0.95]); sc = torch.tensor([1.0, 0.7])
-    xt = torch.empty(x0.shape, dtype=BF, device=dev)
+    xt = poisoned(x0.shape, BF, dev)
     ops.q_sample(x0.to(dev), nz.to(dev), sa.to(dev), sb.to(dev), sc.to(dev), xt)
     close(xt, (sa * sc).view(2, 1, 1, 1, 1) * x0 + sb.view(2, 1, 1, 1, 1) * nz, 1e-2, 1e-2, "q_sample")
     pred = rb(torch.randn(x0.shape, generator=g))
-    loss = torch.empty(1, device=dev); dp = torch.empty(x0.shape, dtype=BF, device=dev)
+    loss = poisoned((1,), torch.float32, dev); dp = poisoned(x0.shape, BF, dev)
     ops.mse_loss(pred.to(dev, BF), nz.to(dev), loss, dp, grad_scale=0.5)
     ref = ((pred - nz) ** 2).mean(dim=(1, 2, 3, 4)).mean()
     assert abs(loss.item() - ref.item()) < 1e-4 * ref.item()
@@ -373,9 +369,19 @@ def _attn_ref(q, k, v, scale, mask_block=0):
     return torch.einsum("bhij,bhjd->bhid", s.softmax(-1), v)
 
 
-@pytest.mark.parametrize("NB,H,Sq,Sk", [(2, 2, 300, 77), (1, 5, 1500, 77), (3, 1, 40, 20), (1, 2, 130, 128)])
+def _zero_ref_scale(r, dv_ref):
+    """the absolute tolerance of a gradient scales with max |reference|.  With ONE key per query the softmax is the constant 1 and the
+    references of dq and dk are identically zero, while the device's dS = p (dO . v - dO . o) keeps the bf16 rounding of o: an error
+    relative to |dO| |v|, which is the scale of dv = p^T dO -- so a gradient whose own reference is zero is held to max |dv_ref|"""
+    return r.abs().max().item() or dv_ref.abs().max().item()
+
+
+@pytest.mark.parametrize("NB,H,Sq,Sk", [(2, 2, 300, 77), (1, 5, 1500, 77), (3, 1, 40, 20), (1, 2, 130, 128),
+                                        (2, 2, 130, 33), (1, 1, 129, 64), (1, 2, 1025, 96), (1, 1, 1, 1)])
 def test_attn_small_cross(dev, NB, H, Sq, Sk):
-    """text cross-attention (CrossAttention.forward, lvdm/modules/attention.py:101-181): every query of a sample against its <= 128 keys"""
+    """text cross-attention (CrossAttention.forward, lvdm/modules/attention.py:101-181): every query of a sample against its <= 128 keys.
+    One, two (33 and 64 keys), three and four 32-key tiles; 1025 queries cross the backward's 1024-query chunk with a one-row tail; a
+    single query against a single key.  o, lse and dq are written whole, dk / dv are fp32 accumulators the binding zeroes"""
     from vt355 import ops
     g = torch.Generator().manual_seed(Sq + Sk)
     D = H * 64
@@ -387,19 +393,47 @@ def test_attn_small_cross(dev, NB, H, Sq, Sk):
     (ref * sp(do)).sum().backward()
     mg = lambda t: t.permute(0, 2, 1, 3).reshape(t.shape[0], t.shape[2], D)
     qd, kvd = q.to(dev, BF), kv.to(dev, BF)
-    o = torch.empty(NB, Sq, D, dtype=BF, device=dev); lse = torch.empty(NB, H, Sq, device=dev)
+    o = poisoned((NB, Sq, D), BF, dev); lse = poisoned((NB, H, Sq), torch.float32, dev)
     ops.attn_small_fwd(qd, kvd[..., :D], kvd[..., D:], o, lse, H, 0.125)
     close(o, mg(ref), 2e-2, 1e-2, "cross-attention output")
-    dq = torch.empty(NB, Sq, D, dtype=BF, device=dev)
-    dk = torch.empty(NB, Sk, D, device=dev); dv = torch.empty(NB, Sk, D, device=dev)
+    dq = poisoned((NB, Sq, D), BF, dev)
+    dk = poisoned((NB, Sk, D), torch.float32, dev); dv = poisoned((NB, Sk, D), torch.float32, dev)
     ops.attn_small_bwd(qd, kvd[..., :D], kvd[..., D:], o, do.to(dev, BF), lse, dq, dk, dv, H, 0.125)
     for got, r, nm in ((dq, qr.grad, "dq"), (dk, kr.grad, "dk"), (dv, vr.grad, "dv")):
-        close(got, mg(r), 3e-2, 2e-2 * r.abs().max().item(), "cross-attention " + nm)
+        close(got, mg(r), 3e-2, 2e-2 * _zero_ref_scale(r, vr.grad), "cross-attention " + nm)
+    lref = torch.logsumexp(torch.einsum("bhid,bhjd->bhij", qr, kr).detach() * 0.125, -1) * 1.4426950408889634
+    close(lse, lref, 1e-3, 2e-2, "cross-attention lse2")
 
 
-@pytest.mark.parametrize("R,T,H", [(256, 16, 2), (80, 16, 1), (40960, 16, 5), (72, 4, 8), (33 * 8, 8, 1)])
+def test_attn_small_refuses_more_than_128_keys_and_odd_sequence_lengths(dev):
+    """129 keys do not fit the resident key set; a packed sequence length must divide the 32-row tile (T = 3 does not): both are refused
+    on the host, forward and backward, and the library writes nothing (the binding zeroes the cross form's fp32 dk / dv accumulators before
+    it calls the library: those come back as zeros)"""
+    from vt355 import ops
+    from vt355._lib import VtError
+    D = 64
+    for Sq, Sk, T in ((40, 129, 0), (96, 96, 3)):
+        NB = 1
+        q = torch.zeros(NB, Sq, D, dtype=BF, device=dev); kv = torch.zeros(NB, Sk, 2 * D, dtype=BF, device=dev)
+        o = poisoned((NB, Sq, D), BF, dev); lse = poisoned((NB, 1, Sq), torch.float32, dev)
+        dq = poisoned((NB, Sq, D), BF, dev)
+        dk, dv = (poisoned((NB, Sk, D), BF, dev) for _ in range(2)) if T else (poisoned((NB, Sk, D), torch.float32, dev) for _ in range(2))
+        with pytest.raises(VtError, match="vt_attn_small_fwd"):
+            ops.attn_small_fwd(q, kv[..., :D], kv[..., D:], o, lse, 1, 0.125, mask_block=T)
+        with pytest.raises(VtError, match="vt_attn_small_bwd"):
+            ops.attn_small_bwd(q, kv[..., :D], kv[..., D:], q, q, torch.zeros_like(lse), dq, dk, dv, 1, 0.125, mask_block=T)
+        untouched(o, [], "refused attn_small_fwd: o"); untouched(lse, [], "refused attn_small_fwd: lse"); untouched(dq, [], "refused attn_small_bwd: dq")
+        if T:                                # bf16 dk / dv belong to the kernel alone: nothing is written
+            untouched(dk, [], "refused attn_small_bwd: dk"); untouched(dv, [], "refused attn_small_bwd: dv")
+        else:                                # the fp32 accumulators are zeroed by the binding before the library refuses: zeros, and nothing added
+            assert bool((dk == 0).all()) and bool((dv == 0).all()), "refused attn_small_bwd: dk / dv accumulators"
+
+
+@pytest.mark.parametrize("R,T,H", [(256, 16, 2), (80, 16, 1), (40960, 16, 5), (72, 4, 8), (33 * 8, 8, 1), (160, 32, 2), (130, 2, 1), (97, 1, 2)])
 def test_attn_small_packed_sequences(dev, R, T, H):
-    """temporal self-attention (TemporalTransformer, attention.py:395-519): R / T consecutive sequences of T rows, fused qkv"""
+    """temporal self-attention (TemporalTransformer, attention.py:395-519): R / T consecutive sequences of T rows, fused qkv.  Every divisor
+    of the 32-row tile is a legal T: 32 (a 128-row item plus a 32-row tail), 16, 8, 4, 2 (a two-row tail item) and 1.  At T = 1 the one
+    unmasked probability is exp2(0) = 1, so by the kernel's own arithmetic o == v and dv == dO bit for bit"""
     from vt355 import ops
     g = torch.Generator().manual_seed(R + T)
     D = H * 64
@@ -407,9 +441,9 @@ def test_attn_small_packed_sequences(dev, R, T, H):
     qkv = rb(torch.randn(R, 3 * D, generator=g))
     do = rb(torch.randn(R, D, generator=g))
     d = qkv.to(dev, BF).view(1, R, 3 * D)
-    o = torch.empty(1, R, D, dtype=BF, device=dev); lse = torch.empty(1, H, R, device=dev)
+    o = poisoned((1, R, D), BF, dev); lse = poisoned((1, H, R), torch.float32, dev)
     ops.attn_small_fwd(d[..., :D], d[..., D:2 * D], d[..., 2 * D:], o, lse, H, 0.125, mask_block=T)
-    dqkv = torch.empty(1, R, 3 * D, dtype=BF, device=dev)
+    dqkv = poisoned((1, R, 3 * D), BF, dev)
     ops.attn_small_bwd(d[..., :D], d[..., D:2 * D], d[..., 2 * D:], o, do.to(dev, BF).view(1, R, D), lse,
                        dqkv[..., :D], dqkv[..., D:2 * D], dqkv[..., 2 * D:], H, 0.125, mask_block=T)
     rows = slice(R - 2048, R) if big else slice(0, R)          # the full first-level size: check the last 128 sequences
@@ -419,11 +453,22 @@ def test_attn_small_packed_sequences(dev, R, T, H):
     (ref * do[rows].double().view(n, T, H, 64).permute(0, 2, 1, 3)).sum().backward()
     close(o[0, rows], ref.permute(0, 2, 1, 3).reshape(n * T, D), 2e-2, 1e-2, "temporal attention output")
     gref = x.grad.permute(1, 3, 0, 2, 4).reshape(n * T, 3 * D)
-    close(dqkv[0, rows], gref, 3e-2, 2e-2 * gref.abs().max().item(), "temporal attention dqkv")
+    if T == 1:
+        assert torch.equal(o[0], d[0, :, 2 * D:]), "T = 1: o must equal v bit for bit"
+        assert torch.equal(dqkv[0, :, 2 * D:], do.to(dev, BF)), "T = 1: dv must equal dO bit for bit"
+        assert gref[:, :2 * D].abs().max().item() == 0.0                # the references of dq and dk are identically zero: _zero_ref_scale
+        close(dqkv[0, :, :2 * D], gref[:, :2 * D], 3e-2, 2e-2 * gref[:, 2 * D:].abs().max().item(), "temporal attention dq | dk at T = 1")
+    else:
+        close(dqkv[0, rows], gref, 3e-2, 2e-2 * gref.abs().max().item(), "temporal attention dqkv")
+    if big:                                                             # written whole: the rows not compared above are at least finite
+        assert bool(torch.isfinite(o.float()).all()) and bool(torch.isfinite(dqkv.float()).all()) and bool(torch.isfinite(lse).all())
 
 
 # ------------------------------------------------------------------------------------------------ generic-head-dim attention
 def _gen_case(dev, NB, H, Sq, Sk, hd, hstride, kv_len=None, mask_block=0, seed=0, bf16_out=False):
+    """every output is poisoned first.  Written whole: the head_dim (80 | 128) columns of every head of o and dq, lse, dk / dv in the packed
+    and the bf16 forms (the fp32 dk / dv accumulators are zeroed by the binding and summed into).  Never written: the columns between
+    head_dim and hstride of every head.  bf16 dk / dv rows at and past a sample's kv_len come back exactly 0."""
     from vt355 import ops
     g = torch.Generator().manual_seed(seed + Sq + Sk + hd)
     hp = 80 if hd == 72 else 128
@@ -446,21 +491,31 @@ def _gen_case(dev, NB, H, Sq, Sk, hd, hstride, kv_len=None, mask_block=0, seed=0
     D = H * hstride
     fl = lambda t: t.reshape(NB, -1, D).to(dev, BF)
     qd, kd, vd, dod = fl(q), fl(k), fl(v), fl(do)
-    o = torch.zeros(NB, Sq, D, dtype=BF, device=dev); lse = torch.empty(NB, H, Sq, device=dev)
+    o = poisoned((NB, Sq, D), BF, dev); lse = poisoned((NB, H, Sq), torch.float32, dev)
     kl = None if kv_len is None else torch.tensor(kv_len, dtype=torch.int32, device=dev)
     ops.attn_gen_fwd(qd, kd, vd, o, lse, H, hp, hstride, scale, kv_len=kl, mask_block=mask_block)
     un = lambda t: t.view(NB, -1, H, hstride)[..., :hd].permute(0, 2, 1, 3)
     close(un(o), ref, 2e-2, 1e-2, "attention output")
-    dq = torch.zeros(NB, Sq, D, dtype=BF, device=dev)
-    if mask_block:
-        dk = torch.zeros(NB, Sk, D, dtype=BF, device=dev); dv = torch.zeros(NB, Sk, D, dtype=BF, device=dev)
-    elif bf16_out:        # written whole by the key-stationary pass: poison first
-        dk = torch.full((NB, Sk, D), float("nan"), dtype=BF, device=dev); dv = torch.full((NB, Sk, D), float("nan"), dtype=BF, device=dev)
-    else:
-        dk = torch.empty(NB, Sk, D, device=dev); dv = torch.empty(NB, Sk, D, device=dev)
+    stored = lambda t: (slice(None), slice(None), slice(None), slice(0, hp))        # of the [NB, S, H, hstride] view
+    untouched(o.view(NB, Sq, H, hstride), stored(o), "attention output: columns past head_dim")
+    assert bool(torch.isfinite(o.float().view(NB, Sq, H, hstride)[..., :hp]).all()), "attention output: pad columns of the stored head"
+    lse_ref = torch.logsumexp(s.detach(), -1) * 1.4426950408889634
+    close(lse, lse_ref, 1e-3, 2e-2, "attention lse2")
+    dq = poisoned((NB, Sq, D), BF, dev)
+    out_dt = BF if (mask_block or bf16_out) else torch.float32
+    dk = poisoned((NB, Sk, D), out_dt, dev); dv = poisoned((NB, Sk, D), out_dt, dev)
     ops.attn_gen_bwd(qd, kd, vd, o, dod, lse, dq, dk, dv, H, hp, hstride, scale, kv_len=kl, mask_block=mask_block)
     for got, r, nm in ((dq, qr.grad, "dq"), (dk, kr.grad, "dk"), (dv, vr.grad, "dv")):
-        close(un(got), r, 3e-2, 2e-2 * r.abs().max().item(), "attention " + nm)
+        close(un(got), r, 3e-2, 2e-2 * _zero_ref_scale(r, vr.grad), "attention " + nm)
+    untouched(dq.view(NB, Sq, H, hstride), stored(dq), "attention dq: columns past head_dim")
+    if out_dt == BF:
+        untouched(dk.view(NB, Sk, H, hstride), stored(dk), "attention dk: columns past head_dim")
+        untouched(dv.view(NB, Sk, H, hstride), stored(dv), "attention dv: columns past head_dim")
+        if kv_len is not None:
+            for b, n in enumerate(kv_len):
+                for t, nm in ((dk, "dk"), (dv, "dv")):
+                    pad = t.view(NB, Sk, H, hstride)[b, n:, :, :hp]
+                    assert bool((pad == 0).all()), f"attention {nm}: rows of sample {b} at and past kv_len = {n} must be exactly 0"
 
 
 @pytest.mark.parametrize("NB,H,Sq,Sk", [(3, 2, 256, 256), (2, 3, 100, 77), (1, 16, 64, 64)])
@@ -498,6 +553,39 @@ def test_attn_gen_hd128(dev, NB, H, Sq, Sk):
     _gen_case(dev, NB, H, Sq, Sk, 128, 128)
 
 
+def test_attn_gen_hd128_packed(dev):
+    """head_dim 128 with mask_block: 160 rows = ten 16-row sequences, a 128-row item plus a 32-row tail"""
+    _gen_case(dev, 1, 2, 160, 160, 128, 128, mask_block=16)
+
+
+def test_attn_gen_hd128_varlen(dev):
+    """head_dim 128 with kv_len (fp32 dk / dv accumulators): all 47 keys, and a single key"""
+    _gen_case(dev, 2, 1, 130, 47, 128, 128, kv_len=[47, 1])
+
+
+@pytest.mark.parametrize("hd", [72, 128])
+def test_attn_gen_bf16_dk_dv_varlen_padded_keys_get_zeros(dev, hd):
+    """bf16 dK / dV written whole TOGETHER with kv_len: the poisoned rows at and past a sample's valid length come back exactly 0"""
+    _gen_case(dev, 3, 2, 100, 77, hd, 80 if hd == 72 else 128, kv_len=[20, 77, 1], bf16_out=True)
+
+
+@pytest.mark.parametrize("bf16_out", [False, True], ids=["fp32_dkdv", "bf16_dkdv"])
+@pytest.mark.parametrize("NB,H,Sq,Sk", [(1, 1, 1, 1), (2, 2, 1, 77), (2, 2, 100, 1)])
+@pytest.mark.parametrize("hd", [72, 128])
+def test_attn_gen_one_query_one_key(dev, hd, NB, H, Sq, Sk, bf16_out):
+    """a single query, a single key, and both: one lane of one tile is live"""
+    _gen_case(dev, NB, H, Sq, Sk, hd, 80 if hd == 72 else 128, bf16_out=bf16_out)
+
+
+@pytest.mark.parametrize("hd,hstride", [(72, 88), (128, 136)])
+def test_attn_gen_heads_stored_wider_than_head_dim(dev, hd, hstride):
+    """heads hstride > head_dim apart: the 8 columns between two heads belong to nobody and keep their poison (the kernels store 16-byte
+    vectors per lane; a stray one lands exactly there)"""
+    _gen_case(dev, 2, 2, 100, 77, hd, hstride)
+    _gen_case(dev, 2, 2, 100, 77, hd, hstride, bf16_out=True)
+    _gen_case(dev, 1, 2, 96, 96, hd, hstride, mask_block=16)
+
+
 # ------------------------------------------------------------------------------------------------ operand packing
 @pytest.mark.parametrize("R,C,ld", [(320, 1024, 1024), (72, 40, 48), (640, 640, 640), (8, 8, 8), (1280, 200, 256)])
 def test_transpose_matches_torch(dev, R, C, ld):
@@ -522,18 +610,18 @@ def test_transpose_plan_runs_many_transposes_in_one_launch(dev):
     for R, C, ld in [(320, 320, 320), (1280, 320, 320), (8, 8, 8), (2560, 640, 640), (72, 200, 208), (1000, 136, 512)]:
         buf = rb(torch.randn(R, ld, generator=g)).to(dev, BF)
         src = buf[:, :C]
-        dst = torch.full((C, R), 7.0, dtype=BF, device=dev)
+        dst = torch.full((C, R), 7.0, dtype=BF, device=dev)      # sentinel, not poison: every element must be overwritten by the plan (compared bit for bit below)
         assert plan.add(src, dst)
         lin.append((buf, src, dst))
     for Cout, Cin, kernel in [(320, 64, (3, 3)), (64, 320, (3, 1, 1))]:
         w = rb(torch.randn(Cout, Cin, *kernel, generator=g)).to(dev, BF)
         taps = math.prod(kernel)
         ws = ops.pack_conv_weight_nd(w).view(Cout, taps, Cin).contiguous()
-        dst = torch.full((Cin, taps * Cout), 7.0, dtype=BF, device=dev)
+        dst = torch.full((Cin, taps * Cout), 7.0, dtype=BF, device=dev)      # sentinel, not poison: every element must be overwritten by the plan (compared bit for bit below)
         assert plan.add_conv_dx(ws, dst)
         conv.append((ws, dst))
     odd = rb(torch.randn(12, 16, generator=g)).to(dev, BF)
-    assert not plan.add(odd, torch.empty(16, 12, dtype=BF, device=dev))                  # 12 rows: not a multiple of 8
+    assert not plan.add(odd, poisoned((16, 12), BF, dev))                  # 12 rows: not a multiple of 8
     for rnd in range(2):
         plan.run()
         for buf, src, dst in lin:
@@ -575,7 +663,7 @@ def test_gemm_fp8_matches_dequantized_reference(dev, M, N, K):
     aq_ref = (a / sa_ref).to(torch.float8_e4m3fn); wq_ref = (w / sw_ref).to(torch.float8_e4m3fn)
     assert (aq.cpu().view(torch.uint8) != aq_ref.view(torch.uint8)).float().mean().item() < 1e-3       # rounding ties aside
     ref = (aq.cpu().float() * sa.item()) @ (wq.cpu().float() * sw.item()).T + b
-    out = torch.empty(M, N, dtype=BF, device=dev)
+    out = poisoned((M, N), BF, dev)
     ops.gemm_fp8(aq, wq, out, sa, sw, b.to(dev, BF))
     close(out, ref, 1e-2, 1e-2 * ref.abs().max().item(), "fp8 GEMM")
     # and against the unquantised product: the quantisation error of E4M3 (3 mantissa bits) on both operands
