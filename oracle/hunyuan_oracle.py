@@ -63,8 +63,9 @@ def rotate_half(x):
 
 
 def rope(x, cos, sin):
-    """x [B, L, H, D]; cos / sin [L, D]"""
-    return x * cos[None, :, None] + rotate_half(x) * sin[None, :, None]
+    """x [B, L, H, D]; cos / sin [L, D].  The rotation runs in the tables' precision (fp32 tables under a bf16 activation, as
+    apply_rotary_emb does) and the result keeps the activation's dtype"""
+    return (x * cos[None, :, None] + rotate_half(x) * sin[None, :, None]).to(x.dtype)
 
 
 def varlen_attention(q, k, v, valid_len):

@@ -276,18 +276,22 @@ def rs_forward(P, c, x):
 RS_FLOW = dict(RS_TINY, num_queries=IMG_TOKENS)          # 16 queries per frame x 4 frames: the tiny UNet's per-frame image context
 
 
-def dc_flow_loss(Pu, cfg, Pr, rcfg, z, context, image_tokens, t, noise, fs, cond_frame_index, alphas_cumprod, scale_arr, round_bf16=True):
+def dc_flow_loss(Pu, cfg, Pr, rcfg, z, context, image_tokens, t, noise, fs, cond_frame_index, alphas_cumprod, scale_arr, round_bf16=True,
+                 model_dtype=None):
     """LatentVisualDiffusionFlow's deterministic core (ddpm3d.py:1311-1480 get_batch_input + :787-848 p_losses, parameterization v, use_scale,
-    conditioning_key hybrid): Resampler -> [text | image] context; input = [q_sample(z * scale_t) | cond-frame latent repeated over time]"""
-    rb = (lambda v: v.to(torch.bfloat16).to(z.dtype)) if round_bf16 else (lambda v: v)          # the device hands these to the UNet in bf16
-    ctx = torch.cat([context, rb(rs_forward(Pr, rcfg, image_tokens))], dim=1)
+    conditioning_key hybrid): Resampler -> [text | image] context; input = [q_sample(z * scale_t) | cond-frame latent repeated over time].
+    model_dtype: the dtype the two networks run in (default: z's); the schedule arithmetic, the target and the loss stay in z's dtype, as the
+    device keeps them in fp32 around its bf16 networks"""
+    md = model_dtype or z.dtype
+    rb = (lambda v: v.to(torch.bfloat16).to(md)) if round_bf16 else (lambda v: v.to(md))          # the device hands these to the UNet in bf16
+    ctx = torch.cat([context.to(md), rb(rs_forward(Pr, rcfg, image_tokens.to(md)))], dim=1)
     T = z.shape[2]
     cond = z[:, :, cond_frame_index:cond_frame_index + 1].expand(-1, -1, T, -1, -1)
     x0 = z * scale_arr[t].view(-1, 1, 1, 1, 1).to(z.dtype)
     sa = alphas_cumprod[t].sqrt().float().to(z.dtype).view(-1, 1, 1, 1, 1)
     sb = (1 - alphas_cumprod[t]).sqrt().float().to(z.dtype).view(-1, 1, 1, 1, 1)
     x_in = torch.cat([rb(sa * x0 + sb * noise), rb(cond)], dim=1)
-    out = dc_unet_forward(Pu, cfg, x_in, t, ctx, fs=fs)
+    out = dc_unet_forward(Pu, cfg, x_in, t, ctx, fs=fs).to(z.dtype)
     target = sa * noise - sb * x0
     return ((out - target) ** 2).mean(dim=(1, 2, 3, 4)).mean()
 

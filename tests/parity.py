@@ -80,12 +80,17 @@ def cosine(got, ref):
 def grad_report(pairs, cos_min, rel_max):
     """pairs: (name, device gradient, reference gradient).  Returns (overall rel-L2, worst per-parameter rel-L2, bad) where bad lists
     (name, rel, cos) of every parameter that is not `cos > cos_min and rel < rel_max`; a NaN figure is bad and makes worst NaN.
+    rel_max: one float for every parameter, or a mapping name -> bar (see `floor_bars`); a name the mapping does not hold is an error.
     Every device gradient must be finite: the first that is not fails the report by name."""
     worst, bad, tot_n, tot_d = 0.0, [], 0.0, 0.0
     n_pairs = 0
+    per_name = not isinstance(rel_max, (int, float))
     for name, gd, gr in pairs:
         n_pairs += 1
         assert gd is not None, f"{name}: no device gradient"
+        if per_name and name not in rel_max:
+            raise KeyError(f"{name}: no rel-L2 bar for this parameter (a parameter without a bar is not a pass)")
+        bar = rel_max[name] if per_name else rel_max
         gd = gd.detach().double().cpu().flatten()
         gr = _ref64(gr, f"{name}: reference gradient").flatten()
         assert gd.shape == gr.shape, f"{name}: gradient of {gd.numel()} elements against the reference's {gr.numel()}"
@@ -94,12 +99,97 @@ def grad_report(pairs, cos_min, rel_max):
         tot_n += e * e; tot_d += d * d
         rel = e / max(d, 1e-12)
         cos = torch.nn.functional.cosine_similarity(gd, gr, dim=0).item()      # each norm clamped at 1e-8 on its own: tiny gradients keep their angle
-        if not (cos > cos_min and rel < rel_max):
+        if not (cos > cos_min and rel < bar):
             bad.append((name, rel, cos))
         worst = float("nan") if math.isnan(rel) or math.isnan(worst) else max(worst, rel)
     assert n_pairs > 0, "grad_report: no gradients to compare"
     overall = math.sqrt(tot_n) / max(math.sqrt(tot_d), 1e-30)
     return overall, worst, bad
+
+
+# ------------------------------------------------------------------ bars from the reference's own bf16 noise floor
+# The fp64 oracle restated in bf16 on the CPU (same bf16-rounded weights, inputs, masks and upstream gradient; every op rounds its result
+# to bf16) is one sample of the rounding noise a correct bf16 implementation carries.  The device keeps fp32 accumulators and rounds at
+# stores only, so its own sample is expected to be the smaller one; MARGIN covers the parameter-to-parameter scatter between two draws.
+MARGIN = 1.5
+EXCEPTION_MARGIN_MAX = 3.0          # a parameter behind a rounding point only the device has (stated with its cause where it is used)
+EXCEPTION_SHARE_MAX = 0.01          # at most this share of a model's parameters
+
+
+def _median(values):
+    v = sorted(values)
+    assert v, "median of nothing"
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def grad_floor(noisy, ref):
+    """noisy, ref: {name: gradient} of the bf16 and of the fp64 restatement of the same model.  Returns ({name: rel-L2}, overall rel-L2
+    over all parameters).  Both must hold the same names; a non-finite entry on either side raises ValueError (a bug of the test)."""
+    if set(noisy) != set(ref):
+        raise KeyError(f"grad_floor: the two runs hold different parameters: {sorted(set(noisy) ^ set(ref))[:6]}")
+    assert ref, "grad_floor: no gradients"
+    floor, tot_n, tot_d = {}, 0.0, 0.0
+    for name, r in ref.items():
+        if noisy[name] is None or r is None:
+            raise ValueError(f"{name}: a restatement left no gradient (a bug of the test)")
+        a = _ref64(noisy[name], f"{name}: bf16 restatement").flatten()
+        b = _ref64(r, f"{name}: fp64 restatement").flatten()
+        if a.shape != b.shape:
+            raise ValueError(f"{name}: {a.numel()} elements in the bf16 restatement, {b.numel()} in the fp64 one")
+        e = (a - b).norm().item(); d = b.norm().item()
+        tot_n += e * e; tot_d += d * d
+        floor[name] = e / max(d, 1e-12)
+    return floor, math.sqrt(tot_n) / max(math.sqrt(tot_d), 1e-30)
+
+
+def _clamped(floor):
+    med = _median(floor.values())
+    return {n: max(f, med) for n, f in floor.items()}
+
+
+def floor_bars(floor, rel_max, margin=MARGIN, exceptions=None):
+    """{name: min(rel_max, margin * max(floor[name], median floor))}: the old flat bar stays as the cap, and a parameter whose bf16 draw
+    happened to land unusually close to fp64 is held to the model's median, a bar an independent noise sample can meet.
+    exceptions: {name: (margin, cause)} for a parameter behind a rounding point that only the device has -- margin at most 3, at most 1 %
+    of the model's parameters, a cause in words, and still never above rel_max."""
+    assert floor and rel_max > 0 and margin > 0
+    exceptions = exceptions or {}
+    assert set(exceptions) <= set(floor), f"exceptions for parameters the model does not have: {sorted(set(exceptions) - set(floor))}"
+    assert len(exceptions) <= EXCEPTION_SHARE_MAX * len(floor), f"{len(exceptions)} exceptions for {len(floor)} parameters"
+    for n, (mg, cause) in exceptions.items():
+        assert margin <= mg <= EXCEPTION_MARGIN_MAX and str(cause).strip(), f"{n}: exception margin {mg} / cause {cause!r}"
+    return {n: min(rel_max, (exceptions[n][0] if n in exceptions else margin) * f) for n, f in _clamped(floor).items()}
+
+
+def overall_bar(rel_max, overall_floor, margin=MARGIN):
+    """the bar of the overall rel-L2: the old one, or margin x the bf16 restatement's own overall figure where that is lower"""
+    return min(rel_max, margin * overall_floor)
+
+
+def floor_ratio(pairs, floor):
+    """(worst rel-L2 / clamped floor over the parameters, the parameter that has it): what a test prints next to its other figures"""
+    cl, worst, at = _clamped(floor), -1.0, None
+    for name, gd, gr in pairs:
+        r = rel_l2(gd, gr) / max(cl[name], 1e-30)
+        if at is None or not (r <= worst):
+            worst, at = r, name
+    assert at is not None, "floor_ratio: no gradients"
+    return worst, at
+
+
+def floor_report(pairs, noisy, cos_min, rel_max, exceptions=None):
+    """grad_report with floor-derived bars.  pairs: a list of (name, device gradient, fp64 reference gradient); noisy: {name: gradient of the
+    same step restated in bf16 on the CPU}; rel_max: the old flat bar, kept as the cap.  Returns (overall rel-L2, overall bf16 floor, worst
+    per-parameter rel-L2, bad, worst device / floor ratio, the parameter that has it)"""
+    pairs = list(pairs)
+    floor, ofloor = grad_floor({n: noisy[n] for n, _, _ in pairs}, {n: r for n, _, r in pairs})
+    overall, worst, bad = grad_report(pairs, cos_min, floor_bars(floor, rel_max, exceptions=exceptions))
+    return (overall, ofloor, worst, bad) + floor_ratio(pairs, floor)
+
+
+def bf16_leaves(params):
+    """{name: a bf16 leaf that requires grad} of the tensors in params (other entries, such as a LoRA scaling float, pass through)"""
+    return {k: (v.detach().to(torch.bfloat16).requires_grad_(True) if isinstance(v, torch.Tensor) else v) for k, v in params.items()}
 
 
 # ------------------------------------------------------------------ poisoned outputs

@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 import cogvideox_oracle as O
-from parity import grad_report, poisoned, poisoned_like, relerr
+from parity import bf16_leaves, floor_report, poisoned, poisoned_like, relerr
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -253,14 +253,24 @@ def test_one_full_size_block_full_finetune_all_parameter_grads(dev):
     zero_grad = [n for n in ft.names if n.endswith("norm_k.bias")]     # exact gradient is 0 (softmax is shift-invariant): only its size is checked
     for name in zero_grad:
         assert ft.g(name).cpu().float().norm() < 0.05 * ft.g(name.replace("bias", "weight")).norm().item() + 1e-6, name
-    overall, worst, bad = grad_report(((n, ft.g(n), Pref[n].grad) for n in ft.names if n not in zero_grad), 0.99, 0.15)
+    # the oracle once more in bf16 (it costs less than the fp32 run above): its own distance from fp32 per parameter sets the bars.  Over 17 776
+    # rows a bf16 reduction loses most of a norm parameter's gradient -- there the floor is far above the old flat bar, and the old bar holds
+    Pb = bf16_leaves(Pref)
+    out_b = O.dit_forward(Pb, cfg, nref.to(BF), text, t)
+    assert out_b.dtype == BF
+    pred_b = O.get_velocity(out_b.float(), nref, t, abar)
+    torch.mean(((1 / (1 - abar[t])).view(-1, 1, 1, 1, 1) * (pred_b - x0) ** 2).reshape(1, -1), dim=1).mean().backward()
+    checked = [n for n in ft.names if n not in zero_grad]
+    overall, ofloor, worst, bad, ratio, at = floor_report([(n, ft.g(n), Pref[n].grad) for n in checked], {n: Pb[n].grad for n in checked}, 0.99, 0.15)
     gd = ft.grad.cpu().float()
     gr = torch.cat([Pref[n].grad.reshape(-1) for n in ft.names])
     tot = F.cosine_similarity(gd, gr, dim=0).item()
     print(f"[full-size block 2b FULL-FT] loss dev {loss.item():.6f} oracle {loss_ref.item():.6f} rel {lrel:.2e}; whole gradient cos {tot:.5f}; "
-          f"parameter gradients overall rel-L2 {overall:.3e}, worst {worst:.3e}; {len(ft.names)} tensors")
+          f"parameter gradients overall rel-L2 {overall:.3e} (bf16 floor {ofloor:.3e}), worst {worst:.3e}, worst device / floor {ratio:.2f} at {at}; "
+          f"{len(ft.names)} tensors")
     assert lrel < 1e-3 and tot > 0.999                          # observed 6.2e-5 (r02)
     assert not bad, bad[:12]
+    assert overall < 1.5 * ofloor, (overall, ofloor)
 
 
 def test_t5_xxl_layer_fullsize(dev):

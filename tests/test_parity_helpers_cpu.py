@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import parity
-from parity import all_written, close, grad_report, is_poison, poisoned, poisoned_like, rel_l2, relerr, untouched
+from parity import all_written, close, floor_bars, floor_report, grad_floor, grad_report, is_poison, overall_bar, poisoned, poisoned_like, rel_l2, relerr, untouched
 
 BF = torch.bfloat16
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -197,6 +197,79 @@ def test_the_old_gradient_loop_accepted_nan():
     assert old_grad_loop([(n, m[n].double(), ref[n]) for n in ref], COS_MIN, GREL_MAX)[1]    # it did see finite errors
 
 
+# ------------------------------------------------------------------ bars from the bf16 noise floor
+def test_grad_report_takes_a_bar_per_parameter_and_a_missing_name_is_an_error():
+    ref, got = _grads()
+    pairs = [(n, got[n], ref[n]) for n in ref]
+    bars = {n: GREL_MAX for n in ref}
+    assert grad_report(pairs, COS_MIN, bars) == grad_report(pairs, COS_MIN, GREL_MAX)              # a float keeps its behaviour
+    m = dict(got); m["a.weight"] = got["a.weight"] * 1.03; m["b.weight"] = got["b.weight"] * 1.03
+    bars["a.weight"] = 0.02
+    _, _, bad = grad_report([(n, m[n], ref[n]) for n in ref], COS_MIN, bars)
+    assert [b[0] for b in bad] == ["a.weight"]                    # 3 % off: over its own 2 % bar, b.weight under the flat 15 %
+    del bars["norm.weight"]
+    with pytest.raises(KeyError, match=r"norm\.weight: no rel-L2 bar"):
+        grad_report(pairs, COS_MIN, bars)
+    with pytest.raises(KeyError):
+        grad_report(pairs, COS_MIN, {})
+
+
+def test_grad_floor_measures_the_bf16_restatement_and_refuses_non_finite_entries():
+    ref, got = _grads()
+    floor, overall = grad_floor(got, ref)
+    assert set(floor) == set(ref) and all(0 < f < 2.0 ** -8 for f in floor.values())
+    assert floor["a.bias"] == pytest.approx(rel_l2(got["a.bias"], ref["a.bias"]))
+    tot = sum((got[n].double() - ref[n]).pow(2).sum() for n in ref).sqrt() / sum(ref[n].pow(2).sum() for n in ref).sqrt()
+    assert overall == pytest.approx(tot.item())
+    for side in ("noisy", "ref"):
+        for val in (float("nan"), float("inf")):
+            a, b = dict(got), dict(ref)
+            d = a if side == "noisy" else b
+            t = d["b.weight"].clone(); t[3, 3] = val; d["b.weight"] = t
+            with pytest.raises(ValueError, match=r"b\.weight"):
+                grad_floor(a, b)
+    with pytest.raises(KeyError):
+        grad_floor({n: got[n] for n in list(got)[:-1]}, ref)
+    m = dict(got); m["a.bias"] = None
+    with pytest.raises(ValueError, match=r"a\.bias"):
+        grad_floor(m, ref)
+
+
+def test_floor_bars_cap_at_the_old_bar_clamp_at_the_median_and_limit_exceptions():
+    floor = {"lucky": 1e-4, "low": 0.01, "mid": 0.02, "high": 0.04, "noisy": 0.3}
+    bars = floor_bars(floor, 0.2)
+    assert parity.MARGIN == 1.5
+    assert bars == {"lucky": pytest.approx(0.03), "low": pytest.approx(0.03), "mid": pytest.approx(0.03), "high": pytest.approx(0.06), "noisy": 0.2}
+    assert all(b <= 0.2 for b in floor_bars(floor, 0.2, margin=100.0).values())           # whatever the margin, no bar above the old one
+    assert overall_bar(5e-2, 0.02) == pytest.approx(0.03) and overall_bar(5e-2, 0.2) == 5e-2
+    # an exception: a cause in words, a margin of at most 3, at most 1 % of the parameters, never above the old bar
+    many = {f"p{i}": 0.02 for i in range(200)}
+    ex = floor_bars(many, 0.2, exceptions={"p7": (3.0, "fp32-atomic dQ hand-off the restatement does not have")})
+    assert ex["p7"] == pytest.approx(0.06) and ex["p8"] == pytest.approx(0.03)
+    assert floor_bars(many, 0.05, exceptions={"p7": (3.0, "cause")})["p7"] == 0.05
+    for bad in ({"p7": (3.5, "cause")}, {"p7": (2.0, " ")}, {"nope": (2.0, "cause")}, {f"p{i}": (2.0, "cause") for i in range(3)}):
+        with pytest.raises(AssertionError):
+            floor_bars(many, 0.2, exceptions=bad)
+    with pytest.raises(AssertionError):
+        floor_bars(floor, 0.2, exceptions={"high": (2.0, "one of five parameters is more than 1 %")})
+
+
+def test_floor_report_flags_what_the_flat_bar_let_through():
+    """a gradient 5 % off passes the flat 15 % bar and fails a bar derived from a 0.2 % floor; the report names the worst ratio"""
+    ref, got = _grads()
+    m = {n: g.double() for n, g in got.items()}
+    m["b.weight"] = ref["b.weight"] * 1.05
+    pairs = [(n, m[n], ref[n]) for n in ref]
+    assert not grad_report(pairs, COS_MIN, GREL_MAX)[2]
+    overall, ofloor, worst, bad, ratio, at = floor_report(pairs, got, COS_MIN, GREL_MAX)
+    assert [b[0] for b in bad] == ["b.weight"] and at == "b.weight" and worst == pytest.approx(0.05)
+    assert 0 < ofloor < 2.0 ** -8 and ratio > 10
+    o2, f2, w2, bad2, r2, _ = floor_report([(n, got[n], ref[n]) for n in ref], got, COS_MIN, GREL_MAX)          # the restatement against its own floor
+    assert not bad2 and o2 == pytest.approx(f2) and r2 <= 1.0 + 1e-12
+    with pytest.raises(KeyError):
+        floor_report(pairs, {n: got[n] for n in list(got)[:2]}, COS_MIN, GREL_MAX)
+
+
 # ------------------------------------------------------------------ poisoned / untouched
 DTYPES = [torch.float32, torch.bfloat16, torch.float16, torch.float64, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64,
           torch.float8_e4m3fn, torch.float8_e5m2]
@@ -266,7 +339,9 @@ def test_all_written_allows_the_sentinel_byte_where_the_expected_result_holds_it
 
 # ------------------------------------------------------------------ the GPU test sources
 GPU_SOURCES = sorted(glob.glob(os.path.join(HERE, "*_gpu.py"))) + [os.path.join(HERE, "grad_clip_common.py")]
-FORBIDDEN_DEFS = {"close", "_rel", "_relerr", "relerr", "_grad_report", "_check_param_grads"}
+FORBIDDEN_DEFS = {"close", "_rel", "_relerr", "relerr", "_grad_report", "_check_param_grads",
+                  # the floor-derived bars have one home too: a GPU test builds no bars, floors or margins of its own
+                  "grad_report", "grad_floor", "floor_bars", "floor_report", "_floor_report", "floor_ratio", "overall_bar", "MARGIN"}
 EMPTY = re.compile(r"\b(new_)?empty(_like|_strided)?\s*\(")
 # every torch.empty / empty_like left in a GPU test: (file, the stripped line, why it is not a kernel output).  A buffer that a kernel
 # writes whole does not belong here: it is allocated with parity.poisoned.

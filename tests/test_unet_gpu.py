@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import golden_io
-from parity import grad_report, poisoned, rel_l2
+from parity import bf16_leaves, floor_report, overall_bar, poisoned, rel_l2
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -33,9 +33,14 @@ def _tiny(dev, seed=11, cfg=None):
     return U, cfg, m, Pr
 
 
-def _model_grads(m, ts, Pr, names=None):
-    """(overall rel-L2, worst per-parameter rel-L2, parameters not above cosine 0.98 and below rel-L2 0.2); every gradient finite"""
-    return grad_report(((n, m._view(ts.grad, n), Pr[n].grad) for n in (names or m.shapes)), 0.98, 0.2)
+def _bf16_grads(U, cfg, Pr, x, t, ctx, fps, noise, masks=None, lora=None):
+    """the oracle's train step once more on the CPU in bf16 -- the same rounded weights, inputs, masks and target, every op rounding to bf16,
+    the loss accumulated in fp32 from the bf16 output as on the device: {name: gradient} of the base weights and of the adapters in `lora`"""
+    Pb = bf16_leaves({**Pr, **(lora or {})})
+    out = U.unet_forward(Pb, cfg, x.to(BF), t, ctx.to(BF), fps=fps, dropout_masks=masks)
+    assert out.dtype == BF
+    U.lvdm_loss(out.float(), noise.float()).backward()
+    return {n: v.grad for n, v in Pb.items() if isinstance(v, torch.Tensor)}
 
 
 def test_tiny_unet_forward_matches_golden_and_oracle(dev):
@@ -71,10 +76,12 @@ def test_tiny_unet_train_step_matches_oracle(dev):
     lref = U.lvdm_loss(ref, noise.double())
     lref.backward()
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
-    overall, worst, bad = _model_grads(m, ts, Pr)
-    print(f"[unet tiny train] loss dev {loss.item():.6f} oracle {lref.item():.6f}; grads: overall rel-L2 {overall:.3e}, worst per-parameter {worst:.3e}")
+    overall, ofloor, worst, bad, ratio, at = floor_report([(n, m._view(ts.grad, n), Pr[n].grad) for n in m.shapes],
+                                                          _bf16_grads(U, cfg, Pr, x, t, ctx, fps, noise), 0.98, 0.2)
+    print(f"[unet tiny train] loss dev {loss.item():.6f} oracle {lref.item():.6f}; grads: overall rel-L2 {overall:.3e} (bf16 floor {ofloor:.3e}), "
+          f"worst per-parameter {worst:.3e}, worst device / floor {ratio:.2f} at {at}")
     assert not bad, bad[:10]
-    assert overall < 5e-2
+    assert overall < overall_bar(5e-2, ofloor)
     opt = FusedAdamW(ts.params, lr=1e-3, fullft_state=ts)
     before = ts.flat.clone()
     opt.step()
@@ -119,10 +126,11 @@ def test_tiny_unet_train_mode_dropout_matches_oracle(dev):
     assert abs(lref.item() - leval.item()) > 1e-4 * leval.item()                   # the masks change the result ...
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
     e_out = rel_l2(out, ref)
-    overall, worst, bad = _model_grads(m, ts, Pr)
+    overall, ofloor, worst, bad, ratio, at = floor_report([(n, m._view(ts.grad, n), Pr[n].grad) for n in m.shapes],
+                                                          _bf16_grads(U, cfg, Pr, x, t, ctx, fps, noise, masks=masks), 0.98, 0.2)
     print(f"[unet tiny train-mode dropout] loss dev {loss.item():.6f} oracle {lref.item():.6f} (eval {leval.item():.6f}); out rel-L2 {e_out:.3e}; "
-          f"grads overall {overall:.3e}, worst {worst:.3e}")
-    assert e_out < 3e-2 and not bad and overall < 5e-2, bad[:8]
+          f"grads overall {overall:.3e} (bf16 floor {ofloor:.3e}), worst {worst:.3e}, worst device / floor {ratio:.2f} at {at}")
+    assert e_out < 3e-2 and not bad and overall < overall_bar(5e-2, ofloor), bad[:8]
     # a different seed draws different masks; eval mode draws none
     m.dropout_seed = 5
     with torch.no_grad():
@@ -161,10 +169,12 @@ def test_tiny_unet_lora_train_step_matches_oracle(dev):
     e_out, e_gold = rel_l2(out, ref), rel_l2(out, torch.from_numpy(g["lora.out"]))
     assert abs(loss.item() - lref.item()) < 2e-2 * lref.item(), (loss.item(), lref.item())
     lo = m.lora
-    overall, worst, bad = grad_report(((n, lo._view(ts.grad, n), Lr[n].grad) for n in lo.shapes), 0.98, 0.2)
+    overall, ofloor, worst, bad, ratio, at = floor_report([(n, lo._view(ts.grad, n), Lr[n].grad) for n in lo.shapes],
+                                                          _bf16_grads(U, cfg, Pr, x, t, ctx, fps, noise, lora=Lr), 0.98, 0.2)
     print(f"[unet tiny LoRA] out rel-L2 vs oracle {e_out:.3e}, vs reference golden {e_gold:.3e}; loss dev {loss.item():.6f} oracle {lref.item():.6f}; "
-          f"adapter grads overall {overall:.3e}, worst {worst:.3e} over {len(lo.shapes)} tensors")
-    assert e_out < 3e-2 and e_gold < 5e-2 and not bad and overall < 5e-2, bad[:8]
+          f"adapter grads overall {overall:.3e} (bf16 floor {ofloor:.3e}), worst {worst:.3e} over {len(lo.shapes)} tensors, "
+          f"worst device / floor {ratio:.2f} at {at}")
+    assert e_out < 3e-2 and e_gold < 5e-2 and not bad and overall < overall_bar(5e-2, ofloor), bad[:8]
     base_before = m.flat_bf16.clone()
     opt = FusedAdamW(ts.params, lr=1e-3, fullft_state=ts)
     before = ts.flat.clone()
@@ -218,34 +228,41 @@ def _block_case(dev, kind, full=False):
     shape = [B, T, H, W]
     for v in Pr.values():
         v.requires_grad_(True)
-    xr = (x.float() if full else x.double()).requires_grad_(True)
     dt_ = torch.float32 if full else torch.float64
-    x4 = xr.permute(0, 2, 1, 3, 4).reshape(B * T, cin, H, W)
+    se = torch.nn.functional.silu(emb)
+
+    def oracle(Pd, dt):
+        """the block's oracle function on the parameters Pd in dtype dt -> (input leaf, embedding leaf or None, output [B, C, T, H, W])"""
+        xr = x.to(dt).requires_grad_(True)
+        x4 = xr.permute(0, 2, 1, 3, 4).reshape(B * T, cin, H, W)
+        er = None
+        if kind in ("res", "res_same"):
+            # the oracle applies SiLU itself: feed it the pre-activation whose SiLU is `se` rounded to bf16 -> pass se through a patched call
+            er = se.to(BF).to(dt).repeat_interleave(T, dim=0).requires_grad_(True)
+            import torch.nn.functional as F
+            real_silu = F.silu
+            try:
+                F.silu = lambda t, *a, **k: t if t is er else real_silu(t, *a, **k)
+                ref4 = U.res_block(x4, er, Pd, layer.pre, B, True)
+            finally:
+                F.silu = real_silu
+        elif kind == "st":
+            ref4 = U.spatial_transformer(x4, ctx.to(dt).repeat_interleave(T, dim=0), Pd, layer.pre, layer.heads)
+        else:
+            return xr, er, U.temporal_transformer(xr, Pd, layer.pre, layer.heads)
+        return xr, er, ref4.reshape(B, T, ref4.shape[1], ref4.shape[2], ref4.shape[3]).permute(0, 2, 1, 3, 4)
+
     if kind in ("res", "res_same"):
-        se = torch.nn.functional.silu(emb)
         sev = _Var(se.to(dev, BF)); demb = torch.zeros(B, emb.shape[1], device=dev)
         yv = run.res_block(layer, xv, shape, sev, demb)
-        # the oracle applies SiLU itself: feed it the pre-activation whose SiLU is `se` rounded to bf16 -> pass se through a patched call
-        er = se.to(BF).to(dt_).repeat_interleave(T, dim=0).requires_grad_(True)
-        import torch.nn.functional as F
-        real_silu = F.silu
-        try:
-            F.silu = lambda t, *a, **k: t if t is er else real_silu(t, *a, **k)
-            ref4 = U.res_block(x4, er, Pr, layer.pre, B, True)
-        finally:
-            F.silu = real_silu
     elif kind == "st":
         ctxv = _Var(ctx.to(dev, BF).view(B * 77, -1).contiguous()); ctxv.g = False
         yv = run.spatial_transformer(layer, xv, shape, ctxv, 77)
-        ref4 = U.spatial_transformer(x4, ctx.to(dt_).repeat_interleave(T, dim=0), Pr, layer.pre, layer.heads)
     elif kind in ("tt", "init_tt"):
         yv = run.temporal_transformer(layer, xv, shape)
-        ref4 = None
-        ref5 = U.temporal_transformer(xr, Pr, layer.pre, layer.heads)
     else:
         pytest.skip("down / up run inside forward(): covered by the whole-network test")
-    cout = yv.d.shape[1]
-    ref5 = ref5 if kind in ("tt", "init_tt") else ref4.reshape(B, T, cout, ref4.shape[2], ref4.shape[3]).permute(0, 2, 1, 3, 4)
+    xr, er, ref5 = oracle(Pr, dt_)
     gy = torch.randn(ref5.shape, generator=g).to(BF).float()
     (ref5 * gy.to(dt_)).sum().backward()
     e_out = rel_l2(yv.d, _cl(ref5))
@@ -254,9 +271,14 @@ def _block_case(dev, kind, full=False):
         run.tape.pop()()
     e_dx = rel_l2(xv.g, _cl(xr.grad))
     names = [n for n in m.shapes if n.startswith(layer.pre + ".")]
-    worst = max(rel_l2(m._view(ts.grad, n), Pr[n].grad) for n in names)              # rel_l2 refuses a non-finite gradient
-    print(f"[unet block {kind}{' FULL SIZE ' + str([B, T, H, W, cin]) if full else ''}] out rel-L2 {e_out:.3e}, dx {e_dx:.3e}, worst parameter gradient {worst:.3e} over {len(names)} tensors")
-    assert e_out < 2e-2 and e_dx < 4e-2 and worst < 6e-2
+    Pb = bf16_leaves({n: Pr[n] for n in Pr if n.startswith(layer.pre + ".")})           # (at full size too: the bf16 run costs less than the fp32 one)
+    _, _, refb = oracle(Pb, BF)
+    assert refb.dtype == BF
+    (refb.float() * gy).sum().backward()                 # the upstream gradient meets the bf16 output in fp32, as the device's first backward kernel reads it
+    _, _, worst, bad, ratio, at = floor_report([(n, m._view(ts.grad, n), Pr[n].grad) for n in names], {n: Pb[n].grad for n in names}, -1.0, 6e-2)
+    note = f", worst device / floor {ratio:.2f} at {at}"
+    print(f"[unet block {kind}{' FULL SIZE ' + str([B, T, H, W, cin]) if full else ''}] out rel-L2 {e_out:.3e}, dx {e_dx:.3e}, worst parameter gradient {worst:.3e} over {len(names)} tensors{note}")
+    assert e_out < 2e-2 and e_dx < 4e-2 and not bad, bad[:8]
     if kind in ("res", "res_same"):
         dse = er.grad.view(B, T, -1).sum(1)
         assert rel_l2(demb, dse) < 4e-2

@@ -486,7 +486,7 @@ class _STRun(_Run):
         ops.gemm(pat, self.P.w["x_embedder.proj.weight"], h0, self.W("x_embedder.proj.bias"), epilogue=EPI_GATED_RES, residual=pos, r_mod=S)
         h = _Var(h0)
         if self.save:
-            def bwd_patch():
+            def bwd_patch(h=h):                                 # bound now: `h` is rebound to every block's output below
                 dwp = torch.zeros(D, 64, dtype=F32, device=dev)
                 ops.linear_dw(h.g, pat, dwp, accumulate=False)
                 self.G("x_embedder.proj.weight").add_(dwp[:, :Cin * pt * ph * pw])
