@@ -298,6 +298,32 @@ int vt_lora_pack_b_wide(const float* Bcat, void* Wext, int ldw, int n_adapters, 
 int vt_lora_pack_bt_wide(const float* Bcat, void* WText, int ldwt, int n_adapters, int d_out, int r, int rp, int ext, float scale,
                          void* stream);
 
+/* LoRA dropout (peft lora_dropout > 0: y = W x + b + (alpha/r) B A drop(x), one nn.Dropout per adapted Linear): _drop siblings of the
+ * six rank-side kernels.  No mask is stored; each kernel recomputes it.  Adapter j of a call is adapter site site0 + j (the engine
+ * numbers the sites 4 * layer + {0,1,2,3} for to_q, to_k, to_v, to_out.0); element (m, k) of the logical [M, K] adapter input (K, not
+ * ldx) is e = m * K + k and is kept iff word e % 4 of Philox4x32-10(key = seed, counter = (site << 36) + e / 4) >= floor(p * 2^32):
+ * vt_dropout_bf16's convention with offset = site << 36.  The n_adapters adapters of a call (R = n_adapters * r rank columns in the
+ * narrow kernels) read the same X under n_adapters different masks.  1 / (1 - p) multiplies the fp32 sums.  0 <= p < 1, else
+ * VT_ERR_BAD_SHAPE.  The masks are Philox, not torch's generator: statistically, not bit-wise, peft's. */
+int vt_lora_down_drop(const void* X, int ldx, const void* A, int lda, int R, int n_adapters, void* T, int ldt, long long M, int K,
+                      int zero_cols, float p, unsigned long long seed, int site0, void* stream);
+                                                                 /* T[m, j r + i] = 1/(1-p) sum_k keep_j(m,k) X[m,k] A[j r + i, k] */
+int vt_skinny_tn_drop(const void* Big, int ldb, const void* Small, int lds_, int R, int n_adapters, float* out, long long osp,
+                      long long osr, float alpha, long long M, int P, float* workspace, float p, unsigned long long seed, int site0,
+                      void* stream);                             /* out[p*osp+i*osr] += alpha/(1-p) sum_m keep_{i / r}(m,p) Big[m,p] Small[m,i];
+                                                                    Big is the logical [M, P] adapter input; n_adapters 1 or 3 */
+int vt_lora_up_add_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int R, int n_adapters, long long M, int K,
+                        float p, unsigned long long seed, int site0, void* stream);
+                                                                 /* dX[m,k] += 1/(1-p) sum_j keep_j(m,k) sum_i dT[m, j r + i] A[j r + i, k] */
+int vt_lora_down_wide_drop_fits(int n_adapters, int rp);         /* 1 if vt_lora_down_wide_drop takes n_adapters adapters in one call
+                                                                    (one masked X block per adapter must fit 64 KB of LDS) */
+int vt_lora_down_wide_drop(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T, int ldt,
+                           long long M, int K, float p, unsigned long long seed, int site0, void* stream);
+int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                         float alpha, long long M, int P, float p, unsigned long long seed, int site, void* stream);   /* one adapter */
+int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                             long long M, int K, float p, unsigned long long seed, int site0, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * VideoCrafter2 UNet path (BASELINE configs[3]): lvdm UNetModel.forward and its backward
  * (videotuna/models/lvdm/modules/networks/openaimodel3d.py:650-694) on ONE channels-last layout [B, T, H, W, C].

@@ -4,8 +4,11 @@ Each rank has its own model (same seeded base weights); blocks of --steps steps 
 of the box hits every rank alike.  Prints one JSON line: per rank the median ms per step with its spread over the rounds, the peak HBM
 of its blocks (the other ranks' idle models, ~3.4 GB of weights each, are resident and counted) and the step-time delta against rank 4
 of the same run.  Ranks <= 16 run the narrow rank-side kernels (csrc/lora.hip), 64 and 128 the MFMA ones (csrc/lora_wide.hip).
+--lora-dropout P (> 0) times every rank twice, lora_dropout = 0 and = P on the same model, alternating block by block: the entry
+"<rank>+drop" carries the delta against the same rank without dropout (the _drop kernels recompute a Philox mask in every pass).
 
     python tools/bench_lora_rank.py [--ranks 4,16,64,128] [--rounds 3] [--steps 2] [--warmup 1] [--micro-batch 4] > profiles/lora_rank_step.json
+    python tools/bench_lora_rank.py --ranks 4,64 --lora-dropout 0.1 > profiles/lora_dropout_step.json
 """
 import argparse
 import json
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--micro-batch", type=int, default=4)
+    ap.add_argument("--lora-dropout", type=float, default=0.0, help="P > 0: time lora_dropout = 0 and = P per rank, alternating")
     ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 is not the benchmark's model")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -55,13 +59,17 @@ def main():
         model.requires_grad_(False)
         peft = get_peft_model(model, LoraConfig(r=r, lora_alpha=r / 4.0, target_modules=["to_k", "to_q", "to_v", "to_out.0"]))
         st = peft._lora_state
-        runs[r] = dict(peft=peft, st=st, opt=FusedAdamW(st.params, lr=1.2e-5, lora_state=st), ms=[], peak=0.0, loss=None)
+        runs[str(r)] = dict(peft=peft, st=st, opt=FusedAdamW(st.params, lr=1.2e-5, lora_state=st), ms=[], peak=0.0, loss=None, p=0.0, rank=r)
+        if args.lora_dropout > 0:
+            LoraConfig(r=r, lora_dropout=args.lora_dropout)        # validates P
+            runs[f"{r}+drop"] = dict(runs[str(r)], ms=[], p=args.lora_dropout)
 
     def step(run):
         x0 = torch.randn(B, Fr, C, Hh, Ww, device=dev, generator=dgen)
         text = (torch.randn(B, St, 4096, device=dev, generator=dgen) * 0.2).to(torch.bfloat16)
         noise = torch.randn(B, Fr, C, Hh, Ww, device=dev, generator=dgen)
         t = torch.randint(0, 1000, (B,), device=dev, generator=dgen)
+        run["st"].p = run["p"]
         run["opt"].zero_grad()
         noisy = sched.add_noise(x0, noise, t)
         out = run["peft"](hidden_states=noisy, encoder_hidden_states=text, timestep=t, return_dict=False)[0]
@@ -76,7 +84,7 @@ def main():
             step(run)
     torch.cuda.synchronize()
     for _ in range(args.rounds):
-        for r, run in runs.items():
+        for run in runs.values():
             torch.cuda.reset_peak_memory_stats(dev)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -89,16 +97,20 @@ def main():
     res = {"metric": "CogVideoX-2B T2V LoRA step 49x480x720 bf16 by adapter rank, same process, alternating", "unit": "ms per step",
            "micro_batch": B, "layers": args.layers, "rounds": args.rounds, "steps_per_block": args.steps, "warmup_per_rank": args.warmup,
            "device": torch.cuda.get_device_name(0), "ranks": {}}
-    base = statistics.median(runs[ranks[0]]["ms"])
-    for r, run in runs.items():
+    base = statistics.median(runs[str(ranks[0])]["ms"])
+    for key, run in runs.items():
         st = run["st"]
         med = statistics.median(run["ms"])
-        res["ranks"][str(r)] = {"median_ms": round(med, 2), "spread_ms": round(max(run["ms"]) - min(run["ms"]), 2),
+        res["ranks"][key] = {"median_ms": round(med, 2), "spread_ms": round(max(run["ms"]) - min(run["ms"]), 2),
                                 "rounds_ms": [round(v, 2) for v in run["ms"]], "samples_per_s": round(B / (med / 1e3), 3),
                                 "peak_hbm_gb_all_models_resident": round(run["peak"], 1),
                                 "layout": {"wide": st.wide, "rp": st.rp, "ext_qkv": st.ext_qkv, "ext_o": st.ext_o},
                                 "trainable_params": st.flat.numel(), "loss_last": float(run["loss"]),
                                 f"delta_vs_r{ranks[0]}_ms": round(med - base, 2), f"delta_vs_r{ranks[0]}_pct": round(100.0 * (med - base) / base, 2)}
+        if run["p"] > 0:
+            same = statistics.median(runs[str(run["rank"])]["ms"])
+            res["ranks"][key].update({"lora_dropout": run["p"], "delta_vs_no_dropout_ms": round(med - same, 2),
+                                      "delta_vs_no_dropout_pct": round(100.0 * (med - same) / same, 2)})
     print(json.dumps(res), flush=True)
     return 0
 

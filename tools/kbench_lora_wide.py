@@ -12,7 +12,12 @@ Sustained rates: the HBM figure is the one profiles/gradclip_kbench.txt measured
 1.41 G elements: 5607.6 GB/s); the MFMA figure is what the library's large bf16 GEMMs hold inside the training step (1080-1100
 TFLOP/s; 1090 used).  A fraction is algorithmic work over time over that rate, not a counter reading.
 
+--drop P (> 0) times the lora_dropout sibling of every kernel that has one right after it ("path" ends in "+drop"; tn_dB reads the saved
+T and has none): same bytes, plus one Philox4x32-10 per 4 elements and adapter.  "vs_sibling" is its median over the sibling's.  Above
+rank 80 three masked X blocks do not fit the LDS and the dropped down-projection is three calls, one per adapter.
+
     python tools/kbench_lora_wide.py [--launches 20] [--warmup 5] > profiles/lora_wide_kbench.txt
+    python tools/kbench_lora_wide.py --drop 0.1 --ranks 4,16,32,64,128 > profiles/lora_dropout_kbench.txt
 """
 import argparse
 import json
@@ -31,6 +36,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rows", type=int, default=35552)
     ap.add_argument("--dim", type=int, default=1920)
+    ap.add_argument("--drop", type=float, default=0.0, help="P > 0: also time the lora_dropout siblings")
+    ap.add_argument("--ranks", default="16,32,64,128", help="ranks <= 16 also run the narrow kernels")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
@@ -55,6 +62,8 @@ def main():
             ts.append(e0.elapsed_time(e1))
         return statistics.median(ts), max(ts) - min(ts)
 
+    SEED, last = 0x2F3C5A7E9B1D4C68 >> 2, {}
+
     def line(kernel, r, path, fn, nbytes, flops, launches_per_call=1):
         med, spread = timed(fn)
         rec = {"kernel": kernel, "rank": r, "path": path, "rows": M, "dim": d, "launches_per_call": launches_per_call,
@@ -63,13 +72,19 @@ def main():
                "gb_per_s": round(nbytes / 1e9 / (med / 1e3), 1), "tflop_per_s": round(flops / 1e12 / (med / 1e3), 2),
                "frac_of_sustained_hbm": round(nbytes / 1e9 / (med / 1e3) / SUSTAINED_GBPS, 3),
                "frac_of_sustained_mfma": round(flops / 1e12 / (med / 1e3) / SUSTAINED_TFLOPS, 4)}
+        if path.endswith("+drop"):
+            rec["lora_dropout"] = args.drop
+            rec["vs_sibling"] = round(med / last[(kernel, path[:-5])], 3)
+        last[(kernel, path)] = med
         print(json.dumps(rec), flush=True)
         return rec
 
     print(json.dumps({"sustained_gb_per_s": SUSTAINED_GBPS, "sustained_gb_per_s_source": "profiles/gradclip_kbench.txt (vt_adamw, 1.41 G elements)",
                       "sustained_tflop_per_s": SUSTAINED_TFLOPS, "sustained_tflop_per_s_source": "DESIGN 5: gemm_*_bf16 in the training step",
                       "device": torch.cuda.get_device_name(0)}), flush=True)
-    for r, force in ((16, True), (32, False), (64, False), (128, False)):
+    P = args.drop
+    for r in [int(v) for v in args.ranks.split(",")]:
+        force = r <= 16
         rp, eq, eo, _ = extension_layout(r, wide=True)
         x1 = torch.randn(M, d + eq, device=dev, generator=g).to(BF)
         dy = torch.randn(M, d, device=dev, generator=g).to(BF)
@@ -79,29 +94,67 @@ def main():
         path = "wide (forced)" if force else "wide"
         line("down", r, path, lambda: ops.lora_down_wide(x1, A, 3, r, rp, eq, x1[:, d:], d),
              2.0 * (M * d + 3 * r * d + M * eq), 2.0 * M * d * 3 * r)
+        if P > 0:
+            one = ops.lora_down_wide_drop_fits(3, rp)
+
+            def down_drop():
+                if one:
+                    ops.lora_down_wide_drop(x1, A, 3, r, rp, eq, x1[:, d:], d, P, SEED, 0)
+                else:
+                    for j in range(3):
+                        ops.lora_down_wide_drop(x1, A[j * r:(j + 1) * r], 1, r, rp, rp if j < 2 else eq - 2 * rp, x1[:, d + j * rp:], d, P, SEED, j)
+            line("down", r, path + "+drop", down_drop, 2.0 * ((1 if one else 3) * M * d + 3 * r * d + M * eq), 2.0 * M * d * 3 * r, 1 if one else 3)
         line("tn_dB", r, path, lambda: ops.lora_tn_wide(dy, x1[:, d:], r, gB, r, 1, 0.25, d),
              2.0 * (M * d + M * r) + 8.0 * d * r, 2.0 * M * d * r)
         line("tn_dA", r, path, lambda: ops.lora_tn_wide(x1, x1[:, d:], r, gA, 1, d, 1.0, d),
              2.0 * (M * d + M * r) + 8.0 * d * r, 2.0 * M * d * r)
+        if P > 0:
+            line("tn_dA", r, path + "+drop", lambda: ops.lora_tn_wide_drop(x1, x1[:, d:], r, gA, 1, d, 1.0, d, P, SEED, 0),
+                 2.0 * (M * d + M * r) + 8.0 * d * r, 2.0 * M * d * r)
         x1[:, d:].mul_(0.01)                  # the in-place correction is repeated: keep the sum finite
         line("up_add", r, path, lambda: ops.lora_up_add_wide(x1, x1[:, d:], A, 3, r, rp, d),
              2.0 * (2 * M * d + M * 3 * rp + 3 * r * d), 2.0 * M * d * 3 * r)
-        if r == 16:                           # the narrow kernels at the same rank: one call per adapter, as the engine issues them
+        if P > 0:
+            line("up_add", r, path + "+drop", lambda: ops.lora_up_add_wide_drop(x1, x1[:, d:], A, 3, r, rp, d, P, SEED, 0),
+                 2.0 * (2 * M * d + M * 3 * rp + 3 * r * d), 2.0 * M * d * 3 * r)
+        if r <= 16:                           # the narrow kernels at the same rank, as the engine issues them: one call up to 3 r = 16, else one per adapter
             xn = torch.randn(M, d + 64, device=dev, generator=g).to(BF)
+            nc = 1 if 3 * r <= 16 else 3                       # calls per projection
+            Rc, na = (3 * r, 3) if nc == 1 else (r, 1)         # rank columns and adapters per call
 
             def down_narrow():
+                if nc == 1:
+                    return ops.lora_down(xn, A, 3 * r, xn[:, d:], d)
                 for j in range(3):
                     ops.lora_down(xn, A[j * r:(j + 1) * r], r, xn[:, d + j * r:], d, zero_cols=(64 - 2 * r - 16) if j == 2 else 0)
 
-            def up_narrow():
+            def down_narrow_drop():
+                if nc == 1:
+                    return ops.lora_down_drop(xn, A, 3 * r, 3, xn[:, d:], d, P, SEED, 0)
                 for j in range(3):
-                    ops.lora_up_add(xn, xn[:, d + j * r:], A[j * r:(j + 1) * r], r, d)
+                    ops.lora_down_drop(xn, A[j * r:(j + 1) * r], r, 1, xn[:, d + j * r:], d, P, SEED, j, zero_cols=(64 - 2 * r - 16) if j == 2 else 0)
 
-            line("down", r, "narrow", down_narrow, 2.0 * (3 * M * d + 3 * r * d + M * 64), 2.0 * M * d * 3 * r, 3)
+            def up_narrow():
+                for j in range(nc):
+                    ops.lora_up_add(xn, xn[:, d + j * r:], A[j * r:j * r + Rc], Rc, d)
+
+            def up_narrow_drop():
+                for j in range(nc):
+                    ops.lora_up_add_drop(xn, xn[:, d + j * r:], A[j * r:j * r + Rc], Rc, na, d, P, SEED, j)
+
+            gAn = torch.zeros(Rc, d, device=dev)
+            line("down", r, "narrow", down_narrow, 2.0 * (nc * M * d + 3 * r * d + M * 64), 2.0 * M * d * 3 * r, nc)
+            if P > 0:
+                line("down", r, "narrow+drop", down_narrow_drop, 2.0 * (nc * M * d + 3 * r * d + M * 64), 2.0 * M * d * 3 * r, nc)
             line("tn_dB", r, "narrow", lambda: ops.skinny_tn(dy, xn[:, d:], r, gB, r, 1, 0.25, d), 2.0 * (M * d + M * r) + 8.0 * d * r, 2.0 * M * d * r)
-            line("tn_dA", r, "narrow", lambda: ops.skinny_tn(xn, xn[:, d:], r, gA, 1, d, 1.0, d), 2.0 * (M * d + M * r) + 8.0 * d * r, 2.0 * M * d * r)
+            line("tn_dA", r, "narrow", lambda: ops.skinny_tn(xn, xn[:, d:], Rc, gAn, 1, d, 1.0, d), 2.0 * (M * d + M * Rc) + 8.0 * d * Rc, 2.0 * M * d * Rc)
+            if P > 0:
+                line("tn_dA", r, "narrow+drop", lambda: ops.skinny_tn_drop(xn, xn[:, d:], Rc, na, gAn, 1, d, 1.0, d, P, SEED, 0),
+                     2.0 * (M * d + M * Rc) + 8.0 * d * Rc, 2.0 * M * d * Rc)
             xn[:, d:].mul_(0.01)
-            line("up_add", r, "narrow", up_narrow, 2.0 * (3 * 2 * M * d + M * 3 * r + 3 * r * d), 2.0 * M * d * 3 * r, 3)
+            line("up_add", r, "narrow", up_narrow, 2.0 * (nc * 2 * M * d + M * 3 * r + 3 * r * d), 2.0 * M * d * 3 * r, nc)
+            if P > 0:
+                line("up_add", r, "narrow+drop", up_narrow_drop, 2.0 * (nc * 2 * M * d + M * 3 * r + 3 * r * d), 2.0 * M * d * 3 * r, nc)
             del xn
         del x1, dy
     return 0

@@ -83,6 +83,14 @@ PROTOTYPES = {
     "vt_lora_up_add_wide": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _vp],
     "vt_lora_pack_b_wide": [_fp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
     "vt_lora_pack_bt_wide": [_fp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp],
+    # lora_dropout > 0: the same products under recomputed Philox keep masks (p, seed, site0 after the sibling's arguments)
+    "vt_lora_down_drop": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _ll, _i, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_skinny_tn_drop": [_vp, _i, _vp, _i, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _fp, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_up_add_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_down_wide_drop_fits": [_i, _i],
+    "vt_lora_down_wide_drop": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_tn_wide_drop": [_vp, _i, _vp, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_up_add_wide_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     # ---- VideoCrafter2 UNet path ----
     "vt_conv_cl": [_vp, _ll, _vp, _vp, _fp, _i, _vp, _ll, _vp, _ll] + [_i] * 13 + [_vp],
     "vt_conv_dw_cl": [_vp, _ll, _vp, _ll, _fp] + [_i] * 13 + [_i, _vp],

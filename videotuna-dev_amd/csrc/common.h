@@ -126,3 +126,36 @@ __device__ __forceinline__ void rope_bwd8(const float* rope_cos, const float* ro
     }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11; Random123): the counter-based generator behind every stateless dropout mask of the library
+// (oracle/philox.py restates it in numpy).
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// The dropout mask convention shared by vt_dropout_bf16 and the LoRA _drop kernels: element e of a logical [M, C] array (e = m * C + c) is
+// kept iff word e % 4 of Philox(key = seed, counter = offset + e / 4) >= thresh, thresh = floor(p * 2^32) saturated to 2^32 - 1.
+static inline unsigned vt_keep_thresh(float p) {
+    const double t = (double)p * 4294967296.0;
+    return t >= 4294967295.0 ? 0xffffffffu : (unsigned)t;
+}
+// the 4 mask words of counter ctr
+__device__ __forceinline__ void keep_words4(unsigned long long ctr, unsigned long long seed, unsigned* rnd) {
+    philox4x32_10((unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), rnd);
+}
+// 8 consecutive bf16 (4 dwords) whose first element has counter ctr: dropped elements become +0
+__device__ __forceinline__ u32x4 keep_mask8(u32x4 v, unsigned long long ctr, unsigned long long seed, unsigned thresh) {
+    unsigned rnd[8];
+    keep_words4(ctr, seed, rnd);
+    keep_words4(ctr + 1, seed, rnd + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] &= (rnd[2 * i] >= thresh ? 0x0000ffffu : 0u) | (rnd[2 * i + 1] >= thresh ? 0xffff0000u : 0u);
+    return v;
+}
+// counter offset of adapter site s: 2^36 counters = 2^38 elements per site
+__device__ __forceinline__ unsigned long long lora_site_offset(int site) { return (unsigned long long)site << 36; }

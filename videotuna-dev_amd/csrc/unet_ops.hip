@@ -261,16 +261,6 @@ extern "C" int vt_add_rows_bf16(const void* a, long long lda, const void* b, lon
 // e = m * C + c: the mask is a pure function of (seed, offset, element index), so the backward pass calls the same kernel on the
 // gradient with the same (seed, offset) and no mask is stored.  nn.Dropout of TemporalConvBlock (openaimodel3d.py:278-296, p = 0.1)
 // in training mode.  mask_out (uint8 [M, C], optional): the keep bits, for parity tests (the oracle applies the exported mask).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 __global__ __launch_bounds__(UO_THREADS) void dropout_kernel(const bf16_t* x, long long ldx, bf16_t* y, long long ldy, long long M, int C, unsigned thresh,
                                                             float inv_keep, unsigned long long seed, unsigned long long offset, unsigned char* mask) {
     const int nch = C >> 3;

@@ -171,6 +171,8 @@ class CogVideoXTransformer3DModel(nn.Module):
         self._packed = None           # engine operands, built lazily from the parameters
         self._pos_cache: Dict[tuple, torch.Tensor] = {}
         self.lora = None              # set by vt355.lora.inject
+        self.lora_dropout_seed = None        # lora_dropout > 0: None = a fresh mask seed per training forward, an int pins it
+        self.last_lora_dropout_seed = None   # the seed the latest training forward used
         self.fullft = None            # set by vt355.fullft.enable_full_finetune
 
     # ----- HF-like surface -----

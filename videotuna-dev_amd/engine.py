@@ -133,7 +133,64 @@ def packed(model) -> SimpleNamespace:
 # The rank-r side kernels (csrc/lora.hip) take at most 16 rank columns per call.  The three q / k / v adapters of a fused projection fit one
 # call up to rank 5 (3 r <= 16: the shipped recipes, r = 4); above that (r <= 16) each adapter gets its own call on its r columns.
 # Ranks 17..128 (st.wide) take the MFMA kernels of csrc/lora_wide.hip: every adapter of a projection in one pass over the activation.
-def _lora_down_qkv(x1, st, i, d):
+#
+# lora_dropout: ``drop`` is None or (p, seed) of the forward in flight; the adapter sites of layer i are 4 i + {0, 1, 2, 3} for
+# to_q, to_k, to_v, to_out.0 and every site has its own keep mask.  With drop the _drop siblings run (same passes over the activation, the
+# mask recomputed in the kernel); without it the calls below are exactly the ones made before lora_dropout existed.
+def lora_dropout_seed(model):
+    """(p, seed) for one training forward of a model whose adapters have lora_dropout > 0, else None.  model.lora_dropout_seed pins the
+    seed; None draws a fresh one per forward from torch's CPU generator (every rank of a data-parallel job draws its own)."""
+    st = model.lora
+    if st is None or not getattr(st, "p", 0.0) or not model.training:
+        return None
+    seed = getattr(model, "lora_dropout_seed", None)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    model.last_lora_dropout_seed = int(seed)
+    return float(st.p), int(seed)
+
+
+def _lora_down_qkv_drop(x1, st, i, d, drop):
+    r, (p, seed) = st.r, drop
+    a = st.a_qkv(st.flat_bf16, i)
+    if st.wide:
+        if ops.lora_down_wide_drop_fits(3, st.rp):
+            ops.lora_down_wide_drop(x1, a, 3, r, st.rp, st.ext_qkv, x1[:, d:], d, p, seed, 4 * i)
+            return
+        for j in range(3):      # one masked copy of the X block per adapter does not fit the LDS: a call per adapter on its rp columns
+            ops.lora_down_wide_drop(x1, a[j * r:(j + 1) * r], 1, r, st.rp, st.rp if j < 2 else st.ext_qkv - 2 * st.rp,
+                                    x1[:, d + j * st.rp:], d, p, seed, 4 * i + j)
+        return
+    if 3 * r <= 16:
+        ops.lora_down_drop(x1, a, 3 * r, 3, x1[:, d:], d, p, seed, 4 * i)
+        return
+    for j in range(3):
+        ops.lora_down_drop(x1, a[j * r:(j + 1) * r], r, 1, x1[:, d + j * r:], d, p, seed, 4 * i + j,
+                           zero_cols=(EXT - 2 * r - 16) if j == 2 else 0)
+
+
+def _lora_qkv_input_grads_drop(x1, dx1, st, i, d, need_dx, drop):
+    r, (p, seed) = st.r, drop
+    if st.wide:
+        for j in range(3):
+            ops.lora_tn_wide_drop(x1, dx1[:, d + j * st.rp:], r, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d, p, seed, 4 * i + j)
+        if need_dx:
+            ops.lora_up_add_wide_drop(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3, r, st.rp, d, p, seed, 4 * i)
+        return
+    if 3 * r <= 16:
+        ops.skinny_tn_drop(x1, dx1[:, d:], 3 * r, 3, st.a_qkv(st.grad, i), 1, d, 1.0, d, p, seed, 4 * i)
+        if need_dx:
+            ops.lora_up_add_drop(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3 * r, 3, d, p, seed, 4 * i)
+        return
+    for j in range(3):
+        ops.skinny_tn_drop(x1, dx1[:, d + j * r:], r, 1, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d, p, seed, 4 * i + j)
+        if need_dx:
+            ops.lora_up_add_drop(dx1, dx1[:, d + j * r:], st.a_qkv(st.flat_bf16, i)[j * r:(j + 1) * r], r, 1, d, p, seed, 4 * i + j)
+
+
+def _lora_down_qkv(x1, st, i, d, drop=None):
+    if drop is not None:
+        return _lora_down_qkv_drop(x1, st, i, d, drop)
     r = st.r
     a = st.a_qkv(st.flat_bf16, i)
     if st.wide:
@@ -146,8 +203,10 @@ def _lora_down_qkv(x1, st, i, d):
         ops.lora_down(x1, a[j * r:(j + 1) * r], r, x1[:, d + j * r:], d, zero_cols=(EXT - 2 * r - 16) if j == 2 else 0)
 
 
-def _lora_qkv_input_grads(x1, dx1, st, i, d, need_dx=True):
+def _lora_qkv_input_grads(x1, dx1, st, i, d, need_dx=True, drop=None):
     """dA_qkv += dT^T x1 and (need_dx) dx1 += dT A_qkv for the fused projection's three adapters (dT = the extension columns of dx1)"""
+    if drop is not None:
+        return _lora_qkv_input_grads_drop(x1, dx1, st, i, d, need_dx, drop)
     r = st.r
     if st.wide:
         for j in range(3):
@@ -201,10 +260,10 @@ def _use_recompute(model, dims) -> bool:
     return need > 0.6 * free
 
 
-def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch):
+def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=None):
     """One CogVideoXBlock forward (diffusers CogVideoXBlock via cogvideo_pl.py:865-871): returns (h_out, a) where a holds
     what the block's backward needs (only ``h_in`` unless ``save``).  Called again from the backward pass when the block's
-    activations are recomputed instead of kept."""
+    activations are recomputed instead of kept, with the ``drop`` = (p, seed) of the first pass: the same lora_dropout masks."""
     c = model.config
     P = packed(model)
     st = model.lora
@@ -225,7 +284,7 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch):
     ops.ln_modulate_fwd(h, x1, Lw.n1g, Lw.n1b, (m1.shift_txt, m1.scale_txt, m1.shift_vid, m1.scale_vid, m1.bs),
                         a.mean1, a.rstd1, d, S, St, c.norm_eps)
     if st is not None:
-        _lora_down_qkv(x1, st, i, d)
+        _lora_down_qkv(x1, st, i, d, drop)
     qkv = E(M, 3 * d)
     ops.gemm(x1, Lw.w_qkv, qkv, Lw.b_qkv, K=KEq)
     qkh = E(M, 2 * d)
@@ -235,7 +294,11 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch):
     lse = E(B, H, S, dt=torch.float32)
     qk3, qkv3, o3 = qkh.view(B, S, 2 * d), qkv.view(B, S, 3 * d), o.view(B, S, d + eo)
     ops.attn_fwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], o3[:, :, :d], lse, B, H, S, q_prescaled=True)
-    if st is not None and st.wide:
+    if st is not None and drop is not None and st.wide:
+        ops.lora_down_wide_drop(o, st.a_out(st.flat_bf16, i), 1, st.r, st.rp, eo, o[:, d:], d, drop[0], drop[1], 4 * i + 3)
+    elif st is not None and drop is not None:
+        ops.lora_down_drop(o, st.a_out(st.flat_bf16, i), st.r, 1, o[:, d:], d, drop[0], drop[1], 4 * i + 3)
+    elif st is not None and st.wide:
         ops.lora_down_wide(o, st.a_out(st.flat_bf16, i), 1, st.r, st.rp, eo, o[:, d:], d)
     elif st is not None:
         ops.lora_down(o, st.a_out(st.flat_bf16, i), st.r, o[:, d:], d)
@@ -307,9 +370,10 @@ def run_forward(model, x, text, t, save: bool, rope=None):
     dims = (B, Fr, C, Hh, Ww, S, St, Sv, M)
     scratch = SimpleNamespace(xg=E(M, d), gbuf=E(M, c.ff_mult * d))     # transient: norm2 output, GELU output
     recompute = save and _use_recompute(model, dims)
+    drop = lora_dropout_seed(model)         # None unless lora_dropout > 0 and model.training
     saved: List[SimpleNamespace] = []
     for i in range(L):
-        h2, a = block_forward(model, i, h, mod, dims, rope, save and not recompute, scratch)
+        h2, a = block_forward(model, i, h, mod, dims, rope, save and not recompute, scratch, drop)
         if save:
             saved.append(a)         # recompute: only the block input (a.h_in), the rest is rebuilt in the backward pass
         h = h2
@@ -333,7 +397,8 @@ def run_forward(model, x, text, t, save: bool, rope=None):
     ctx = None
     if save:
         ctx = SimpleNamespace(blocks=saved, mod=mod, h_last=h, y1=y1, fm1=fm1, fr1=fr1, fm2=fm2, fr2=fr2,
-                              dims=dims, f_scale=f_scale, rope=rope, recompute=recompute, scratch=scratch if recompute else None)
+                              dims=dims, f_scale=f_scale, rope=rope, recompute=recompute, scratch=scratch if recompute else None,
+                              lora_drop=drop)
         if ft is not None:
             ctx.y2, ctx.tsin, ctx.e1_pre, ctx.e1, ctx.emb_pre, ctx.se, ctx.patches, ctx.text = y2, tsin, e1_pre, e1, emb_pre, emb, patches, text
     return out, ctx
@@ -353,6 +418,7 @@ def run_backward(model, ctx, dout: torch.Tensor):
     tn = ops.lora_tn_wide if wide else ops.skinny_tn          # rank gradients: MFMA kernel above rank 16
     E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
     mod = ctx.mod
+    drop = ctx.lora_drop          # (p, seed) of this forward's lora_dropout masks, or None
 
     # ---- final layers ----
     dtok = E(B * Sv, c.out_channels * p * p); ops.patchify(dout, dtok, p)
@@ -382,7 +448,7 @@ def run_backward(model, ctx, dout: torch.Tensor):
     for i in reversed(range(L)):
         Lw, a = P.layers[i], ctx.blocks[i]
         if ctx.recompute:           # rebuild this block's activations from its input
-            _, a = block_forward(model, i, a.h_in, mod, ctx.dims, ctx.rope, True, ctx.scratch)
+            _, a = block_forward(model, i, a.h_in, mod, ctx.dims, ctx.rope, True, ctx.scratch, drop)
         m1, m2 = _mod(mod, 2 * i, d), _mod(mod, 2 * i + 1, d)
         # --- feed-forward branch:  h2 = h1 + gate_ff * W2 gelu(W1 x2 + b1) ---
         ops.gate_mul(dh, tg, m2.gate_txt, m2.gate_vid, m2.bs, d, S, St)
@@ -392,12 +458,20 @@ def run_backward(model, ctx, dout: torch.Tensor):
         # --- attention branch:  h1 = h + gate_msa * (Wo' [O | T2]) ---
         ops.gate_mul(dh1, tg, m1.gate_txt, m1.gate_vid, m1.bs, d, S, St)
         ops.gemm(tg, Lw.w_o_t, dO, None)                                  # [M, d+ext_o]: dO | dT2
-        tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o
-        tn(a.o, dO[:, d:], r, st.a_out(st.grad, i), 1, d, 1.0, d)                   # dA_o
-        if wide:
-            ops.lora_up_add_wide(dO, dO[:, d:], st.a_out(st.flat_bf16, i), 1, r, rp, d)
+        tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o (reads the saved T: no mask)
+        ao, a_o, site = st.a_out(st.grad, i), st.a_out(st.flat_bf16, i), 4 * i + 3
+        if drop is None:
+            tn(a.o, dO[:, d:], r, ao, 1, d, 1.0, d)                                 # dA_o
+            if wide:
+                ops.lora_up_add_wide(dO, dO[:, d:], a_o, 1, r, rp, d)
+            else:
+                ops.lora_up_add(dO, dO[:, d:], a_o, r, d)
+        elif wide:                                                                  # the same two products under the masks of to_out.0's site
+            ops.lora_tn_wide_drop(a.o, dO[:, d:], r, ao, 1, d, 1.0, d, drop[0], drop[1], site)
+            ops.lora_up_add_wide_drop(dO, dO[:, d:], a_o, 1, r, rp, d, drop[0], drop[1], site)
         else:
-            ops.lora_up_add(dO, dO[:, d:], st.a_out(st.flat_bf16, i), r, d)
+            ops.skinny_tn_drop(a.o, dO[:, d:], r, 1, ao, 1, d, 1.0, d, drop[0], drop[1], site)
+            ops.lora_up_add_drop(dO, dO[:, d:], a_o, r, 1, d, drop[0], drop[1], site)
         dq.zero_()
         qk3, qkv3 = a.qkh.view(B, S, 2 * d), a.qkv.view(B, S, 3 * d)
         ops.attn_bwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], a.o.view(B, S, d + eo)[:, :, :d],
@@ -410,7 +484,7 @@ def run_backward(model, ctx, dout: torch.Tensor):
             ops.gemm(dqkv, Lw.w_qkv_t[d:], dx1[:, d:], None)              # the first block's input (frozen embeddings) needs no gradient: dT1 only
         for j in range(3):
             tn(dqkv[:, j * d:], a.x1[:, d + j * rp:], r, st.b_qkv(st.grad, i)[j * d:], r, 1, st.scaling, d)
-        _lora_qkv_input_grads(a.x1, dx1, st, i, d, need_dx=i > 0)
+        _lora_qkv_input_grads(a.x1, dx1, st, i, d, need_dx=i > 0, drop=drop)
         if i > 0:
             ops.ln_modulate_bwd(dx1, a.h_in, a.mean1, a.rstd1, Lw.n1g, (m1.scale_txt, m1.scale_vid, m1.bs), dh1, dh_in,
                                 d, S, St)

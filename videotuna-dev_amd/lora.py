@@ -45,6 +45,11 @@ def extension_layout(r: int, wide: bool = None):
 
 @dataclass
 class LoraConfig:
+    """peft.LoraConfig's fields as the CogVideoX recipes set them.  ``lora_dropout`` = p > 0: in training mode every adapted Linear
+    drops elements of its own input before lora_A, ``(alpha/r) B A (keep * x) / (1 - p)`` with one mask per adapted Linear and forward,
+    as peft's per-layer nn.Dropout does; model.eval() and p = 0 run the undropped kernels.  The masks come from Philox4x32-10 keyed by
+    ``model.lora_dropout_seed`` (None: a fresh seed per forward from torch's CPU generator; the seed used is kept in
+    ``model.last_lora_dropout_seed``), not from torch's device generator: statistically, not bit-wise, peft's masks."""
     r: int = 8
     lora_alpha: float = 8
     target_modules: Optional[Sequence[str]] = None
@@ -55,8 +60,8 @@ class LoraConfig:
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
-        if self.lora_dropout:
-            raise NotImplementedError("lora_dropout > 0 is not supported (the reference config uses 0)")
+        if not 0.0 <= float(self.lora_dropout) < 1.0:
+            raise ValueError(f"lora_dropout must be in [0, 1), got {self.lora_dropout}")
         if self.bias != "none":
             raise NotImplementedError("bias != 'none' is not supported")
         if self.r <= 0 or self.r > MAX_R:
@@ -99,6 +104,7 @@ class LoraState:
         # K-extension layout: per-adapter column stride and the extension widths of the fused qkv / out operands
         self.rp, self.ext_qkv, self.ext_o, self.wide = extension_layout(cfg.r)
         self.scaling = float(cfg.lora_alpha) / cfg.r
+        self.p = float(cfg.lora_dropout)      # lora_dropout: > 0 selects the _drop rank-side kernels in training mode
         self.d = model.inner_dim
         self.L = model.config.num_layers
         tm = list(cfg.target_modules or TARGETS)

@@ -712,6 +712,71 @@ def lora_pack_bt_wide(bcat_f32, wtext, ldwt: int, n_adapters: int, d_out: int, r
                                               _stream()), "vt_lora_pack_bt_wide")
 
 
+# ---- lora_dropout > 0 (csrc/lora.hip, csrc/lora_wide.hip): the six rank-side products under recomputed Philox keep masks ----
+# Adapter j of a call is adapter site site0 + j; element (m, k) of the logical [M, K] input is kept iff word e % 4 of
+# Philox(seed, (site << 36) + e / 4), e = m * K + k, is >= floor(p * 2^32) (oracle/philox.py: dropout_keep_mask(M, K, p, seed, site << 36)).
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def lora_down_drop(x, a, R: int, n_adapters: int, t_out, K: int, p: float, seed: int, site0: int, zero_cols: int = 48):
+    """lora_down with the n_adapters adapters of r = R / n_adapters rows each reading x under their own keep masks, times 1/(1-p)."""
+    _req(x, BF16, "x", 2); _req(a, BF16, "a", 2); _req(t_out, BF16, "t", 2)
+    check(load_library().vt_lora_down_drop(x.data_ptr(), x.stride(0), a.data_ptr(), a.stride(0), R, n_adapters, t_out.data_ptr(),
+                                           t_out.stride(0), x.shape[0], K, zero_cols, float(p), int(seed) & _U64, site0, _stream()),
+          "vt_lora_down_drop")
+
+
+def skinny_tn_drop(big, small, R: int, n_adapters: int, out, osp: int, osr: int, alpha: float, P: int, p: float, seed: int, site0: int,
+                   use_workspace: bool = False):
+    """skinny_tn with big (the logical [M, P] adapter input) masked per group of R / n_adapters columns of small, times 1/(1-p)."""
+    _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
+    lib = load_library()
+    ws = None
+    if use_workspace:
+        need = lib.vt_skinny_tn_workspace_bytes(P) // 4
+        key = big.device
+        if key not in _SKINNY_WS or _SKINNY_WS[key].numel() < need:
+            _SKINNY_WS[key] = torch.empty(need, dtype=torch.float32, device=big.device)
+        ws = _SKINNY_WS[key]
+    check(lib.vt_skinny_tn_drop(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, n_adapters, out.data_ptr(),
+                                osp, osr, alpha, big.shape[0], P, _p(ws), float(p), int(seed) & _U64, site0, _stream()),
+          "vt_skinny_tn_drop")
+
+
+def lora_up_add_drop(dx, dt, a, R: int, n_adapters: int, K: int, p: float, seed: int, site0: int):
+    """dx[:, :K] += 1/(1-p) sum_j keep_j * (dt[:, j r:(j+1) r] @ a[j r:(j+1) r]) in place, r = R / n_adapters."""
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    check(load_library().vt_lora_up_add_drop(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(), a.stride(0),
+                                             R, n_adapters, dx.shape[0], K, float(p), int(seed) & _U64, site0, _stream()),
+          "vt_lora_up_add_drop")
+
+
+def lora_down_wide_drop_fits(n_adapters: int, rp: int) -> bool:
+    """whether lora_down_wide_drop takes n_adapters adapters of padded rank rp in one call (else: one call per adapter)"""
+    return bool(load_library().vt_lora_down_wide_drop_fits(n_adapters, rp))
+
+
+def lora_down_wide_drop(x, a, n_adapters: int, r: int, rp: int, ext: int, t_out, K: int, p: float, seed: int, site0: int):
+    _req(x, BF16, "x", 2); _req(a, BF16, "a", 2); _req(t_out, BF16, "t", 2)
+    check(load_library().vt_lora_down_wide_drop(x.data_ptr(), x.stride(0), a.data_ptr(), a.stride(0), n_adapters, r, rp, ext,
+                                                t_out.data_ptr(), t_out.stride(0), x.shape[0], K, float(p), int(seed) & _U64, site0,
+                                                _stream()), "vt_lora_down_wide_drop")
+
+
+def lora_tn_wide_drop(big, small, R: int, out, osp: int, osr: int, alpha: float, P: int, p: float, seed: int, site: int):
+    _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
+    check(load_library().vt_lora_tn_wide_drop(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, out.data_ptr(),
+                                              osp, osr, alpha, big.shape[0], P, float(p), int(seed) & _U64, site, _stream()),
+          "vt_lora_tn_wide_drop")
+
+
+def lora_up_add_wide_drop(dx, dt, a, n_adapters: int, r: int, rp: int, K: int, p: float, seed: int, site0: int):
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    check(load_library().vt_lora_up_add_wide_drop(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(), a.stride(0),
+                                                  n_adapters, r, rp, dx.shape[0], K, float(p), int(seed) & _U64, site0, _stream()),
+          "vt_lora_up_add_wide_drop")
+
+
 # =====================================================================================================================
 # VideoCrafter2 UNet path (include/vt355.h, second half): channels-last [N, T, H, W, C] activations
 # =====================================================================================================================
