@@ -159,3 +159,21 @@ __device__ __forceinline__ u32x4 keep_mask8(u32x4 v, unsigned long long ctr, uns
 }
 // counter offset of adapter site s: 2^36 counters = 2^38 elements per site
 __device__ __forceinline__ unsigned long long lora_site_offset(int site) { return (unsigned long long)site << 36; }
+// The arguments that only a dropped LoRA rank-side kernel has.  Each of those kernels is a template whose trailing argument pack is one
+// LoraDrop or empty: the undropped instantiation then has no such kernel argument at all (an empty struct would still take a byte and
+// move the hidden arguments behind it) and `if constexpr` leaves none of the mask code in it.
+struct LoraDrop {
+    unsigned thresh;
+    float inv_keep;          // 1 / (1 - p)
+    unsigned long long seed;
+    int site0;               // adapter j of a call is site site0 + j
+    // read by the kernels of lora.hip only (lora_wide.hip takes n, r, rp with or without dropout and leaves these unread):
+    int n, r;                // lora_down, lora_up_add: the n adapters of r rank rows each that share the call
+    long long mbase;         // skinny_tn: the launch's first row within the call (the mask's element index counts rows of the whole input)
+};
+__device__ __forceinline__ LoraDrop lora_drop_arg() { return LoraDrop{}; }
+__device__ __forceinline__ LoraDrop lora_drop_arg(const LoraDrop& d) { return d; }
+static inline LoraDrop vt_lora_drop(float p, unsigned long long seed, int site0, int n = 0, int r = 0) {
+    return LoraDrop{vt_keep_thresh(p), 1.0f / (1.0f - p), seed, site0, n, r, 0};
+}
+static inline int vt_lora_drop_bad(float p, int site0) { return !(p >= 0.f) || !(p < 1.f) || site0 < 0 || site0 > (1 << 20); }

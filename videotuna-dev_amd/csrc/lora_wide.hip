@@ -7,6 +7,9 @@
 // Operands whose reduction index is the slow one in memory (the M rows of the rank gradients, the rank rows of A in the dX
 // correction) are transposed on their way into LDS.  LDS rows are padded by 8 elements: the 16-byte fragment reads of 16 rows
 // then start 4 banks apart.
+// lora_dropout > 0: each product's dropped form is the same kernel with the trailing LoraDrop argument (mask convention and
+// semantics: see lora.hip and common.h).  Adapter j of a call is site site0 + j; element (m, k) of the logical [M, K] adapter input
+// has index e = m * K + k.
 #include "common.h"
 
 #define LW_PAD 8
@@ -25,12 +28,20 @@ __device__ __forceinline__ void lw_store_pair_t(bf16_t* dst, int stride, int col
 // One block owns 64 rows of X and every output column, so X is read once whatever the rank.  Per 64-deep K block the X rows and
 // the n*rp (padded) rows of A go through LDS; wave w owns the 16-column tiles w, w+4, ... (at most 6) of all four 16-row tiles.
 // The product is taken as A X^T so that a lane ends up with 4 consecutive columns of one row: one 8-byte store.
+// DROP: T[m, j*rp + i] = 1/(1-p) sum_k keep_j(m,k) X[m,k] * A[j*r + i, k] with one masked copy of the 64 x 64 X block per adapter in
+// LDS: the mask is taken once per element and adapter while staging (masking the shared fragments in registers would repeat the
+// Philox work in each of the four waves).  The column tiles of a wave run through the adapters in order, so the X fragments are
+// reloaded only where the adapter changes.
 #define LWD_TPW 6
+template <typename... D>
 __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, int ldx, const bf16_t* A, int lda, int n, int r, int rp,
-                                                            int ext, bf16_t* T, int ldt, long long M, int K) {
+                                                            int ext, bf16_t* T, int ldt, long long M, int K, D... drop) {
+    constexpr bool DROP = sizeof...(D) > 0;
+    const LoraDrop dr = lora_drop_arg(drop...);
+    const int nx = DROP ? n : 1;                // X blocks in LDS
     extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
-    bf16_t* sX = lw_smem;                       // [64][LW_KS]
-    bf16_t* sA = lw_smem + 64 * LW_KS;          // [n*rp][LW_KS], zero rows where i >= r
+    bf16_t* sX = lw_smem;                       // [nx][64][LW_KS]; DROP: block j = X masked for adapter j
+    bf16_t* sA = lw_smem + nx * 64 * LW_KS;     // [n*rp][LW_KS], zero rows where i >= r
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int NC = n * rp, nct = NC >> 4;
     const long long row0 = (long long)blockIdx.x * 64;
@@ -48,7 +59,13 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
             const long long m = row0 + row;
             u32x4 v = zero4;
             if (m < M) v = *(const u32x4*)(X + (size_t)m * ldx + k0 + 8 * ch);
-            *(u32x4*)(sX + row * LW_KS + 8 * ch) = v;
+            if constexpr (DROP) {
+                const unsigned long long e4 = ((unsigned long long)m * K + k0 + 8 * ch) >> 2;
+                for (int j = 0; j < n; ++j)
+                    *(u32x4*)(sX + (j * 64 + row) * LW_KS + 8 * ch) = keep_mask8(v, lora_site_offset(dr.site0 + j) + e4, dr.seed, dr.thresh);
+            } else {
+                *(u32x4*)(sX + row * LW_KS + 8 * ch) = v;
+            }
         }
         for (int u = tid; u < NC * 8; u += 256) {
             const int c = u >> 3, ch = u & 7;
@@ -61,12 +78,23 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 xf[4];
+            int jcur = -1;
+            if constexpr (!DROP) {
 #pragma unroll
-            for (int rt = 0; rt < 4; ++rt) xf[rt] = lw_frag(sX + (rt * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
+                for (int rt = 0; rt < 4; ++rt) xf[rt] = lw_frag(sX + (rt * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
+            }
 #pragma unroll
             for (int i = 0; i < LWD_TPW; ++i) {
                 const int t = wave + 4 * i;
                 if (t < nct) {
+                    if constexpr (DROP) {
+                        const int j = (16 * t) / rp;
+                        if (j != jcur) {
+                            jcur = j;
+#pragma unroll
+                            for (int rt = 0; rt < 4; ++rt) xf[rt] = lw_frag(sX + (j * 64 + rt * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
+                        }
+                    }
                     const bf16x8 af = lw_frag(sA + (t * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
 #pragma unroll
                     for (int rt = 0; rt < 4; ++rt) acc[i][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, xf[rt], acc[i][rt], 0, 0, 0);
@@ -84,6 +112,7 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
                 const long long m = row0 + rt * 16 + fr;
                 if (m < M) {
                     u32x2 o;
+                    if constexpr (DROP) acc[i][rt] *= dr.inv_keep;
                     o[0] = pack2(acc[i][rt][0], acc[i][rt][1]);
                     o[1] = pack2(acc[i][rt][2], acc[i][rt][3]);
                     *(u32x2*)(T + (size_t)m * ldt + t * 16 + 4 * fq) = o;
@@ -99,8 +128,13 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
         if (m < M) *(u32x2*)(T + (size_t)m * ldt + NC + 4 * cc) = u32x2{0u, 0u};
     }
 }
-extern "C" int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
-                                 int ldt, long long M, int K, void* stream) {
+// DROP: n_adapters masked X blocks and the padded A rows must fit the 64 KB of LDS a block gets without opting in to more
+extern "C" int vt_lora_down_wide_drop_fits(int n_adapters, int rp) {
+    return (size_t)n_adapters * (64 + rp) * LW_KS * sizeof(bf16_t) <= 65536 && n_adapters * rp <= 16 * 4 * LWD_TPW;
+}
+// dr == nullptr: no dropout
+static int lora_down_wide_launch(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T, int ldt,
+                                 long long M, int K, const LoraDrop* dr, void* stream) {
     if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
         n_adapters * rp > 16 * 4 * LWD_TPW || ext < n_adapters * rp || (ext % 4) || (ldx % 8) || (lda % 8) || (ldt % 4) || ldt < ext)
         return VT_ERR_BAD_SHAPE;
@@ -108,10 +142,24 @@ extern "C" int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda,
     if (((uintptr_t)T) & 7) return VT_ERR_BAD_ALIGN;
     const long long blocks = (M + 63) / 64;
     if (blocks > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-    const size_t lds = (size_t)(64 + n_adapters * rp) * LW_KS * sizeof(bf16_t);
-    hipLaunchKernelGGL(lora_wide_down_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X, ldx,
-                       (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K);
+    const size_t lds = (size_t)((dr ? n_adapters : 1) * 64 + n_adapters * rp) * LW_KS * sizeof(bf16_t);
+    if (dr == nullptr)
+        hipLaunchKernelGGL(lora_wide_down_kernel<>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X, ldx,
+                           (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K);
+    else
+        hipLaunchKernelGGL(lora_wide_down_kernel<LoraDrop>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X,
+                           ldx, (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K, *dr);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+extern "C" int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
+                                 int ldt, long long M, int K, void* stream) {
+    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, nullptr, stream);
+}
+extern "C" int vt_lora_down_wide_drop(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
+                                      int ldt, long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
+    if (n_adapters <= 0 || !vt_lora_down_wide_drop_fits(n_adapters, rp) || vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, &dr, stream);
 }
 
 // ---------------- out[p*osp + i*osr] += alpha * sum_m Big[m,p] * Small[m,i]   (i < R <= 128) ----------------
@@ -121,11 +169,16 @@ extern "C" int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda,
 // chosen so that about two blocks per CU exist, which keeps the atomic traffic (slices * P * R * 4 bytes) well under the bytes of
 // Big itself.  Atomic sums depend on arrival order: the result is not bitwise reproducible (there is no two-stage mode here).
 // I_FAST: the operand order that makes a wave's atomic instruction run along the output's fast index (i when osr == 1, else p).
+// DROP: out += alpha/(1-p) * sum_m keep_s(m,p) Big[m,p] * Small[m,i] for one adapter, site s = site0: Big is masked on its way into
+// LDS (each element of Big is staged once per call); alpha carries the 1 / (1 - p).
 #define LWT_BLOCKS 512
-template <bool I_FAST>
+template <bool I_FAST, typename... D>
 __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, int ldb, const bf16_t* Small, int lds_, int R, float* out,
                                                           long long osp, long long osr, float alpha, long long M, int P,
-                                                          int tiles_per_slice) {
+                                                          int tiles_per_slice, D... drop) {
+    constexpr bool DROP = sizeof...(D) > 0;
+    const LoraDrop dr = lora_drop_arg(drop...);
+    const unsigned long long off = lora_site_offset(dr.site0);
     __shared__ __attribute__((aligned(16))) bf16_t sB[128 * LW_KS];
     __shared__ __attribute__((aligned(16))) bf16_t sS[128 * LW_KS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
@@ -151,6 +204,11 @@ __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, in
             if (p < P) {
                 if (m < M) r0 = *(const u32x4*)(Big + (size_t)m * ldb + p);
                 if (m + 1 < M) r1 = *(const u32x4*)(Big + (size_t)(m + 1) * ldb + p);
+                if constexpr (DROP) {
+                    const unsigned long long e4 = ((unsigned long long)m * P + p) >> 2;
+                    if (m < M) r0 = keep_mask8(r0, off + e4, dr.seed, dr.thresh);
+                    if (m + 1 < M) r1 = keep_mask8(r1, off + e4 + (P >> 2), dr.seed, dr.thresh);
+                }
             }
             lw_store_pair_t(sB, LW_KS, 8 * pc, q, r0, r1);
         }
@@ -197,8 +255,9 @@ __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, in
             }
         }
 }
-extern "C" int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
-                               float alpha, long long M, int P, void* stream) {
+// dr == nullptr: no dropout, else alpha carries the 1 / (1 - p)
+static int lora_tn_wide_launch(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                               float alpha, long long M, int P, const LoraDrop* dr, void* stream) {
     if (M <= 0 || P <= 0 || (P % 8) || R <= 0 || R > 128 || (ldb % 8) || lds_ < R || osp <= 0 || osr <= 0) return VT_ERR_BAD_SHAPE;
     if (((uintptr_t)Big) & 15) return VT_ERR_BAD_ALIGN;
     if ((((uintptr_t)Small) & 1) || (((uintptr_t)out) & 3)) return VT_ERR_BAD_ALIGN;
@@ -212,13 +271,26 @@ extern "C" int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int 
     if (tps > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
     dim3 grid((unsigned)pblocks, (unsigned)slices);
     hipStream_t st = (hipStream_t)stream;
-    if (osr == 1)
-        hipLaunchKernelGGL(lora_wide_tn_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)Big, ldb, (const bf16_t*)Small, lds_, R, out,
-                           osp, osr, alpha, M, P, (int)tps);
-    else
-        hipLaunchKernelGGL(lora_wide_tn_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)Big, ldb, (const bf16_t*)Small, lds_, R, out,
-                           osp, osr, alpha, M, P, (int)tps);
+#define LWT_ARGS (const bf16_t*)Big, ldb, (const bf16_t*)Small, lds_, R, out, osp, osr, alpha, M, P, (int)tps
+    if (dr == nullptr) {
+        if (osr == 1) hipLaunchKernelGGL(lora_wide_tn_kernel<true>, grid, dim3(256), 0, st, LWT_ARGS);
+        else hipLaunchKernelGGL(lora_wide_tn_kernel<false>, grid, dim3(256), 0, st, LWT_ARGS);
+    } else {
+        if (osr == 1) hipLaunchKernelGGL((lora_wide_tn_kernel<true, LoraDrop>), grid, dim3(256), 0, st, LWT_ARGS, *dr);
+        else hipLaunchKernelGGL((lora_wide_tn_kernel<false, LoraDrop>), grid, dim3(256), 0, st, LWT_ARGS, *dr);
+    }
+#undef LWT_ARGS
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+extern "C" int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                               float alpha, long long M, int P, void* stream) {
+    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha, M, P, nullptr, stream);
+}
+extern "C" int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                                    float alpha, long long M, int P, float p, unsigned long long seed, int site, void* stream) {
+    if (vt_lora_drop_bad(p, site)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site);
+    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha * dr.inv_keep, M, P, &dr, stream);
 }
 
 // ---------------- dX[m,k] += sum_j sum_i dT[m, j*rp + i] * A[j*r + i, k]   (in place, bf16; all adapters in one pass) ----------------
@@ -226,9 +298,17 @@ extern "C" int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int 
 // padded rank columns) and the block walks the K columns 64 at a time, A^T of those columns staged in LDS ([k][c], zero where the
 // padded column c carries no adapter row).  A^T dT^T puts 4 consecutive columns of one row in a lane: dX is read and written once,
 // 8 bytes per lane and tile.
+// DROP: dX[m,k] += 1/(1-p) sum_j keep_j(m,k) sum_i dT[m, j*rp + i] * A[j*r + i, k] with an adapter-outer loop: adapter j's MFMA chain
+// runs over the 32-deep steps that touch its columns [j rp, (j+1) rp) with the dT fragments of lanes whose 8 columns belong to
+// another adapter zeroed (rp = 48, 80: an adapter boundary falls inside a step; a lane's 8 columns never straddle one because
+// rp % 16 == 0), its sum is masked -- a lane's 4 consecutive columns of a row are one Philox counter -- and added to a running fp32
+// total.
 #define LWU_MAXKS 12
+template <typename... D>
 __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int ldx, const bf16_t* dT, int ldt, const bf16_t* A, int lda,
-                                                              int n, int r, int rp, long long M, int K) {
+                                                              int n, int r, int rp, long long M, int K, D... drop) {
+    constexpr bool DROP = sizeof...(D) > 0;
+    const LoraDrop dr = lora_drop_arg(drop...);
     extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int NC = n * rp, NCp = (NC + 31) & ~31, nks = NCp >> 5, LS = NCp + LW_PAD;
@@ -262,19 +342,58 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
             lw_store_pair_t(sAt, LS, 8 * pc, q, rr[0], rr[1]);
         }
         __syncthreads();
-        f32x4 acc[2][4];
+        f32x4 acc[2][4];            // DROP: the running total of the adapters' masked sums, before the 1 / (1 - p)
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
             for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (DROP) {
+            const bf16x8 zero8 = __builtin_bit_cast(bf16x8, zero4);
+            for (int j = 0; j < n; ++j) {
+                const int c_lo = j * rp, c_hi = c_lo + rp;
+                f32x4 aj[2][4];
 #pragma unroll
-        for (int ks = 0; ks < LWU_MAXKS; ++ks) {
-            if (ks < nks) {
+                for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    const bf16x8 af = lw_frag(sAt + (ct * 16 + fr) * LS + ks * 32 + 8 * fq);
+                    for (int ct = 0; ct < 4; ++ct) aj[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int rt = 0; rt < 2; ++rt) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, dtf[rt][ks], acc[rt][ct], 0, 0, 0);
+                for (int ks = 0; ks < LWU_MAXKS; ++ks) {
+                    if (ks < nks && ks * 32 + 32 > c_lo && ks * 32 < c_hi) {
+                        const int c = ks * 32 + 8 * fq;
+                        const bool mine = c >= c_lo && c < c_hi;
+                        const bf16x8 d0 = mine ? dtf[0][ks] : zero8, d1 = mine ? dtf[1][ks] : zero8;
+#pragma unroll
+                        for (int ct = 0; ct < 4; ++ct) {
+                            const bf16x8 af = lw_frag(sAt + (ct * 16 + fr) * LS + ks * 32 + 8 * fq);
+                            aj[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, d0, aj[0][ct], 0, 0, 0);
+                            aj[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, d1, aj[1][ct], 0, 0, 0);
+                        }
+                    }
+                }
+                // D[row = column k0 + 16ct + 4fq + reg][col = row fr of the row tile]
+                const unsigned long long off = lora_site_offset(dr.site0 + j);
+#pragma unroll
+                for (int rt = 0; rt < 2; ++rt) {
+                    const unsigned long long e4 = ((unsigned long long)(row0 + rt * 16 + fr) * K + k0 + 4 * fq) >> 2;
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        unsigned rnd[4];
+                        keep_words4(off + e4 + 4 * ct, dr.seed, rnd);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[rt][ct][q] += rnd[q] >= dr.thresh ? aj[rt][ct][q] : 0.f;
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < LWU_MAXKS; ++ks) {
+                if (ks < nks) {
+#pragma unroll
+                    for (int ct = 0; ct < 4; ++ct) {
+                        const bf16x8 af = lw_frag(sAt + (ct * 16 + fr) * LS + ks * 32 + 8 * fq);
+#pragma unroll
+                        for (int rt = 0; rt < 2; ++rt) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, dtf[rt][ks], acc[rt][ct], 0, 0, 0);
+                    }
                 }
             }
         }
@@ -287,17 +406,26 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
                 for (int ct = 0; ct < 4; ++ct) {
                     u32x2* px = (u32x2*)(dX + (size_t)m * ldx + k0 + ct * 16 + 4 * fq);
                     const u32x2 old = *px;
+                    const float lo0 = __uint_as_float(old[0] << 16), hi0 = __uint_as_float(old[0] & 0xffff0000u);
+                    const float lo1 = __uint_as_float(old[1] << 16), hi1 = __uint_as_float(old[1] & 0xffff0000u);
+                    const f32x4 a = acc[rt][ct];
                     u32x2 o;
-                    o[0] = pack2(__uint_as_float(old[0] << 16) + acc[rt][ct][0], __uint_as_float(old[0] & 0xffff0000u) + acc[rt][ct][1]);
-                    o[1] = pack2(__uint_as_float(old[1] << 16) + acc[rt][ct][2], __uint_as_float(old[1] & 0xffff0000u) + acc[rt][ct][3]);
+                    if constexpr (DROP) {          // one expression per element: the multiply and the add contract into an fma
+                        o[0] = pack2(lo0 + dr.inv_keep * a[0], hi0 + dr.inv_keep * a[1]);
+                        o[1] = pack2(lo1 + dr.inv_keep * a[2], hi1 + dr.inv_keep * a[3]);
+                    } else {
+                        o[0] = pack2(lo0 + a[0], hi0 + a[1]);
+                        o[1] = pack2(lo1 + a[2], hi1 + a[3]);
+                    }
                     *px = o;
                 }
             }
         }
     }
 }
-extern "C" int vt_lora_up_add_wide(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
-                                   long long M, int K, void* stream) {
+// dr == nullptr: no dropout
+static int lora_up_add_wide_launch(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                   long long M, int K, const LoraDrop* dr, void* stream) {
     if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
         n_adapters * rp > 32 * LWU_MAXKS || (ldx % 4) || ldx < K || (ldt % 8) || ldt < n_adapters * rp || (lda % 8))
         return VT_ERR_BAD_SHAPE;
@@ -307,9 +435,23 @@ extern "C" int vt_lora_up_add_wide(void* dX, int ldx, const void* dT, int ldt, c
     if (blocks > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
     const int NCp = (n_adapters * rp + 31) & ~31;
     const size_t lds = (size_t)64 * (NCp + LW_PAD) * sizeof(bf16_t);
-    hipLaunchKernelGGL(lora_wide_up_add_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
-                       (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K);
+    if (dr == nullptr)
+        hipLaunchKernelGGL(lora_wide_up_add_kernel<>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
+                           (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K);
+    else
+        hipLaunchKernelGGL(lora_wide_up_add_kernel<LoraDrop>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
+                           (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+extern "C" int vt_lora_up_add_wide(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                   long long M, int K, void* stream) {
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, nullptr, stream);
+}
+extern "C" int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                        long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
+    if (vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, stream);
 }
 
 // ---------------- write (alpha/r) * B into the ext-column K-extension of the packed weight and of its transpose ----------------
@@ -357,336 +499,3 @@ extern "C" int vt_lora_pack_bt_wide(const float* Bcat, void* WText, int ldwt, in
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
-// =====================================================================================================================
-// lora_dropout > 0: _drop siblings of the three rank-side kernels above (mask convention and semantics: see lora.hip).
-// Adapter j of a call is site site0 + j; element (m, k) of the logical [M, K] adapter input has index e = m * K + k.
-// =====================================================================================================================
-static int lw_drop_args_bad(float p, int site0) { return !(p >= 0.f) || !(p < 1.f) || site0 < 0 || site0 > (1 << 20); }
-
-// ---------------- T[m, j*rp + i] = 1/(1-p) sum_k keep_j(m,k) X[m,k] * A[j*r + i, k] ----------------
-// lora_wide_down_kernel with one masked copy of the 64 x 64 X block per adapter in LDS: the mask is taken once per element and
-// adapter while staging (masking the shared fragments in registers would repeat the Philox work in each of the four waves).  The
-// column tiles of a wave run through the adapters in order, so the X fragments are reloaded only where the adapter changes.
-__global__ __launch_bounds__(256) void lora_wide_down_drop_kernel(const bf16_t* X, int ldx, const bf16_t* A, int lda, int n, int r, int rp,
-                                                                 int ext, bf16_t* T, int ldt, long long M, int K, unsigned thresh,
-                                                                 float inv_keep, unsigned long long seed, int site0) {
-    extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
-    bf16_t* sX = lw_smem;                           // [n][64][LW_KS]: X masked for adapter j
-    bf16_t* sA = lw_smem + n * 64 * LW_KS;          // [n*rp][LW_KS], zero rows where i >= r
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
-    const int NC = n * rp, nct = NC >> 4;
-    const long long row0 = (long long)blockIdx.x * 64;
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    f32x4 acc[LWD_TPW][4];
-#pragma unroll
-    for (int i = 0; i < LWD_TPW; ++i)
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[i][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < K; k0 += 64) {
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int u = tid + 256 * it, row = u >> 3, ch = u & 7;
-            const long long m = row0 + row;
-            u32x4 v = zero4;
-            if (m < M) v = *(const u32x4*)(X + (size_t)m * ldx + k0 + 8 * ch);
-            const unsigned long long e4 = ((unsigned long long)m * K + k0 + 8 * ch) >> 2;
-            for (int j = 0; j < n; ++j)
-                *(u32x4*)(sX + (j * 64 + row) * LW_KS + 8 * ch) = keep_mask8(v, lora_site_offset(site0 + j) + e4, seed, thresh);
-        }
-        for (int u = tid; u < NC * 8; u += 256) {
-            const int c = u >> 3, ch = u & 7;
-            const int j = c / rp, i = c - j * rp;
-            u32x4 v = zero4;
-            if (i < r) v = *(const u32x4*)(A + (size_t)(j * r + i) * lda + k0 + 8 * ch);
-            *(u32x4*)(sA + c * LW_KS + 8 * ch) = v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 xf[4];
-            int jcur = -1;
-#pragma unroll
-            for (int i = 0; i < LWD_TPW; ++i) {
-                const int t = wave + 4 * i;
-                if (t < nct) {
-                    const int j = (16 * t) / rp;
-                    if (j != jcur) {
-                        jcur = j;
-#pragma unroll
-                        for (int rt = 0; rt < 4; ++rt) xf[rt] = lw_frag(sX + (j * 64 + rt * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
-                    }
-                    const bf16x8 af = lw_frag(sA + (t * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
-#pragma unroll
-                    for (int rt = 0; rt < 4; ++rt) acc[i][rt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, xf[rt], acc[i][rt], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < LWD_TPW; ++i) {
-        const int t = wave + 4 * i;
-        if (t < nct) {
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) {
-                const long long m = row0 + rt * 16 + fr;
-                if (m < M) {
-                    u32x2 o;
-                    o[0] = pack2(inv_keep * acc[i][rt][0], inv_keep * acc[i][rt][1]);
-                    o[1] = pack2(inv_keep * acc[i][rt][2], inv_keep * acc[i][rt][3]);
-                    *(u32x2*)(T + (size_t)m * ldt + t * 16 + 4 * fq) = o;
-                }
-            }
-        }
-    }
-    const int zc = (ext - NC) >> 2;
-    for (int u = tid; u < 64 * zc; u += 256) {
-        const int row = u / zc, cc = u - row * zc;
-        const long long m = row0 + row;
-        if (m < M) *(u32x2*)(T + (size_t)m * ldt + NC + 4 * cc) = u32x2{0u, 0u};
-    }
-}
-// n_adapters masked X blocks and the padded A rows must fit the 64 KB of LDS a block gets without opting in to more
-extern "C" int vt_lora_down_wide_drop_fits(int n_adapters, int rp) {
-    return (size_t)n_adapters * (64 + rp) * LW_KS * sizeof(bf16_t) <= 65536 && n_adapters * rp <= 16 * 4 * LWD_TPW;
-}
-extern "C" int vt_lora_down_wide_drop(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
-                                      int ldt, long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
-    if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
-        !vt_lora_down_wide_drop_fits(n_adapters, rp) || ext < n_adapters * rp || (ext % 4) || (ldx % 8) || (lda % 8) || (ldt % 4) ||
-        ldt < ext || lw_drop_args_bad(p, site0))
-        return VT_ERR_BAD_SHAPE;
-    if ((((uintptr_t)X) | ((uintptr_t)A)) & 15) return VT_ERR_BAD_ALIGN;
-    if (((uintptr_t)T) & 7) return VT_ERR_BAD_ALIGN;
-    const long long blocks = (M + 63) / 64;
-    if (blocks > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-    const size_t lds = (size_t)n_adapters * (64 + rp) * LW_KS * sizeof(bf16_t);
-    hipLaunchKernelGGL(lora_wide_down_drop_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X, ldx,
-                       (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K, vt_keep_thresh(p), 1.0f / (1.0f - p), seed,
-                       site0);
-    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-
-// ---------------- out[p*osp + i*osr] += alpha/(1-p) * sum_m keep_s(m,p) Big[m,p] * Small[m,i]   (one adapter, site s) ----------------
-// lora_wide_tn_kernel with Big masked on its way into LDS (each element of Big is staged once per call)
-template <bool I_FAST>
-__global__ __launch_bounds__(256) void lora_wide_tn_drop_kernel(const bf16_t* Big, int ldb, const bf16_t* Small, int lds_, int R, float* out,
-                                                               long long osp, long long osr, float alpha, long long M, int P,
-                                                               int tiles_per_slice, unsigned thresh, unsigned long long seed, int site) {
-    __shared__ __attribute__((aligned(16))) bf16_t sB[128 * LW_KS];
-    __shared__ __attribute__((aligned(16))) bf16_t sS[128 * LW_KS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
-    const int p0 = blockIdx.x * 128;
-    const int nit = (R + 15) >> 4;
-    const long long tile0 = (long long)blockIdx.y * tiles_per_slice;
-    const unsigned long long off = lora_site_offset(site);
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    f32x4 acc[2][8];
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-        for (int it = 0; it < 8; ++it) acc[pt][it] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < tiles_per_slice; ++t) {
-        const long long m0 = (tile0 + t) * 64;
-        if (m0 >= M) break;
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int u = tid + 256 * it, q = u >> 4, pc = u & 15;
-            const int p = p0 + 8 * pc;
-            const long long m = m0 + 2 * q;
-            u32x4 r0 = zero4, r1 = zero4;
-            if (p < P) {
-                const unsigned long long e4 = ((unsigned long long)m * P + p) >> 2;
-                if (m < M) r0 = keep_mask8(*(const u32x4*)(Big + (size_t)m * ldb + p), off + e4, seed, thresh);
-                if (m + 1 < M) r1 = keep_mask8(*(const u32x4*)(Big + (size_t)(m + 1) * ldb + p), off + e4 + (P >> 2), seed, thresh);
-            }
-            lw_store_pair_t(sB, LW_KS, 8 * pc, q, r0, r1);
-        }
-        for (int u = tid; u < nit * 16 * 32; u += 256) {
-            const int q = u / (nit * 16), i = u - q * (nit * 16);
-            const long long m = m0 + 2 * q;
-            unsigned int lo = 0, hi = 0;
-            if (i < R) {
-                if (m < M) lo = *(const unsigned short*)(Small + (size_t)m * lds_ + i);
-                if (m + 1 < M) hi = *(const unsigned short*)(Small + (size_t)(m + 1) * lds_ + i);
-            }
-            *(unsigned int*)(sS + i * LW_KS + 2 * q) = lo | (hi << 16);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 bfr[2];
-#pragma unroll
-            for (int pt = 0; pt < 2; ++pt) bfr[pt] = lw_frag(sB + ((2 * wave + pt) * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
-#pragma unroll
-            for (int it = 0; it < 8; ++it) {
-                if (it < nit) {
-                    const bf16x8 sf = lw_frag(sS + (it * 16 + fr) * LW_KS + ks * 32 + 8 * fq);
-#pragma unroll
-                    for (int pt = 0; pt < 2; ++pt)
-                        acc[pt][it] = I_FAST ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[pt], sf, acc[pt][it], 0, 0, 0)
-                                             : __builtin_amdgcn_mfma_f32_16x16x32_bf16(sf, bfr[pt], acc[pt][it], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt)
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            if (it < nit) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int p = p0 + (2 * wave + pt) * 16 + (I_FAST ? 4 * fq + j : fr);
-                    const int i = it * 16 + (I_FAST ? fr : 4 * fq + j);
-                    if (p < P && i < R) atomicAdd(out + (size_t)p * osp + (size_t)i * osr, alpha * acc[pt][it][j]);
-                }
-            }
-        }
-}
-extern "C" int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
-                                    float alpha, long long M, int P, float p, unsigned long long seed, int site, void* stream) {
-    if (M <= 0 || P <= 0 || (P % 8) || R <= 0 || R > 128 || (ldb % 8) || lds_ < R || osp <= 0 || osr <= 0 || lw_drop_args_bad(p, site))
-        return VT_ERR_BAD_SHAPE;
-    if (((uintptr_t)Big) & 15) return VT_ERR_BAD_ALIGN;
-    if ((((uintptr_t)Small) & 1) || (((uintptr_t)out) & 3)) return VT_ERR_BAD_ALIGN;
-    const long long tiles = (M + 63) / 64;
-    const int pblocks = (P + 127) / 128;
-    long long slices = LWT_BLOCKS / pblocks;
-    if (slices < 1) slices = 1;
-    if (slices > tiles) slices = tiles;
-    const long long tps = (tiles + slices - 1) / slices;
-    slices = (tiles + tps - 1) / tps;
-    if (tps > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-    dim3 grid((unsigned)pblocks, (unsigned)slices);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned thresh = vt_keep_thresh(p);
-    const float alpha_k = alpha * (1.0f / (1.0f - p));
-    if (osr == 1)
-        hipLaunchKernelGGL(lora_wide_tn_drop_kernel<true>, grid, dim3(256), 0, st, (const bf16_t*)Big, ldb, (const bf16_t*)Small, lds_, R,
-                           out, osp, osr, alpha_k, M, P, (int)tps, thresh, seed, site);
-    else
-        hipLaunchKernelGGL(lora_wide_tn_drop_kernel<false>, grid, dim3(256), 0, st, (const bf16_t*)Big, ldb, (const bf16_t*)Small, lds_, R,
-                           out, osp, osr, alpha_k, M, P, (int)tps, thresh, seed, site);
-    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-
-// ---------------- dX[m,k] += 1/(1-p) sum_j keep_j(m,k) sum_i dT[m, j*rp + i] * A[j*r + i, k]   (in place, bf16) ----------------
-// lora_wide_up_add_kernel with an adapter-outer loop: adapter j's MFMA chain runs over the 32-deep steps that touch its columns
-// [j rp, (j+1) rp) with the dT fragments of lanes whose 8 columns belong to another adapter zeroed (rp = 48, 80: an adapter
-// boundary falls inside a step; a lane's 8 columns never straddle one because rp % 16 == 0), its sum is masked -- a lane's 4
-// consecutive columns of a row are one Philox counter -- and added to a running fp32 total.
-__global__ __launch_bounds__(256) void lora_wide_up_add_drop_kernel(bf16_t* dX, int ldx, const bf16_t* dT, int ldt, const bf16_t* A, int lda,
-                                                                   int n, int r, int rp, long long M, int K, unsigned thresh,
-                                                                   float inv_keep, unsigned long long seed, int site0) {
-    extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
-    const int NC = n * rp, NCp = (NC + 31) & ~31, nks = NCp >> 5, LS = NCp + LW_PAD;
-    bf16_t* sAt = lw_smem;                      // [64][LS]
-    const long long row0 = (long long)blockIdx.x * 128 + 32 * wave;
-    const u32x4 zero4 = {0u, 0u, 0u, 0u};
-    const bf16x8 zero8 = __builtin_bit_cast(bf16x8, zero4);
-    bf16x8 dtf[2][LWU_MAXKS];
-#pragma unroll
-    for (int rt = 0; rt < 2; ++rt) {
-        const long long m = row0 + rt * 16 + fr;
-#pragma unroll
-        for (int ks = 0; ks < LWU_MAXKS; ++ks) {
-            u32x4 v = zero4;
-            const int c = ks * 32 + 8 * fq;
-            if (ks < nks && m < M && c < NC) v = *(const u32x4*)(dT + (size_t)m * ldt + c);
-            dtf[rt][ks] = __builtin_bit_cast(bf16x8, v);
-        }
-    }
-    for (int k0 = 0; k0 < K; k0 += 64) {
-        __syncthreads();
-        for (int u = tid; u < NCp * 4; u += 256) {
-            const int pc = u & 7, q = u >> 3;
-            u32x4 rr[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c = 2 * q + h;
-                const int j = c / rp, i = c - j * rp;
-                rr[h] = zero4;
-                if (c < NC && i < r) rr[h] = *(const u32x4*)(A + (size_t)(j * r + i) * lda + k0 + 8 * pc);
-            }
-            lw_store_pair_t(sAt, LS, 8 * pc, q, rr[0], rr[1]);
-        }
-        __syncthreads();
-        f32x4 tot[2][4];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) tot[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int j = 0; j < n; ++j) {
-            const int c_lo = j * rp, c_hi = c_lo + rp;
-            f32x4 acc[2][4];
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < LWU_MAXKS; ++ks) {
-                if (ks < nks && ks * 32 + 32 > c_lo && ks * 32 < c_hi) {
-                    const int c = ks * 32 + 8 * fq;
-                    const bool mine = c >= c_lo && c < c_hi;
-                    const bf16x8 d0 = mine ? dtf[0][ks] : zero8, d1 = mine ? dtf[1][ks] : zero8;
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct) {
-                        const bf16x8 af = lw_frag(sAt + (ct * 16 + fr) * LS + ks * 32 + 8 * fq);
-                        acc[0][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, d0, acc[0][ct], 0, 0, 0);
-                        acc[1][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, d1, acc[1][ct], 0, 0, 0);
-                    }
-                }
-            }
-            // D[row = column k0 + 16ct + 4fq + reg][col = row fr of the row tile]
-            const unsigned long long off = lora_site_offset(site0 + j);
-#pragma unroll
-            for (int rt = 0; rt < 2; ++rt) {
-                const unsigned long long e4 = ((unsigned long long)(row0 + rt * 16 + fr) * K + k0 + 4 * fq) >> 2;
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    unsigned rnd[4];
-                    keep_words4(off + e4 + 4 * ct, seed, rnd);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) tot[rt][ct][q] += rnd[q] >= thresh ? acc[rt][ct][q] : 0.f;
-                }
-            }
-        }
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt) {
-            const long long m = row0 + rt * 16 + fr;
-            if (m < M) {
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    u32x2* px = (u32x2*)(dX + (size_t)m * ldx + k0 + ct * 16 + 4 * fq);
-                    const u32x2 old = *px;
-                    u32x2 o;
-                    o[0] = pack2(__uint_as_float(old[0] << 16) + inv_keep * tot[rt][ct][0],
-                                 __uint_as_float(old[0] & 0xffff0000u) + inv_keep * tot[rt][ct][1]);
-                    o[1] = pack2(__uint_as_float(old[1] << 16) + inv_keep * tot[rt][ct][2],
-                                 __uint_as_float(old[1] & 0xffff0000u) + inv_keep * tot[rt][ct][3]);
-                    *px = o;
-                }
-            }
-        }
-    }
-}
-extern "C" int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
-                                        long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
-    if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
-        n_adapters * rp > 32 * LWU_MAXKS || (ldx % 4) || ldx < K || (ldt % 8) || ldt < n_adapters * rp || (lda % 8) ||
-        lw_drop_args_bad(p, site0))
-        return VT_ERR_BAD_SHAPE;
-    if ((((uintptr_t)dT) | ((uintptr_t)A)) & 15) return VT_ERR_BAD_ALIGN;
-    if (((uintptr_t)dX) & 7) return VT_ERR_BAD_ALIGN;
-    const long long blocks = (M + 127) / 128;
-    if (blocks > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-    const int NCp = (n_adapters * rp + 31) & ~31;
-    const size_t lds = (size_t)64 * (NCp + LW_PAD) * sizeof(bf16_t);
-    hipLaunchKernelGGL(lora_wide_up_add_drop_kernel, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
-                       (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, vt_keep_thresh(p), 1.0f / (1.0f - p), seed,
-                       site0);
-    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}

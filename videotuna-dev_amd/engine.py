@@ -130,13 +130,14 @@ def packed(model) -> SimpleNamespace:
     return P
 
 
-# The rank-r side kernels (csrc/lora.hip) take at most 16 rank columns per call.  The three q / k / v adapters of a fused projection fit one
-# call up to rank 5 (3 r <= 16: the shipped recipes, r = 4); above that (r <= 16) each adapter gets its own call on its r columns.
-# Ranks 17..128 (st.wide) take the MFMA kernels of csrc/lora_wide.hip: every adapter of a projection in one pass over the activation.
+# The rank-side products of the two adapted projections of a block -- "qkv": the three adapters of the fused q | k | v projection,
+# "out": the one of to_out.0 -- each issued from one place: _lora_down, _lora_da, _lora_dx.  They choose the layout (ranks <= 16: the
+# narrow kernels of csrc/lora.hip, ranks 17..128 (st.wide): the MFMA kernels of csrc/lora_wide.hip, every adapter of a projection in one
+# pass over the activation) and whether the dropped kernels run.
 #
 # lora_dropout: ``drop`` is None or (p, seed) of the forward in flight; the adapter sites of layer i are 4 i + {0, 1, 2, 3} for
-# to_q, to_k, to_v, to_out.0 and every site has its own keep mask.  With drop the _drop siblings run (same passes over the activation, the
-# mask recomputed in the kernel); without it the calls below are exactly the ones made before lora_dropout existed.
+# to_q, to_k, to_v, to_out.0 and every site has its own keep mask.  With drop the dropped kernels run (same passes over the activation,
+# the mask recomputed in the kernel); without it the calls are exactly the ones made before lora_dropout existed.
 def lora_dropout_seed(model):
     """(p, seed) for one training forward of a model whose adapters have lora_dropout > 0, else None.  model.lora_dropout_seed pins the
     seed; None draws a fresh one per forward from torch's CPU generator (every rank of a data-parallel job draws its own)."""
@@ -150,79 +151,88 @@ def lora_dropout_seed(model):
     return float(st.p), int(seed)
 
 
-def _lora_down_qkv_drop(x1, st, i, d, drop):
-    r, (p, seed) = st.r, drop
-    a = st.a_qkv(st.flat_bf16, i)
+def _lora_proj(st, i, proj, buf):
+    """(adapters, their stacked A rows [n r, d] in buf, K-extension width, site of the first adapter) of projection ``proj`` of layer i"""
+    if proj == "qkv":
+        return 3, st.a_qkv(buf, i), st.ext_qkv, 4 * i
+    return 1, st.a_out(buf, i), st.ext_o, 4 * i + 3
+
+
+def _narrow_calls(n, r):
+    """(first adapter, adapters) of each call of a narrow rank-side kernel.  These take at most 16 rank columns, so the adapters of a
+    fused projection share one call up to 3 r <= 16 (the shipped recipes, r = 4) and get a call each on their r columns above that."""
+    return [(0, n)] if n * r <= 16 else [(j, 1) for j in range(n)]
+
+
+def _lora_down(st, i, proj, x, d, drop=None):
+    """T = x A^T (drop: of x under each adapter's mask) into the K-extension columns x[:, d:], zeros in the columns no adapter owns"""
+    n, a, ext, site = _lora_proj(st, i, proj, st.flat_bf16)
+    r, rp = st.r, st.rp
     if st.wide:
-        if ops.lora_down_wide_drop_fits(3, st.rp):
-            ops.lora_down_wide_drop(x1, a, 3, r, st.rp, st.ext_qkv, x1[:, d:], d, p, seed, 4 * i)
-            return
-        for j in range(3):      # one masked copy of the X block per adapter does not fit the LDS: a call per adapter on its rp columns
-            ops.lora_down_wide_drop(x1, a[j * r:(j + 1) * r], 1, r, st.rp, st.rp if j < 2 else st.ext_qkv - 2 * st.rp,
-                                    x1[:, d + j * st.rp:], d, p, seed, 4 * i + j)
+        if drop is None:
+            ops.lora_down_wide(x, a, n, r, rp, ext, x[:, d:], d)
+        elif ops.lora_down_wide_drop_fits(n, rp):
+            ops.lora_down_wide_drop(x, a, n, r, rp, ext, x[:, d:], d, *drop, site)
+        else:
+            # one masked copy of the X block per adapter does not fit the LDS (3 adapters, rp > 80): a call per adapter on its rp
+            # columns, the last one zeroes the rest of the extension
+            for j in range(n):
+                ops.lora_down_wide_drop(x, a[j * r:(j + 1) * r], 1, r, rp, rp if j < n - 1 else ext - j * rp, x[:, d + j * rp:], d,
+                                        *drop, site + j)
         return
-    if 3 * r <= 16:
-        ops.lora_down_drop(x1, a, 3 * r, 3, x1[:, d:], d, p, seed, 4 * i)
-        return
-    for j in range(3):
-        ops.lora_down_drop(x1, a[j * r:(j + 1) * r], r, 1, x1[:, d + j * r:], d, p, seed, 4 * i + j,
-                           zero_cols=(EXT - 2 * r - 16) if j == 2 else 0)
+    for j, nj in _narrow_calls(n, r):
+        # a call writes 16 columns from j r (zeros past its rows; the next call overwrites them), the last one zeroes the rest
+        zc = EXT - 16 - j * r if j + nj == n else 0
+        if drop is None:
+            ops.lora_down(x, a[j * r:(j + nj) * r], nj * r, x[:, d + j * r:], d, zero_cols=zc)
+        else:
+            ops.lora_down_drop(x, a[j * r:(j + nj) * r], nj * r, nj, x[:, d + j * r:], d, *drop, site + j, zero_cols=zc)
 
 
-def _lora_qkv_input_grads_drop(x1, dx1, st, i, d, need_dx, drop):
-    r, (p, seed) = st.r, drop
-    if st.wide:
-        for j in range(3):
-            ops.lora_tn_wide_drop(x1, dx1[:, d + j * st.rp:], r, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d, p, seed, 4 * i + j)
-        if need_dx:
-            ops.lora_up_add_wide_drop(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3, r, st.rp, d, p, seed, 4 * i)
-        return
-    if 3 * r <= 16:
-        ops.skinny_tn_drop(x1, dx1[:, d:], 3 * r, 3, st.a_qkv(st.grad, i), 1, d, 1.0, d, p, seed, 4 * i)
-        if need_dx:
-            ops.lora_up_add_drop(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3 * r, 3, d, p, seed, 4 * i)
-        return
-    for j in range(3):
-        ops.skinny_tn_drop(x1, dx1[:, d + j * r:], r, 1, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d, p, seed, 4 * i + j)
-        if need_dx:
-            ops.lora_up_add_drop(dx1, dx1[:, d + j * r:], st.a_qkv(st.flat_bf16, i)[j * r:(j + 1) * r], r, 1, d, p, seed, 4 * i + j)
-
-
-def _lora_down_qkv(x1, st, i, d, drop=None):
-    if drop is not None:
-        return _lora_down_qkv_drop(x1, st, i, d, drop)
+def _lora_da(st, i, proj, x, dxe, d, drop=None):
+    """dA += dT^T x (drop: x under each adapter's mask); x: the projection's input, dT: the extension columns of dxe [M, d + ext]"""
+    n, ga, _, site = _lora_proj(st, i, proj, st.grad)
     r = st.r
-    a = st.a_qkv(st.flat_bf16, i)
+    for j, nj in ([(j, 1) for j in range(n)] if st.wide else _narrow_calls(n, r)):          # lora_tn_wide: one adapter per call
+        dt, g = dxe[:, d + j * st.rp:], ga[j * r:(j + nj) * r]
+        if st.wide and drop is None:
+            ops.lora_tn_wide(x, dt, r, g, 1, d, 1.0, d)
+        elif st.wide:
+            ops.lora_tn_wide_drop(x, dt, r, g, 1, d, 1.0, d, *drop, site + j)
+        elif drop is None:
+            ops.skinny_tn(x, dt, nj * r, g, 1, d, 1.0, d)
+        else:
+            ops.skinny_tn_drop(x, dt, nj * r, nj, g, 1, d, 1.0, d, *drop, site + j)
+
+
+def _lora_dx(st, i, proj, dxe, d, drop=None):
+    """dxe[:, :d] += dT A (drop: each adapter's term under its mask), dT = the extension columns of dxe"""
+    n, a, _, site = _lora_proj(st, i, proj, st.flat_bf16)
+    r = st.r
     if st.wide:
-        ops.lora_down_wide(x1, a, 3, r, st.rp, st.ext_qkv, x1[:, d:], d)
+        if drop is None:
+            ops.lora_up_add_wide(dxe, dxe[:, d:], a, n, r, st.rp, d)
+        else:
+            ops.lora_up_add_wide_drop(dxe, dxe[:, d:], a, n, r, st.rp, d, *drop, site)
         return
-    if 3 * r <= 16:
-        ops.lora_down(x1, a, 3 * r, x1[:, d:], d)
-        return
-    for j in range(3):          # call j writes 16 columns from j r (zeros past its r; the next call overwrites them), the last one zeroes the rest
-        ops.lora_down(x1, a[j * r:(j + 1) * r], r, x1[:, d + j * r:], d, zero_cols=(EXT - 2 * r - 16) if j == 2 else 0)
+    for j, nj in _narrow_calls(n, r):
+        if drop is None:
+            ops.lora_up_add(dxe, dxe[:, d + j * r:], a[j * r:(j + nj) * r], nj * r, d)
+        else:
+            ops.lora_up_add_drop(dxe, dxe[:, d + j * r:], a[j * r:(j + nj) * r], nj * r, nj, d, *drop, site + j)
+
+
+# Aliases that only tests/test_side_kernels_gpu.py calls; they go when its call sites move to the helpers above.
+def _lora_down_qkv(x1, st, i, d, drop=None):
+    """the qkv down-projection by its earlier name"""
+    _lora_down(st, i, "qkv", x1, d, drop)
 
 
 def _lora_qkv_input_grads(x1, dx1, st, i, d, need_dx=True, drop=None):
-    """dA_qkv += dT^T x1 and (need_dx) dx1 += dT A_qkv for the fused projection's three adapters (dT = the extension columns of dx1)"""
-    if drop is not None:
-        return _lora_qkv_input_grads_drop(x1, dx1, st, i, d, need_dx, drop)
-    r = st.r
-    if st.wide:
-        for j in range(3):
-            ops.lora_tn_wide(x1, dx1[:, d + j * st.rp:], r, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d)
-        if need_dx:
-            ops.lora_up_add_wide(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3, r, st.rp, d)
-        return
-    if 3 * r <= 16:
-        ops.skinny_tn(x1, dx1[:, d:], 3 * r, st.a_qkv(st.grad, i), 1, d, 1.0, d)
-        if need_dx:
-            ops.lora_up_add(dx1, dx1[:, d:], st.a_qkv(st.flat_bf16, i), 3 * r, d)
-        return
-    for j in range(3):
-        ops.skinny_tn(x1, dx1[:, d + j * r:], r, st.a_qkv(st.grad, i)[j * r:(j + 1) * r], 1, d, 1.0, d)
-        if need_dx:
-            ops.lora_up_add(dx1, dx1[:, d + j * r:], st.a_qkv(st.flat_bf16, i)[j * r:(j + 1) * r], r, d)
+    """dA_qkv += dT^T x1 and (need_dx) dx1 += dT A_qkv by their earlier name (see _lora_down_qkv)"""
+    _lora_da(st, i, "qkv", x1, dx1, d, drop)
+    if need_dx:
+        _lora_dx(st, i, "qkv", dx1, d, drop)
 
 
 def _mod(mod: torch.Tensor, idx: int, d: int):
@@ -284,7 +294,7 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
     ops.ln_modulate_fwd(h, x1, Lw.n1g, Lw.n1b, (m1.shift_txt, m1.scale_txt, m1.shift_vid, m1.scale_vid, m1.bs),
                         a.mean1, a.rstd1, d, S, St, c.norm_eps)
     if st is not None:
-        _lora_down_qkv(x1, st, i, d, drop)
+        _lora_down(st, i, "qkv", x1, d, drop)
     qkv = E(M, 3 * d)
     ops.gemm(x1, Lw.w_qkv, qkv, Lw.b_qkv, K=KEq)
     qkh = E(M, 2 * d)
@@ -294,14 +304,8 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
     lse = E(B, H, S, dt=torch.float32)
     qk3, qkv3, o3 = qkh.view(B, S, 2 * d), qkv.view(B, S, 3 * d), o.view(B, S, d + eo)
     ops.attn_fwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], o3[:, :, :d], lse, B, H, S, q_prescaled=True)
-    if st is not None and drop is not None and st.wide:
-        ops.lora_down_wide_drop(o, st.a_out(st.flat_bf16, i), 1, st.r, st.rp, eo, o[:, d:], d, drop[0], drop[1], 4 * i + 3)
-    elif st is not None and drop is not None:
-        ops.lora_down_drop(o, st.a_out(st.flat_bf16, i), st.r, 1, o[:, d:], d, drop[0], drop[1], 4 * i + 3)
-    elif st is not None and st.wide:
-        ops.lora_down_wide(o, st.a_out(st.flat_bf16, i), 1, st.r, st.rp, eo, o[:, d:], d)
-    elif st is not None:
-        ops.lora_down(o, st.a_out(st.flat_bf16, i), st.r, o[:, d:], d)
+    if st is not None:
+        _lora_down(st, i, "out", o, d, drop)
     h1 = E(M, d)
     ao = E(M, d) if (save and ft is not None) else None           # branch output before gating (gate gradient)
     ops.gemm(o, Lw.w_o, h1, Lw.b_o, epilogue=EPI_GATED_RES, residual=h, gate_txt=m1.gate_txt, gate_vid=m1.gate_vid,
@@ -414,8 +418,7 @@ def run_backward(model, ctx, dout: torch.Tensor):
     dev = dout.device
     r, rp = st.r, st.rp
     eq, eo = st.ext_qkv, st.ext_o
-    wide = st.wide
-    tn = ops.lora_tn_wide if wide else ops.skinny_tn          # rank gradients: MFMA kernel above rank 16
+    tn = ops.lora_tn_wide if st.wide else ops.skinny_tn       # dB products (they read the saved T: no mask): MFMA kernel above rank 16
     E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
     mod = ctx.mod
     drop = ctx.lora_drop          # (p, seed) of this forward's lora_dropout masks, or None
@@ -459,19 +462,8 @@ def run_backward(model, ctx, dout: torch.Tensor):
         ops.gate_mul(dh1, tg, m1.gate_txt, m1.gate_vid, m1.bs, d, S, St)
         ops.gemm(tg, Lw.w_o_t, dO, None)                                  # [M, d+ext_o]: dO | dT2
         tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o (reads the saved T: no mask)
-        ao, a_o, site = st.a_out(st.grad, i), st.a_out(st.flat_bf16, i), 4 * i + 3
-        if drop is None:
-            tn(a.o, dO[:, d:], r, ao, 1, d, 1.0, d)                                 # dA_o
-            if wide:
-                ops.lora_up_add_wide(dO, dO[:, d:], a_o, 1, r, rp, d)
-            else:
-                ops.lora_up_add(dO, dO[:, d:], a_o, r, d)
-        elif wide:                                                                  # the same two products under the masks of to_out.0's site
-            ops.lora_tn_wide_drop(a.o, dO[:, d:], r, ao, 1, d, 1.0, d, drop[0], drop[1], site)
-            ops.lora_up_add_wide_drop(dO, dO[:, d:], a_o, 1, r, rp, d, drop[0], drop[1], site)
-        else:
-            ops.skinny_tn_drop(a.o, dO[:, d:], r, 1, ao, 1, d, 1.0, d, drop[0], drop[1], site)
-            ops.lora_up_add_drop(dO, dO[:, d:], a_o, r, 1, d, drop[0], drop[1], site)
+        _lora_da(st, i, "out", a.o, dO, d, drop)                                    # dA_o
+        _lora_dx(st, i, "out", dO, d, drop)
         dq.zero_()
         qk3, qkv3 = a.qkh.view(B, S, 2 * d), a.qkv.view(B, S, 3 * d)
         ops.attn_bwd(qk3[:, :, :d], qk3[:, :, d:], qkv3[:, :, 2 * d:], a.o.view(B, S, d + eo)[:, :, :d],
@@ -484,8 +476,9 @@ def run_backward(model, ctx, dout: torch.Tensor):
             ops.gemm(dqkv, Lw.w_qkv_t[d:], dx1[:, d:], None)              # the first block's input (frozen embeddings) needs no gradient: dT1 only
         for j in range(3):
             tn(dqkv[:, j * d:], a.x1[:, d + j * rp:], r, st.b_qkv(st.grad, i)[j * d:], r, 1, st.scaling, d)
-        _lora_qkv_input_grads(a.x1, dx1, st, i, d, need_dx=i > 0, drop=drop)
+        _lora_da(st, i, "qkv", a.x1, dx1, d, drop)
         if i > 0:
+            _lora_dx(st, i, "qkv", dx1, d, drop)
             ops.ln_modulate_bwd(dx1, a.h_in, a.mean1, a.rstd1, Lw.n1g, (m1.scale_txt, m1.scale_vid, m1.bs), dh1, dh_in,
                                 d, S, St)
             dh, dh_in = dh_in, dh

@@ -649,17 +649,22 @@ def lora_down(x, a, R: int, t_out, K: int, zero_cols: int = 48):
 _SKINNY_WS = {}
 
 
+def _skinny_ws(lib, big, P: int, use_workspace: bool):
+    """the per-device workspace of the two-stage skinny_tn reduction (None: fp32 atomics), reused across calls (stream-ordered)"""
+    if not use_workspace:
+        return None
+    need = lib.vt_skinny_tn_workspace_bytes(P) // 4
+    key = big.device
+    if key not in _SKINNY_WS or _SKINNY_WS[key].numel() < need:
+        _SKINNY_WS[key] = torch.empty(need, dtype=torch.float32, device=big.device)
+    return _SKINNY_WS[key]
+
+
 def skinny_tn(big, small, R: int, out, osp: int, osr: int, alpha: float, P: int, use_workspace: bool = False):
     """out[p*osp + r*osr] += alpha * sum_m big[m,p] * small[m,r]; fp32 atomics by default; use_workspace=True selects the two-stage, bitwise-reproducible reduction (measured slightly slower)."""
     _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
     lib = load_library()
-    ws = None
-    if use_workspace:
-        need = lib.vt_skinny_tn_workspace_bytes(P) // 4
-        key = big.device
-        if key not in _SKINNY_WS or _SKINNY_WS[key].numel() < need:
-            _SKINNY_WS[key] = torch.empty(need, dtype=torch.float32, device=big.device)     # reused across calls (stream-ordered)
-        ws = _SKINNY_WS[key]
+    ws = _skinny_ws(lib, big, P, use_workspace)
     check(lib.vt_skinny_tn(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, out.data_ptr(),
                            osp, osr, alpha, big.shape[0], P, _p(ws), _stream()), "vt_skinny_tn")
 
@@ -731,13 +736,7 @@ def skinny_tn_drop(big, small, R: int, n_adapters: int, out, osp: int, osr: int,
     """skinny_tn with big (the logical [M, P] adapter input) masked per group of R / n_adapters columns of small, times 1/(1-p)."""
     _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
     lib = load_library()
-    ws = None
-    if use_workspace:
-        need = lib.vt_skinny_tn_workspace_bytes(P) // 4
-        key = big.device
-        if key not in _SKINNY_WS or _SKINNY_WS[key].numel() < need:
-            _SKINNY_WS[key] = torch.empty(need, dtype=torch.float32, device=big.device)
-        ws = _SKINNY_WS[key]
+    ws = _skinny_ws(lib, big, P, use_workspace)
     check(lib.vt_skinny_tn_drop(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, n_adapters, out.data_ptr(),
                                 osp, osr, alpha, big.shape[0], P, _p(ws), float(p), int(seed) & _U64, site0, _stream()),
           "vt_skinny_tn_drop")
