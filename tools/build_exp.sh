@@ -1,6 +1,7 @@
 #!/bin/bash
 # Experimental: compile variants of csrc/attn_bwd.hip under suffixed symbols into libvt355_exp.so (A/B timing in one process with
-# tools/kbench_variants.py / tools/kbench_stamp.py).  Not part of build().   usage: build_exp.sh suffix="-Dflags ..." ...
+# tools/kbench_variants.py).  Not part of build().   usage: build_exp.sh suffix="-Dflags ..." ...
+# e.g.  build_exp.sh _same="" _spin0="-DCH_SPIN_LIMIT=0"   (_same="": the unchanged source, the control of an A/B)
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/../videotuna-dev_amd/csrc" && pwd)"
 OUT="$HERE/../libvt355_exp.so"

@@ -16,7 +16,7 @@ def setter(l, suf):
 args = sys.argv[1:]
 B = int(args.pop(0)) if args and args[0].isdigit() else 1
 variants = {"shipped:1": (lib.vt_attn_bwd_hd64, setter(lib, ""), 1), "shipped:8": (lib.vt_attn_bwd_hd64, setter(lib, ""), 8)}
-for a in args or ["_st0_ld16:8", "_st16_ld16:8", "_st0_ld17:8"]:
+for a in args or ["_same:8"]:      # default: the control build of tools/build_variants.sh (the unchanged source under a second suffix)
     suf, L = (a.split(":") + ["8"])[:2]
     if suf == "shipped":
         variants[a] = (lib.vt_attn_bwd_hd64, setter(lib, ""), int(L))

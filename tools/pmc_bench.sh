@@ -6,9 +6,11 @@ export TMPDIR=/tmp
 OUT=${1:-gpurun_out/pmc_bench}
 mkdir -p $OUT
 CMD="python3 bench.py --gpus 1 --steps 1 --warmup 1 --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > $OUT/write.log 2>&1
+# every pass under a limit of its own, so that a stuck pass ends the script (set -e): the plain command takes 12 s of wall time on an MI355X;
+# 10 x that for the trace pass, 25 x for a counter pass (the profiler reads the counters around every dispatch)
+timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > $OUT/write.log 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, json, collections
 out = sys.argv[1]

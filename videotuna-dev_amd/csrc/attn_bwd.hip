@@ -4,134 +4,69 @@
 // videotuna/models/cogvideo_hf/cogvideo_pl.py:865-871 (loss.backward() under PL).
 // P is recomputed from Q, K and the forward's log2-domain LSE; the S x S matrices never touch HBM.
 //
-// Structure (shipped, VT_W8=1): one workgroup = 8 waves (two per SIMD, <= 256 registers each, all in VGPRs) = 256 keys
-// of one (batch, head); wave w owns keys [32w, 32w+32) and keeps dK^T and dV^T for them in 64 accumulator registers
-// while the workgroup sweeps all queries in steps of 64 rows.  (VT_W8=0: 4 waves x 64 keys, one per SIMD, all 512
-// registers, software-pipelined in program order -- the first version; with one wave per SIMD MFMA and VALU were busy
-// at the same time only 13 % of the cycles, and half of its VALU instructions were AGPR<->VGPR moves.)
-//   * S = Q K^T and dP = dO V^T are computed with the KEY on the MFMA lane (K / V fragments live in
-//     registers for the whole key block), so the fp32 tiles P and dS are, after bf16 packing, directly
-//     the B operands of dV^T += dO^T P and dK^T += Q^T dS (A operands = transposed LDS reads of the
-//     dO / Q tiles, ds_read_b64_tr_b16).
+// This file holds the shipped kernel only.  The variants it was measured against (a body of four waves, a 32 x 32 S phase, other dQ
+// shapes, timing-only ablations, the step timeline build) are recorded in exp/README.md, "Variants removed from attn_bwd.hip /
+// attn_fwd.hip", with the commit at which their source can still be read and built.
+//
+// Workgroup.  8 waves (two per SIMD, <= 256 registers each, all in VGPRs) = 256 keys of one (batch, head); wave w owns keys
+// [32w, 32w+32) and keeps dK^T and dV^T for them in 64 accumulator registers while the workgroup sweeps all queries in steps
+// of 64 rows.  Two waves per SIMD so that one wave's exp2 / packing runs under the other's MFMAs.
+//
+// S phase (all eight waves, v_mfma_f32_16x16x32_bf16 on 16 x 16 tiles: same cycles per flop as 32x32x16, but the chip holds a
+// higher clock on this shape under load).
+//   * S = Q K^T and dP = dO V^T are computed with the KEY on the MFMA lane (K / V fragments live in registers for the whole
+//     key block), so the fp32 tiles P and dS are, after bf16 packing, directly the B operands of dV^T += dO^T P and
+//     dK^T += Q^T dS (A operands = transposed LDS reads of the dO / Q tiles, ds_read_b64_tr_b16).
 //   * -lse2/c and -delta (delta = rowsum(dO*O)) are loaded as the initial accumulators of S'' and dP'.
-//   * only dS crosses LDS: every wave writes its [32 keys][64 q] part of a [256][64] image; after
-//     one barrier waves 0..3 each compute one 32x32 tile of dQ (its (q-half, d-half)) over all 256 keys
-//     and add it to a fp32 dQ buffer with buffer_atomic_add_f32 (one register of a 32x32 accumulator = two full
-//     128-B row segments) -- or hand it to the next key block (chains, below) -- while waves 4..7 already start
-//     the next step (the dS image is double-buffered).
-// All four LDS images (K block, dS, Q tile, dO tile) have 128-B rows and share one XOR swizzle that
-// is conflict-free for both the row reads (ds_read_b128) and the transposed reads.
+//   * The issue order is software-pipelined and pinned by sched_barrier fences (FENCE): all operand reads of a segment are in
+//     flight before its MFMAs, the next segment's reads are issued between the current segment's MFMAs.  Operand rings: PF_ROWN
+//     Q / dO row operands, PF_TRN transposed dO / Q pairs.  (The compiler's own order issues every operand read right before
+//     the MFMA that needs it: one LDS round trip exposed per k-step.)
 //
-// Scheduling.  The kernel is PERSISTENT: one workgroup per CU ("slot"; 145 KiB of LDS allow exactly one), slot =
-// (XCD, index inside the XCD) under round-robin dispatch, each slot sweeping the key blocks slot, slot + G, slot + 2G ...
-// Consecutive key blocks of a head therefore run side by side on one XCD and stream the same Q / dO tiles through its
-// L2 at the same time (B=2, S=17776, H=30: 18.05 ms with one workgroup per key block -> 17.35 ms).
+// dQ phase (waves 0..3, v_mfma_f32_32x32x16_bf16).  Only dS crosses LDS: every wave writes its [32 keys][64 q] part of a
+// [256][64] image; after one barrier waves 0..3 each compute one 32 x 32 tile of dQ (its (q-half, d-half)) over all 256 keys,
+// DQ_RING k-steps of operands in flight, and add it to a fp32 dQ buffer with buffer_atomic_add_f32 (one register of a 32 x 32
+// accumulator = two full 128-B row segments) -- or hand it to the next key block (chains, below) -- while waves 4..7 already
+// start the next step (the dS image is double-buffered).
 //
-// dQ hand-off chains.  fp32 atomics execute memory-side at ~340 G lane-adds/s for the whole chip whatever the
-// locality or scope (tools/atomic_bench.hip: 1.36 TB/s of payload from 36 CUs up, the same from 256); adding every
-// key block's [S x 64] partial atomically is 7 ms of atomic-unit time per sample at S = 17776, and the kernel without
-// its atomics (results wrong, timing only) runs in 12.7 ms instead of 17.35.  With chain_len = L > 1, runs of up to L
-// consecutive key blocks of a head on consecutive slots of one XCD form a chain in every generation: block j hands its
-// running 64x64 fp32 dQ tile of every step to block j+1 through a ring of CH_R tiles in global memory (write-through
-// stores, cache-bypassing LDS-DMA loads, one ready and one consumed counter per wave, all counted in absolute steps
-// so nothing is reset between generations), block j+1 uses the tile as the initial accumulator of its own dQ MFMAs,
-// and only the last block of a chain issues atomics: ~L times fewer.  Counter loads and tile loads are issued a full
-// step before they are needed (one wave per SIMD: nothing hides a miss), so a consumer runs ~3 steps behind its
-// producer.  Every wait is bounded (CH_SPIN_LIMIT) and gives up with an error word instead of hanging.
-// What it buys (r01, B=2): L=2 16.6 ms, L=4 16.8, L=8 17.9-20 -- far from the 12.7 + 4.6/L the atomic count alone would
-// give, because the hand-off is itself vector-memory work on a one-wave-per-SIMD kernel: with all waits and all
-// atomics removed, the 4 tile stores cost +1.4 ms, the 4 DMA loads +0.8, counters and LDS reads +0.9 (vs 4.6 ms for the
-// 16 atomics they replace), and lock-stepping L blocks adds their stalls.  L = 2 is the default; L2-resident rings
-// (plain stores + agent-scope loads, 16.1 ms) were not adopted: they are only correct if chain neighbours really share
-// an XCD.  The roles are template parameters: with runtime flags the compiler's register allocation made the
-// atomic-only path of the same binary 26 % slower.
+// LDS images, 128-B rows (145 KiB with the chain stage: one workgroup per CU).
+//   * K block [256 keys][64 d] (B operand of dQ): 16-byte chunks XOR swz_f(row), conflict-free for the transposed reads.
+//   * dS [256 keys][64 q] x 2 buffers: row = key, 8 bytes = four consecutive queries, 8-byte position = (query / 4) ^ swz4(key
+//     row).  Swizzled at 8-byte granularity with four row bits so that the S phase's ds_write_b64 of a 16-lane group hit 16
+//     distinct positions and the dQ phase's transposed reads stay conflict-free.
+//   * Q and dO tiles [64 q][64 d] x 2 buffers: 16-byte chunks XOR (row & 6), conflict-free for the 16-row ds_read_b128
+//     fragments AND the transposed reads of a 16 x 16 x 32 operand.
+//   * row constants: 2 buffers x {-lse2/c, -delta} x 64 fp32.
+//
+// Staging.  Waves 4..7 stage the Q / dO tiles by LDS-DMA straight into the buffer the barrier before last freed (no staging
+// registers, no ds_write of the tile; waves 0..3, which carry the dQ phase, stage nothing).  Everything a step fetches from
+// memory is issued right after the previous step's barrier, before that step's dQ atomics.
+//
+// Scheduling.  The kernel is PERSISTENT: one workgroup per CU ("slot"), slot = (XCD, index inside the XCD) under round-robin
+// dispatch, each slot sweeping the key blocks slot, slot + G, slot + 2G ...  Consecutive key blocks of a head therefore run
+// side by side on one XCD and stream the same Q / dO tiles through its L2 at the same time.
+//
+// dQ hand-off chains.  fp32 atomics execute memory-side at ~340 G lane-adds/s for the whole chip whatever the locality or
+// scope (tools/atomic_bench.hip); adding every key block's [S x 64] partial atomically is 7 ms of atomic-unit time per sample
+// at S = 17776.  With chain_len = L > 1 (default 3), runs of up to L consecutive key blocks of a head on consecutive slots of
+// one XCD form a chain in every generation: block j hands its running 64x64 fp32 dQ tile of every step to block j+1 through a
+// ring of CH_R tiles in global memory (one ready and one consumed counter per wave, all counted in absolute steps so nothing is
+// reset between generations), block j+1 uses the tile as the initial accumulator of its own dQ MFMAs, and only the last block
+// of a chain issues atomics: ~L times fewer.  Chain neighbours that share an XCD (checked at run time through XCC_ID) keep the
+// ring in that XCD's L2: plain stores, agent-scope loads; any other pair goes through memory with write-through stores and
+// system-scope loads.  Tiles arrive by LDS-DMA into a stage of their own; counter loads and tile loads are issued a full step
+// before they are needed.  Every wait is bounded (CH_SPIN_LIMIT) and gives up with an error word instead of hanging.
+// The roles are template parameters (ROLE: bit 0 = has a chain predecessor and takes its running dQ tiles, bit 1 = has a
+// successor and hands its tiles on instead of adding them atomically): with runtime flags the compiler's register allocation
+// made the atomic-only path of the same binary 26 % slower.  vt_attn_bwd_set_chain(1, ..) gives the atomics-only launch.
 #include "common.h"
 #include <cstdlib>
 
-// Experiment hooks: the same source can be compiled a second time under another symbol suffix / variant flags
-// (tools/build_variants.sh) so kernel variants are A/B-timed in ONE process.  The shipped build defines neither.
+// Build hooks.  VT_SUFFIX: the same source compiled a second time under another symbol suffix (libvt355_test.so: _tmo with
+// CH_SPIN_LIMIT=0; tools/build_exp.sh: A/B timing of two builds in ONE process).  The shipped build defines none of them.
 #ifndef VT_SUFFIX
 #define VT_SUFFIX
 #endif
-#ifndef VT_PIPE
-#define VT_PIPE 1
-#endif
-#ifndef VT_DRAIN
-#define VT_DRAIN 0    // 1 = spread each step's 16 dQ atomics over the next step's MFMA slots (measured SLOWER: 10.5 vs 8.9 ms)
-#endif
-#ifndef VT_DQSHIFT
-#define VT_DQSHIFT 0   // 1 = the dQ MFMAs of step t-1 run inside step t VALU-bound slots (measured SLOWER: 11.5 vs 8.9 ms, the atomics then leave every wave in one burst right after the barrier)
-#endif
-#ifndef VT_STATMFMA
-#define VT_STATMFMA 0 // 1 = the row constants (-lse2/c, -delta, key mask) enter S'' / dP' through one extra MFMA per tile (three
-#endif                // bf16 terms = 24 bits) instead of 32 v_accvgpr_write per tile.  Parity-clean and 26 % fewer VALU instructions
-                      // per step (480 -> 356), but measured SLOWER: 16.0 vs 15.8 ms with pairs, 20.4 vs 17.35 atomics-only (B=2)
-#ifndef VT_W8
-#define VT_W8 1       // 1 = eight waves per workgroup (32 keys each, two per SIMD), 0 = four (64 keys each, one per SIMD, software-
-                      // pipelined): r01, B=2, pairs: 14.3 vs 15.9 ms; without any atomics 11.5 vs 13.3 ms
-#endif
-#define BWD_THREADS (VT_W8 ? 512 : 256)
-#ifndef VT_DQ16
-#define VT_DQ16 0     // 1 = eight-wave body computes dQ as sixteen 16x16 tiles over ALL waves instead of four 32x32 tiles on waves
-                      // 0..3.  Parity-clean but measured SLOWER (B=2): pairs 16.3-17.6 vs 14.6 ms, atomics only 17.0 vs 16.8 -- eight
-                      // waves then issue hand-off stores / DMA / counters instead of four
-#endif
-#ifndef VT_CHAIN
-#define VT_CHAIN 1    // 0 = compile the dQ hand-off chains out (persistent scheduling only)
-#endif
-#ifndef VT_ATOM_AUX
-#define VT_ATOM_AUX 0  // cache-policy bits of the dQ atomics of the eight-wave body (2 = nt, 16 = sc1): measured, no effect
-#endif
-#ifndef VT_DQPRIO
-#define VT_DQPRIO 0   // 1 = waves 0..3 raise their issue priority for the dQ phase (s_setprio)
-#endif
-#ifndef VT_ABL
-#define VT_ABL 0      // timing-only ablations (results are WRONG): 1 = no dQ phase, 2 = no dQ atomics, 3 = no exp2, 4 = no dS image write, 5 = no row-constant reads, 6 = no transposed Q / dO reads, 7 = 5 + 6 (5..7: eight-wave body)
-#endif
-#ifndef VT_PF
-#define VT_PF 1       // 1 = software-pipelined S phase with the issue order pinned by sched_barrier fences: all operand reads of a segment are
-#endif                // in flight before its MFMAs, the next segment's reads are issued between the current segment's MFMAs
-#define FENCE() __builtin_amdgcn_sched_barrier(0)
-#ifndef DQ_RING
-#define DQ_RING 2
-#endif
-#ifndef VT_DQ2
-#define VT_DQ2 0
-#endif
-#ifndef VT_DMA
-#define VT_DMA (VT_PF && VT_W8 && !VT_DQ16)   // 1 = waves 4..7 stage the Q / dO tiles by LDS-DMA straight into the buffer the barrier before last freed (no
-#endif                                        // staging registers, no ds_write of the tile; waves 0..3, which carry the dQ phase, stage nothing)
-#ifndef VT_M16
-#define VT_M16 (VT_DMA && !VT_STAMP && !VT_STATMFMA && !PF_R0 && !VT_DMA_LATE && !VT_ABL)      // 1 (eight-wave body with VT_PF + VT_DMA only; shipped) = the four products of the S phase (S, dP, dV, dK) are issued as
-#endif                // v_mfma_f32_16x16x32_bf16 on 16 x 16 tiles instead of v_mfma_f32_32x32x16_bf16: same cycles per flop, but the chip holds a
-                      // higher clock on that shape under load (gemm_big_bf16.hip GB_MFMA16).  The Q / dO tile image then uses the swizzle
-                      // row & 6 (conflict-free for the 16-row ds_read_b128 fragments AND the transposed reads of a 16 x 16 x 32 operand);
-                      // the dS image keeps its format, so the dQ phase is untouched.  Same box, B=1: 6.58-6.77 against 6.90-6.95 ms (-4.7 %).
-                      // The instrumented / ablation builds (VT_STAMP, VT_STATMFMA, VT_ABL, PF_R0, VT_DMA_LATE) exist for the 32 x 32 body only: -DVT_M16=0.
-#ifndef VT_DS4
-#define VT_DS4 (VT_M16 && !VT_DQM16)   // 1 = the dS image is swizzled at 8-byte granularity with four row bits (swz4): the S phase's ds_write_b64 of a 16-lane
-#endif                             // group then hit 16 distinct 8-byte positions (with the 16-byte swizzle two lanes shared every position: 256 conflict
-                                   // cycles per workgroup-step, SQ_LDS_BANK_CONFLICT) and the dQ phase's transposed reads stay conflict-free
-#ifndef VT_DQM16
-#define VT_DQM16 0        // 1 = the dQ product of waves 0..3 as four 16 x 16 tiles of v_mfma_f32_16x16x32_bf16 per wave (eight 32-key k-steps) instead of one
-#endif                  // 32 x 32 tile of v_mfma_f32_32x32x16_bf16 (sixteen 16-key k-steps); the hand-off tiles carry the registers as they are.  Parity-clean
-                        // but measured SLOWER on the same box (7.09 vs 6.58-6.69 ms, B=1) -- also with the registers of the two d-tiles exchanged by
-                        // v_permlane16_swap so that every atomic covers 2 rows x 128 B again (7.15-7.32 vs 6.86-6.88): not the atomics' granularity.  Off.
-#ifndef VT_DMA_LATE
-#define VT_DMA_LATE 0  // 1 = waves 4..7 issue their staging pieces inside the S phase instead of right behind the barrier: measured slower (13.14 vs 12.83 ms, B=2)
-#endif
-#ifndef PF_TRN
-#define PF_TRN 4      // transposed-operand pairs of a dV / dK segment in flight before its first MFMA (2: two-deep ring refilled inside the segment)
-#endif
-#ifndef PF_ROWN
-#define PF_ROWN 2     // depth of the ring of Q / dO row operands (4: all k-steps of a q-half in flight before its first MFMA)
-#endif
-#ifndef PF_R0
-#define PF_R0 0       // 1 = the first reads of a step are issued right after the previous step's barrier
-#endif
-#ifndef VT_STAMP
-#define VT_STAMP 0    // 1 = instrumentation build (tools/build_variants.sh): s_memtime stamps of one step of one workgroup, read back with
-#endif                // vt_attn_bwd_stamps<suffix>; the stamps order memory operations around them, so the build is slower than the shipped one
 #ifndef VT_CLK
 #define VT_CLK 0      // 1 = diagnostic build (tools/build_w4.sh): the in-kernel clock of one key block's loop, d(s_memtime) / d(s_memrealtime) x 100 MHz
 #endif                // (MI355X_MICROARCH.md, DVFS item 6); two probes per key block, the loop itself is untouched
@@ -141,6 +76,12 @@
 #define BWD_BODY VT_CAT(attn_bwd_body, VT_SUFFIX)
 #define DELTA_KERNEL VT_CAT(attn_bwd_delta_kernel, VT_SUFFIX)
 #define BWD_ENTRY VT_CAT(vt_attn_bwd_hd64, VT_SUFFIX)
+
+#define BWD_THREADS 512
+#define FENCE() __builtin_amdgcn_sched_barrier(0)
+#define DQ_RING 2     // k-steps of dQ operands in flight
+#define PF_TRN 4      // transposed-operand pairs of a dV / dK segment in flight before its first MFMA
+#define PF_ROWN 2     // depth of the ring of Q / dO row operands
 
 struct AttnBwdParams {
     const bf16_t* q;
@@ -164,34 +105,16 @@ struct AttnBwdParams {
     float* chain_tiles;   // [slots][CH_R][4 waves][4][64 lanes][4] fp32
 };
 
-#define KIMG 0
-#define DSIMG 32768
-#define QTILE 98304
-#define LSEOFF 131072
-#define STATF 132096             // row constants as MFMA operands: 2 buffers x {-lse2/c, -delta} x 64 rows x 32 B
-#ifndef BWD_LDS_PAD
-#define BWD_LDS_PAD 0
-#endif
-#define BWD_LDS (132096 + (VT_STATMFMA ? 8192 : (VT_STAMP ? 1024 : BWD_LDS_PAD)))
-#if VT_STAMP
-#ifndef STAMP_SLOT
-#define STAMP_SLOT 40
-#endif
-#define STAMP_STEP 150
-__device__ unsigned VT_CAT(vt_bwd_stamps, VT_SUFFIX)[256];
-#define STAMP(i, dep) do { if (rec) { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_), "+v"(dep) :: "memory"); \
-                                      if (lane == 0) ((unsigned*)(smem + 132096))[w * 16 + (i)] = (unsigned)t_; } } while (0)
-#else
-#define STAMP(i, dep)
-#endif
+// LDS map (bytes)
+#define KIMG 0                   // K block image, 32 KiB
+#define DSIMG 32768              // dS image, 2 x 32 KiB
+#define QTILE 98304              // 2 x (Q tile 8 KiB | dO tile 8 KiB)
+#define LSEOFF 131072            // 2 x (64 x -lse2/c | 64 x -delta) fp32
+#define BWD_LDS 132096
 #define CH_STAGE_BYTES 16384     // incoming dQ tile of the chain predecessor: 4 waves x 4 KiB, a separate LDS object so
                                  // that the compiler does not order every ds_read of a step behind the DMA that fills it
-#ifndef CH_R
 #define CH_R 4                   // ring depth (tiles of 64 q x 64 d fp32 = 16 KiB)
-#endif
-#ifndef CH_HYST
 #define CH_HYST 1                // tiles of slack a consumer rebuilds whenever it had to wait for its producer
-#endif
 #ifndef CH_SPIN_LIMIT
 #define CH_SPIN_LIMIT (1 << 19)   // polls (~1 us each) before a wait gives up (-DCH_SPIN_LIMIT=0: the forced-time-out test build, libvt355_test.so)
 #endif
@@ -214,11 +137,7 @@ __device__ __forceinline__ bf16x8 tr_pair(const char* p0, const char* p1) {
     return __builtin_bit_cast(bf16x8, v8);
 }
 
-#if VT_W8
-// EIGHT-wave body (VT_W8): wave w owns keys [32w, 32w+32) of the 256-key block -- half the accumulators and half the
-// softmax work per wave, two waves per SIMD so that one wave's exp2 / packing runs under the other's MFMAs (the four-wave
-// body has MFMA and VALU busy at the same time only 13 % of the cycles).  Waves 0..3 run the dQ phase (and the chain
-// hand-off) exactly as the four-wave body does while waves 4..7 already start the next step.
+// One key block (item id) on one slot: K / V fragments, the sweep over all query steps, the dK / dV epilogue.
 template <bool RAGGED, bool PRESCALED, int ROLE>
 __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, char* stage, const int id, const int slot,
                                          const int cons_end, const int base, const bool l2_prev, const bool l2_next,
@@ -236,10 +155,13 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
     const bf16_t* kb_ = p.k + (size_t)b * p.k_bs + head * 64;
     const bf16_t* vb = p.v + (size_t)b * p.v_bs + head * 64;
     const bf16_t* dob = p.dout + (size_t)b * p.do_bs + head * 64;
+    // rq and rdo are unused (the Q / dO tiles go through the raw descriptor words rq_w / rdo_w below).  They stay because the compiler orders
+    // the kernel's scalar prologue differently without them, and this file's machine code changes only together with a measurement.
     __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, (unsigned)((long long)(p.S - 1) * p.q_rs * 2 + 128));
     __amdgpu_buffer_rsrc_t rk = make_rsrc(kb_, (unsigned)((long long)(p.S - 1) * p.k_rs * 2 + 128));
     __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, (unsigned)((long long)(p.S - 1) * p.v_rs * 2 + 128));
     __amdgpu_buffer_rsrc_t rdo = make_rsrc(dob, (unsigned)((long long)(p.S - 1) * p.do_rs * 2 + 128));
+    // dQ accumulation buffer of this (batch, head): rows >= S are out of range -> the atomics are dropped by hardware
     __amdgpu_buffer_rsrc_t rdq = make_rsrc(p.dq + (size_t)b * p.dq_bs + head * 64, (unsigned)((long long)(p.S - 1) * p.dq_rs * 4 + 256));
     const float* lse_b = p.lse2 + (size_t)bh * p.S;
     const float* dl_b = p.delta + (size_t)bh * p.S;
@@ -253,7 +175,6 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
         *(u32x4*)(smem + KIMG + swz_off(key, c)) = v;
     }
     // ---- K / V fragments of this wave's 32 keys, resident for the whole key block ----
-#if VT_M16
     // B operands of S = Q K^T and dP = dO V^T on 16 x 16 x 32 tiles: lane (g, c) holds K[key 16 kt + c][d = 32 s + 8 g .. + 7]
     const int c15 = lane & 15;
     bf16x8 kf16[2][2], vf16[2][2];
@@ -268,21 +189,8 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
         }
         kmask16[kt] = (RAGGED && key >= p.S) ? -1.0e30f : 0.f;
     }
-#else
-    bf16x8 kf[4], vf[4];
-    {
-        const int key = key0 + 32 * w + r;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            kf[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rk, (int)(key * p.k_rs * 2) + (16 * s + 8 * h) * 2, 0, 0));
-            vf[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(key * p.v_rs * 2) + (16 * s + 8 * h) * 2, 0, 0));
-        }
-    }
-    const float kmask = (RAGGED && (key0 + 32 * w + r) >= p.S) ? -1.0e30f : 0.f;
-#endif
 
-    // ---- per-lane LDS offsets (identical to csrc/attn_bwd.hip) ----
-#if VT_M16
+    // ---- per-lane LDS offsets ----
     // Q / dO tile image, swizzle row & 6.  Row fragment (q-tile, k-step s): lane (g, c) reads row c, chunk 4 s + g; a q-tile is 2048 B further.
     // Transposed fragment (d-tile dt) of a 32-query k-step: group g takes the 4-row blocks at rows 4 g and 16 + 4 g (k-slot j of the group =
     // query 4 g + j for j < 4, 16 + 4 g + j - 4 above: the order in which two stacked accumulator tiles supply P / dS), columns 16 dt .. + 15
@@ -292,95 +200,38 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
     int trA16[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) trA16[dt] = (4 * g + ql) * 128 + (((2 * dt + (pl >> 1)) ^ ((4 * g + ql) & 6)) << 4) + (pl & 1) * 8;
-#else
-    int rowrd[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) rowrd[s] = r * 128 + (((2 * s + h) ^ swz_f(r)) << 4);
-    int trA[2][2];
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int sec = 0; sec < 2; ++sec) {
-            const int fx = ((ql >> 1) << 2) | (sec << 1) | h;
-            trA[dt][sec] = (4 * h + ql + 8 * sec) * 128 + (((4 * dt + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
-        }
-#endif
-#if VT_DQ16
-    // dQ phase: the 64x64 block as sixteen 16x16 tiles (v_mfma_f32_16x16x32_bf16), two per wave: q rows 16 qt .., d columns
-    // 32 dh + {0, 16}.  A = dS^T (rows q, k = key) and B = K^T (rows d, k = key) both come from transposed reads: group
-    // g = lane>>4 takes key rows 8g + 4 sec + ql of every 32-key k-step, 16 columns wide; with the images' swizzle the two
-    // blocks of a 32-lane half are 8 rows apart in the same columns -> conflict-free.
-    const int qt = w >> 1, dh = w & 1;
-    int trq16[2], trk16[2][2];
-#pragma unroll
-    for (int sec = 0; sec < 2; ++sec) {
-        const int row = 8 * g + 4 * sec + ql;
-        const int fxr = swz_f(row);
-        trq16[sec] = row * 128 + (((2 * qt + (pl >> 1)) ^ fxr) << 4) + (pl & 1) * 8;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) trk16[j][sec] = row * 128 + (((2 * (2 * dh + j) + (pl >> 1)) ^ fxr) << 4) + (pl & 1) * 8;
-    }
-    const int dq_voff = (int)((16 * qt + 4 * g) * p.dq_rs * 4) + (32 * dh + (lane & 15)) * 4;
-    const int dq_rowb = (int)(p.dq_rs * 4);
-#else
     const int qs_w = w & 1, dt_w = (w >> 1) & 1;          // dQ phase (waves 0..3): (q-half, d-half) of the 64x64 tile
-    int trQA[2], trQB[2];
+    int trQA[2], trQB[2];                                 // transposed reads of the dS image (A, 8-byte swizzle) and the K image (B), [sec]
 #pragma unroll
     for (int sec = 0; sec < 2; ++sec) {
         const int fx = ((ql >> 1) << 2) | (h << 1) | sec;
         const int row = (8 * h + ql + 4 * sec) * 128;
-#if VT_DS4
         trQA[sec] = row + (((2 * (4 * qs_w + 2 * (g & 1) + (pl >> 1)) + (pl & 1)) ^ swz4(8 * h + ql + 4 * sec)) << 3);
-#else
-        trQA[sec] = row + (((4 * qs_w + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
-#endif
         trQB[sec] = row + (((4 * dt_w + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
     }
-#if VT_DQM16
-    // 16 x 16 x 32 operands of the dQ product (the addressing of the VT_DQ16 variant): group g takes key rows 8 g + 4 sec + ql of every 32-key
-    // k-step, 16 columns wide -- q-tiles 2 qs_w + a of the dS image (A), d-tiles 2 dt_w + b of the K image (B)
-    int trq16m[2][2], trk16m[2][2];
-#pragma unroll
-    for (int sec = 0; sec < 2; ++sec) {
-        const int row = 8 * g + 4 * sec + ql;
-        const int fxr = swz_f(row);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            trq16m[a][sec] = row * 128 + (((2 * (2 * qs_w + a) + (pl >> 1)) ^ fxr) << 4) + (pl & 1) * 8;
-            trk16m[a][sec] = row * 128 + (((2 * (2 * dt_w + a) + (pl >> 1)) ^ fxr) << 4) + (pl & 1) * 8;
-        }
-    }
-    const int dq_voff = (int)((32 * qs_w + 8 * (g >> 1)) * p.dq_rs * 4) + (32 * dt_w + 16 * (g & 1) + (lane & 15)) * 4;   // after the lane-row swap
-#else
+    // dQ atomics: byte offset of (row 32 qs_w + 4 h, column 32 dt_w + r) inside a 64-row step; register i adds ((i & 3) + 8 (i >> 2)) rows
     const int dq_voff = (int)((32 * qs_w + 4 * h) * p.dq_rs * 4) + (32 * dt_w + r) * 4;
-#endif
     const int dq_rowb = (int)(p.dq_rs * 4);
-#endif
-    const int fr = swz_f(r);
 
     // ---- dQ hand-off chain (see the header comment); only the dQ waves (w < 4) take part ----
-#if VT_DQ16
-    const int wu = w;                 // every wave owns 2 KiB of a hand-off tile (2 x 16x16 fp32)
-    constexpr bool dqw = true;
-    constexpr int NT = 2, WTILE = 2048;
-#else
     const int wu = w & 3;             // waves 0..3 own 4 KiB each (one 32x32 fp32 tile)
     const bool dqw = w < 4;
     constexpr int NT = 4, WTILE = 4096;
-#endif
     __amdgpu_buffer_rsrc_t rfl = make_rsrc(p.chain_flags, (unsigned)gridDim.x * 64u);
     __amdgpu_buffer_rsrc_t rt_mine = make_rsrc(p.chain_tiles + (size_t)slot * (CH_R * 4096), CH_R * 16384);
     const int fl_ready_me = (slot * 16 + wu) * 4, fl_cons_me = (slot * 16 + 8 + wu) * 4;
     const int fl_ready_prod = ((slot - 1) * 16 + wu) * 4, fl_cons_next = ((slot + 1) * 16 + 8 + wu) * 4;
     const int tile_voff = wu * WTILE + lane * 16;
     const unsigned stage_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)stage;
-    i32x4w rt_prod_w;
+    i32x4w rt_prod_w;                                      // the predecessor's ring as raw descriptor words (inline asm operand)
     {
         const unsigned long long a = (unsigned long long)(p.chain_tiles + (size_t)(has_prod ? slot - 1 : slot) * (CH_R * 4096));
         rt_prod_w = (i32x4w){(int)(unsigned)a, (int)((a >> 32) & 0xffffu), CH_R * 16384, 0x00020000};
     }
+    // counter loads stay in a VGPR until the end-of-step barrier has waited for them anyway; only then are they moved to
+    // an SGPR (a readfirstlane anywhere else makes the compiler drain every outstanding memory operation on the spot)
     auto fl_load = [&](int off) -> int { return (int)__builtin_amdgcn_raw_buffer_load_b32(rfl, off, 0, CH_AUX); };
-    int spins_r = 0, spins_c = 0;
+    int spins_r = 0, spins_c = 0;      // diagnostics: polls spent waiting for the predecessor / the successor
     auto fl_wait = [&](int off, int need, int have, int& spins) {
         int it = 0;
         while (have < need && !dead) {
@@ -391,16 +242,14 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
         }
     };
 
-    // ---- staging of the Q / dO tiles (64 rows x 8 chunks each): one chunk of each per thread ----
-    const int st_voq = (int)((tid >> 3) * p.q_rs * 2) + (tid & 7) * 16;
-    const int st_vodo = (int)((tid >> 3) * p.do_rs * 2) + (tid & 7) * 16;
-    const int st_lds = swz_off(tid >> 3, tid & 7);
+    // ---- staging of the Q / dO tiles (64 rows x 8 chunks each) and of the row constants, by waves 4..7 ----
+    // row constants in the form the MFMA accumulators want:  S'' = Q K^T - lse2/c  and  dP' = dO V^T - delta;
+    // threads t and t + 128 stage the same value (keeps the loop body free of divergent branches)
     const int stat_i = tid & 63;
     const bool stat_is_lse = (tid & 64) == 0;
     const float* stat_src = stat_is_lse ? lse_b : dl_b;
     const float stat_mul = stat_is_lse ? (PRESCALED ? -1.0f : -1.0f / p.scale_log2) : -1.0f;
     const int stat_lds = LSEOFF + (tid & 127) * 4;
-#if VT_DMA
     float gstat = 0.f;
     i32x4w rq_w, rdo_w;
     {
@@ -414,14 +263,13 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = 16 * (w & 3) + 8 * j + (lane >> 3);
-        const int c = (lane & 7) ^ (VT_M16 ? (row & 6) : swz_f(row));
+        const int c = (lane & 7) ^ (row & 6);
         dma_vq[j] = (int)(row * p.q_rs * 2) + c * 16;
         dma_vdo[j] = (int)(row * p.do_rs * 2) + c * 16;
     }
     const unsigned smem_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    // tile t -> buffer t & 1, free since the barrier of step t - 2.  Two halves (Q pieces | dO pieces + row constants) so that the step can
-    // issue them at different points of its S phase: an LDS-DMA piece holds the CU's address path for ~16 cycles, and eight waves
-    // issuing theirs right behind the barrier (these + the dQ waves' chain pieces) queued for ~600 cycles
+    // tile t -> buffer t & 1, free since the barrier of step t - 2: Q pieces, then dO pieces + row constants.  Inline asm, so that the compiler does
+    // not order the step's LDS reads behind them (see prefetch below); lstore's vmcnt(0) retires them before the barrier that publishes the tile
     auto gload_q = [&](int t) {
         if (!dqw) {
             const int sq = (int)((long long)t * 64 * p.q_rs * 2);
@@ -455,41 +303,11 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
             __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): the compiler does not know about the DMA pieces
         }
     };
-#else
-    u32x4 gq, gdo;
-    float gstat = 0.f;
-    auto gload = [&](int t) {
-        const int q0 = t * 64;
-        const int sq = (int)((long long)q0 * p.q_rs * 2), sdo = (int)((long long)q0 * p.do_rs * 2);
-        gq = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rq, st_voq, sq, 0));
-        gdo = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rdo, st_vodo, sdo, 0));
-        int qi = q0 + stat_i;
-        const bool ok = qi < p.S;
-        qi = ok ? qi : p.S - 1;
-        const float v = stat_src[qi] * stat_mul;
-        gstat = ok ? v : 0.f;
-    };
-    auto lstore = [&](int buf) {
-        char* base = smem + QTILE + buf * 16384;
-        *(u32x4*)(base + st_lds) = gq;
-        *(u32x4*)(base + 8192 + st_lds) = gdo;
-        *(float*)(smem + stat_lds + buf * 512) = gstat;     // threads t, t+128, t+256, t+384 write the same value
-    };
-
-#endif
-#if VT_M16
     f32x4 dk16[4][2], dv16[4][2];         // [d-tile][key-tile]: dK^T / dV^T, lane (g, c) holds d = 16 dt + 4 g + i of key 16 kt + c
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int i = 0; i < 2; ++i) { dk16[c][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; dv16[c][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-#else
-    f32x16 dk_acc[2], dv_acc[2];          // [dt]: dK^T / dV^T of this wave's 32 keys
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { dk_acc[c][i] = 0.f; dv_acc[c][i] = 0.f; }
-#endif
 
     const float sc = p.scale_log2;
     const int nsteps = (p.S + 63) / 64;
@@ -500,14 +318,21 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
     __syncthreads();
     int s_ready = (has_prod && dqw) ? __builtin_amdgcn_readfirstlane(pf_ready) : 0;
     // everything step t1 fetches from memory: the chain predecessor's dQ tile t1 (LDS-DMA into the stage), the counter for t1 + 1, the
-    // Q / dO tile t1 + 1.  Shipped order: at the top of step t1.  VT_PF: right after the barrier of step t1 - 1, BEFORE that step's dQ
-    // atomics -- vector-memory instructions issue in order, and the loads of a wave that has just pushed 16 atomics (16 B/clk per CU)
-    // waited ~500-700 cycles for their turn (profiles/r02_attn_bwd_stamps_before_L2_consumer.txt, "loads issued")
+    // Q / dO tile t1 + 1.  Issued right after the barrier of step t1 - 1, BEFORE that step's dQ atomics -- vector-memory instructions issue
+    // in order, and the loads of a wave that has just pushed 16 atomics (16 B/clk per CU) waited ~500-700 cycles for their turn
+    // (profiles/r02_attn_bwd_stamps_before_L2_consumer.txt, "loads issued")
     auto prefetch = [&](int t1) {
         if (has_prod && dqw && t1 < nsteps) {
+            // predecessor's tile t1 must be public.  The counter at hand is a step old, and a consumer that passes with no margin is stopped
+            // again by the next hiccup of its producer, each time for a full uncached round trip that its own successors then inherit: when
+            // it does have to wait, it waits until the producer is CH_HYST tiles ahead, and then coasts on that slack.
             if (s_ready < base + t1 + 1)
                 fl_wait(fl_ready_prod, base + (t1 + 1 + CH_HYST < nsteps ? t1 + 1 + CH_HYST : nsteps), s_ready, spins_r);
-            // hidden LDS-DMA of the predecessor's tile t1 (see the four-wave body for why it goes through inline asm)
+            // LDS-DMA of the 4 x 1 KiB of this wave.  Issued through inline asm: the compiler orders every later LDS access of the step behind
+            // an LDS-DMA it knows about (s_waitcnt vmcnt(0) a few instructions into the step).  Safe because the wait in front of the barrier
+            // below covers them (vector memory retires in order) and the stage is read only behind that barrier.
+            // Cache policy: the predecessor shares this XCD's L2 (l2_prev: its plain stores are there) -> agent-scope load, L1 bypassed;
+            // otherwise system scope against its write-through stores
             if (l2_prev) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
@@ -523,19 +348,13 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
             }
             pf_ready = fl_load(fl_ready_prod);
         }
-#if !(VT_DMA && VT_DMA_LATE)
         gload(t1 + 1);                                 // past the end: bounds-checked loads return zeros
-#endif
     };
-#if VT_PF
     prefetch(0);
-    // S'' / dP' of q-half 0 (initialised with the row constants) and the two-deep ring of Q / dO row operands are carried from step to
-    // step: the first reads of step t + 1 are issued right after the barrier of step t, before anything else
-#if VT_M16
-    // 16 x 16 tiles: s16[q-half][q-tile][key-tile] (lane (g, c): query 16 qt + 4 g + i, key 16 kt + c); row-operand ring of two (q-tile, k-step)
-    // items; item n of a q-half = (k-step n >> 1, q-tile n & 1)
+    // S'' / dP' accumulators, 16 x 16 tiles: s16[q-half][q-tile][key-tile] (lane (g, c): query 16 qt + 4 g + i, key 16 kt + c), and the ring of
+    // PF_ROWN Q / dO row operands; item n of a q-half = (k-step n >> 1, q-tile n & 1), ring slot n & 1
     f32x4 s16[2][2][2], p16[2][2][2];
-    bf16x8 qa16[2], doa16[2];
+    bf16x8 qa16[PF_ROWN], doa16[PF_ROWN];
     // the row constants go straight into the accumulators of BOTH key tiles.  (Kept in registers of their own as the C operand of the first
     // k-step's MFMAs -- one LDS value for two tiles, no spill -- measured slower: 6.94-7.15 vs 6.66-6.77 ms at B=1, same box.)
     auto rd_init16 = [&](const float* lsel_, int qs, int qt, int which) {    // which: 0 = S'' (-lse2 / c [+ key mask]), 1 = dP' (-delta)
@@ -560,58 +379,21 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
         rd_rows16(qn, qn + 8192, 0, 0); rd_rows16(qn, qn + 8192, 0, 1);
         FENCE();
     };
-#else
-    f32x16 sacc[2], pacc[2];
-    bf16x8 qa[PF_ROWN], doa[PF_ROWN];
-    auto rd_init = [&](const float* lsel_, int qs, int g0, int g1) {
-#pragma unroll
-        for (int gg = g0; gg < g1; ++gg) {
-            const f32x4 a = *(const f32x4*)(lsel_ + 32 * qs + 8 * gg + 4 * h);
-            const f32x4 c = *(const f32x4*)(lsel_ + 64 + 32 * qs + 8 * gg + 4 * h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { sacc[qs][4 * gg + e] = RAGGED ? a[e] + kmask : a[e]; pacc[qs][4 * gg + e] = c[e]; }
-        }
-    };
-    auto rd_rows = [&](const char* qimg_, const char* doimg_, int qs, int s_) {
-        qa[s_ % PF_ROWN] = *(const bf16x8*)(qimg_ + qs * 4096 + rowrd[s_]);
-        doa[s_ % PF_ROWN] = *(const bf16x8*)(doimg_ + qs * 4096 + rowrd[s_]);
-    };
-    auto rd_first = [&](int bufn) {
-        const char* qn = smem + QTILE + bufn * 16384;
-        rd_init((const float*)(smem + LSEOFF + bufn * 512), 0, 0, 4);
-#pragma unroll
-        for (int s_ = 0; s_ < PF_ROWN; ++s_) rd_rows(qn, qn + 8192, 0, s_);
-        FENCE();
-    };
-#endif
-#if PF_R0
-    rd_first(0);
-#endif
-#endif
     for (int t = 0; t < nsteps; ++t) {
         const int buf = t & 1;
         int pf_cons = 0;
-#if VT_STAMP
-        const bool rec = slot == STAMP_SLOT && t == STAMP_STEP && base == 0;
-        int stamp_dummy = 0;
-        STAMP(0, stamp_dummy);
-#endif
-#if !VT_PF
-        prefetch(t);
-#endif
         if (has_cons && dqw) pf_cons = fl_load(fl_cons_next);
         const char* qimg = smem + QTILE + buf * 16384;
         const char* doimg = qimg + 8192;
         const float* lsel = (const float*)(smem + LSEOFF + buf * 512);
         char* dsimg = smem + DSIMG + buf * 32768;
-        STAMP(1, stamp_dummy);
 
-#if VT_PF && VT_M16
+        // ---- S phase (all waves) ----
         {
-            // the schedule of the 32 x 32 x 16 body below, on 16 x 16 x 32 tiles: per q-half a segment of 16 S'' / dP' MFMAs (four items of
-            // (k-step, q-tile) x (key-tile, S | dP)), the exp2 block, a segment of 16 dV / dK MFMAs (four d-tiles x (key-tile, dV | dK));
-            // every segment's operand reads are issued during the one before, pinned by the fences
-            bf16x8 doT16[4], qT16[4];
+            // per q-half a segment of 16 S'' / dP' MFMAs (four items of (k-step, q-tile) x (key-tile, S | dP)), the exp2 block (P = exp2(c S''),
+            // dS = P * dP', both packed to bf16 pairs), a segment of 16 dV / dK MFMAs (four d-tiles x (key-tile, dV | dK)); every segment's
+            // operand reads are issued during the one before, pinned by the fences
+            bf16x8 doT16[PF_TRN], qT16[PF_TRN];       // transposed dO / Q operands of the four d-tiles
             unsigned pw16[2][2][2], dw16[2][2][2];
             auto rd_tr16 = [&](int qs, int dt) {
                 const int ro = qs * 4096 + trA16[dt];
@@ -663,12 +445,11 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
                     }
                     FENCE();
                 }
-                // dS image (format of the 32 x 32 body: row = key, 8 bytes = four consecutive queries): tile (qt, kt) -> row 32 w + 16 kt + c,
-                // queries 32 qs + 16 qt + 4 g + (0..3) = chunk 4 qs + 2 qt + (g >> 1), half g & 1
+                // dS image (row = key, 8 bytes = four consecutive queries): tile (qt, kt) -> row 32 w + 16 kt + c,
+                // queries 32 qs + 16 qt + 4 g + (0..3) = 8-byte unit 8 qs + 4 qt + g
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) {
                     const int krow = 32 * w + 16 * kt + c15;
-#if VT_DS4
                     char* drow = dsimg + krow * 128;
                     const int fk = swz4(krow);
 #pragma unroll
@@ -676,156 +457,11 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
                         const u32x2 two = {dw16[qt][kt][0], dw16[qt][kt][1]};
                         *(u32x2*)(drow + (((8 * qs + 4 * qt + g) ^ fk) << 3)) = two;          // 8-byte position = (query / 4) ^ swz4(key row)
                     }
-#else
-                    char* drow = dsimg + krow * 128 + 8 * (g & 1);
-                    const int fk = swz_f(krow);
-#pragma unroll
-                    for (int qt = 0; qt < 2; ++qt) {
-                        const u32x2 two = {dw16[qt][kt][0], dw16[qt][kt][1]};
-                        *(u32x2*)(drow + (((4 * qs + 2 * qt + (g >> 1)) ^ fk) << 4)) = two;
-                    }
-#endif
                 }
                 FENCE();
             }
         }
-#elif VT_PF
-        {
-            // The compiler's own order issues every operand read right before the MFMA that needs it (one LDS round trip exposed per
-            // k-step: profiles/r02_attn_bwd_stamps_before_*.txt -- 650-950 cycles per 8-MFMA segment against 256 of matrix-pipe time).
-            // Here: segment = 8 MFMAs; its reads are issued during the previous segment (q-half 0's first ones right after the previous
-            // step's barrier, below), fences keep the compiler from sinking them.
-            bf16x8 doT[PF_TRN], qT[PF_TRN];
-            unsigned pw[8], dw[8];
-            auto rd_tr = [&](int qs, int j) {          // pair j = (s2, dt) = (j >> 1, j & 1)
-                const int ro = (32 * qs + 16 * (j >> 1)) * 128, dt = j & 1;
-                doT[j % PF_TRN] = tr_pair(doimg + ro + trA[dt][0], doimg + ro + trA[dt][1]);
-                qT[j % PF_TRN] = tr_pair(qimg + ro + trA[dt][0], qimg + ro + trA[dt][1]);
-            };
-#if !PF_R0
-            rd_first(buf);
-#endif
-            FENCE();
-#pragma unroll
-            for (int qs = 0; qs < 2; ++qs) {
-#pragma unroll
-                for (int s_ = 0; s_ < 4; ++s_) {
-                    sacc[qs] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[s_ % PF_ROWN], kf[s_], sacc[qs], 0, 0, 0);
-                    pacc[qs] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa[s_ % PF_ROWN], vf[s_], pacc[qs], 0, 0, 0);
-                    if (s_ + PF_ROWN < 4) rd_rows(qimg, doimg, qs, s_ + PF_ROWN);               // into the slot these MFMAs just read
-                    if (s_ >= 2) rd_tr(qs, s_ - 2);
-                    FENCE();
-                }
-#if VT_DMA && VT_DMA_LATE
-                if (qs == 0) { gload_q(t + 1); FENCE(); }   // waves 4..7: the next tile's Q pieces (past the end: zeros)
-#endif
-#if PF_TRN > 2
-#pragma unroll
-                for (int jj = 2; jj < PF_TRN; ++jj) rd_tr(qs, jj);      // land under the exp2 block
-                FENCE();
-#endif
-                STAMP(2 + 3 * qs, pacc[qs][15]);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float p0 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[qs][2 * i] : sacc[qs][2 * i] * sc);
-                    const float p1 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[qs][2 * i + 1] : sacc[qs][2 * i + 1] * sc);
-                    pw[i] = pack2(p0, p1);
-                    dw[i] = pack2(p0 * pacc[qs][2 * i], p1 * pacc[qs][2 * i + 1]);
-                }
-                STAMP(3 + 3 * qs, dw[7]);
-                FENCE();
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int s2 = j >> 1, dt = j & 1;
-                    const u32x4 pb4 = {pw[4 * s2], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-                    const u32x4 db4 = {dw[4 * s2], dw[4 * s2 + 1], dw[4 * s2 + 2], dw[4 * s2 + 3]};
-                    dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doT[j % PF_TRN], __builtin_bit_cast(bf16x8, pb4), dv_acc[dt], 0, 0, 0);
-                    dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qT[j % PF_TRN], __builtin_bit_cast(bf16x8, db4), dk_acc[dt], 0, 0, 0);
-                    if (j + PF_TRN < 4) rd_tr(qs, j + PF_TRN);       // into the slot these MFMAs just read
-                    if (qs == 0) {                      // the other q-half's first reads ride under these MFMAs
-                        rd_init(lsel, 1, j, j + 1);
-                        if (j >= 4 - PF_ROWN) rd_rows(qimg, doimg, 1, j - (4 - PF_ROWN));
-                    }
-                    FENCE();
-                }
-                char* drow = dsimg + (32 * w + r) * 128 + 8 * h;
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    const u32x2 two = {dw[2 * gg], dw[2 * gg + 1]};
-                    *(u32x2*)(drow + (((4 * qs + gg) ^ fr) << 4)) = two;
-                }
-                STAMP(4 + 3 * qs, dk_acc[1][15]);
-                FENCE();
-#if VT_DMA && VT_DMA_LATE
-                if (qs == 0) { gload_do(t + 1); FENCE(); }  // ... its dO pieces and row constants
-#endif
-            }
-        }
-#else
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs) {
-            // S'' and dP' accumulators start from the row constants (-lse2/c [+ key mask], -delta)
-            f32x16 sacc, pacc;
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-#if VT_ABL == 5 || VT_ABL == 7
-                const f32x4 a = {-8.f, -8.f, -8.f, -8.f}, c = {-0.01f, -0.01f, -0.01f, -0.01f};
-#else
-                const f32x4 a = *(const f32x4*)(lsel + 32 * qs + 8 * gg + 4 * h);
-                const f32x4 c = *(const f32x4*)(lsel + 64 + 32 * qs + 8 * gg + 4 * h);
-#endif
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sacc[4 * gg + e] = RAGGED ? a[e] + kmask : a[e]; pacc[4 * gg + e] = c[e]; }
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const bf16x8 qa = *(const bf16x8*)(qimg + qs * 4096 + rowrd[s]);
-                const bf16x8 doa = *(const bf16x8*)(doimg + qs * 4096 + rowrd[s]);
-                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[s], sacc, 0, 0, 0);
-                pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa, vf[s], pacc, 0, 0, 0);
-            }
-            // P = exp2(c * S''), dS = P * dP'; both packed to bf16 pairs (B operands + dS image)
-            unsigned pw[8], dw[8];
-            STAMP(2 + 3 * qs, pacc[15]);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float p0 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i] : sacc[2 * i] * sc);
-                const float p1 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i + 1] : sacc[2 * i + 1] * sc);
-                pw[i] = pack2(p0, p1);
-                dw[i] = pack2(p0 * pacc[2 * i], p1 * pacc[2 * i + 1]);
-            }
-            STAMP(3 + 3 * qs, dw[7]);
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const u32x4 pb4 = {pw[4 * s2], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-                const u32x4 db4 = {dw[4 * s2], dw[4 * s2 + 1], dw[4 * s2 + 2], dw[4 * s2 + 3]};
-                const bf16x8 pb = __builtin_bit_cast(bf16x8, pb4), dsb = __builtin_bit_cast(bf16x8, db4);
-                const int ro = (32 * qs + 16 * s2) * 128;
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-#if VT_ABL == 6 || VT_ABL == 7
-                    (void)ro;
-                    const bf16x8 doT = vf[2 * s2 + dt], qT = kf[2 * s2 + dt];
-#else
-                    const bf16x8 doT = tr_pair(doimg + ro + trA[dt][0], doimg + ro + trA[dt][1]);
-                    const bf16x8 qT = tr_pair(qimg + ro + trA[dt][0], qimg + ro + trA[dt][1]);
-#endif
-                    dv_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doT, pb, dv_acc[dt], 0, 0, 0);
-                    dk_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qT, dsb, dk_acc[dt], 0, 0, 0);
-                }
-            }
-            // dS image: row = key (32w + r), 8 bytes = q 32qs + 8g' + 4h + (0..3)
-            char* drow = dsimg + (32 * w + r) * 128 + 8 * h;
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                const u32x2 two = {dw[2 * gg], dw[2 * gg + 1]};
-                *(u32x2*)(drow + (((4 * qs + gg) ^ fr) << 4)) = two;
-            }
-            STAMP(4 + 3 * qs, dk_acc[1][15]);
-        }
-#endif
         lstore(buf ^ 1);
-#if VT_DMA
         // the predecessor's tile t (LDS-DMA the compiler does not know about) must have landed before the barrier: it was issued before
         // this wave's previous 16 atomics (+ 1 counter store), which may stay in flight -- vector memory completes in order
         // (step 0 has no atomics behind the DMA yet: wait for everything)
@@ -833,97 +469,13 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
             if (has_cons || t == 0) __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0)
             else __builtin_amdgcn_s_waitcnt(0x4F70);                                      // vmcnt(16)
         }
-#endif
-        STAMP(8, stamp_dummy);
         __syncthreads();
-        STAMP(9, stamp_dummy);
-#if VT_PF && PF_R0
-        rd_first(buf ^ 1);
-#endif
 
-#if VT_DQ16
-        // ---- dQ: two 16x16 tiles per wave over all 256 keys (all eight waves) ----
-        {
-            if (has_prod) s_ready = __builtin_amdgcn_readfirstlane(pf_ready);      // the barrier drained the memory pipeline
-            const int s_cons = has_cons ? __builtin_amdgcn_readfirstlane(pf_cons) : 0;
-            f32x4 dq16[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (has_prod) dq16[j] = *(const f32x4*)(stage + wu * WTILE + j * 1024 + lane * 16);
-                else dq16[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-#if VT_PF
-            if (has_prod) __builtin_amdgcn_s_waitcnt(0xc07f);
-            if (has_cons && t > 0) {
-                __builtin_amdgcn_s_waitcnt(0x0F70);
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + t), rfl, fl_ready_me, 0, CH_AUX);
-            }
-            prefetch(t + 1);
-#endif
-#pragma unroll
-            for (int s3 = 0; s3 < 8; ++s3) {
-                const bf16x8 fa = tr_pair(dsimg + s3 * 4096 + trq16[0], dsimg + s3 * 4096 + trq16[1]);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const bf16x8 fb = tr_pair(smem + KIMG + s3 * 4096 + trk16[j][0], smem + KIMG + s3 * 4096 + trk16[j][1]);
-                    dq16[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb, dq16[j], 0, 0, 0);
-                }
-            }
-            if (has_cons) {
-                const int a = base + t;
-                int need = a - CH_R + 1;
-                if (t < CH_R && need > cons_end) need = cons_end;
-                if (need > 0) fl_wait(fl_cons_next, need, s_cons, spins_c);
-#if !VT_PF
-                if (t > 0) {
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                                   // vmcnt(0): tile t-1 is a step old
-                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)a, rfl, fl_ready_me, 0, CH_AUX);
-                }
-#endif
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if (l2_next)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dq16[j]), rt_mine, tile_voff + j * 1024, (a % CH_R) * 16384, 0);
-                    else
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dq16[j]), rt_mine, tile_voff + j * 1024, (a % CH_R) * 16384, CH_AUX);
-                }
-            } else {
-                const int soff = (int)((long long)t * 64 * p.dq_rs * 4);
-#if VT_ABL == 2
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) asm volatile("" ::"v"(dq16[j][e]));
-                (void)soff;
-#else
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)      // register e = q row 4g + e; 16 consecutive d per lane group
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dq16[j][e] * p.scale, rdq, dq_voff,
-                                                                        soff + e * dq_rowb + 64 * j, 0);
-#endif
-            }
-            if (has_prod) __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + t + 1), rfl, fl_cons_me, 0, CH_AUX);
-        }
-    }
-#else
-        // ---- dQ tile (32 q x 32 d) over all 256 keys: waves 0..3 only; waves 4..7 go on with the next step ----
-#if VT_PF
+        // ---- dQ phase: one tile (32 q x 32 d) over all 256 keys on waves 0..3, then the hand-off or the atomics; waves 4..7 go on with the next step ----
         if (!dqw) prefetch(t + 1);
-#endif
         if (dqw) {
-#if VT_DQPRIO
-            __builtin_amdgcn_s_setprio(3);         // the step barrier waits for these waves: let them win the issue arbitration
-#endif
             if (has_prod) s_ready = __builtin_amdgcn_readfirstlane(pf_ready);      // the barrier drained the memory pipeline
             const int s_cons = has_cons ? __builtin_amdgcn_readfirstlane(pf_cons) : 0;
-#if VT_PF && VT_DQM16
-            f32x4 dqt[2][2];                          // [q-tile a][d-tile b]; piece j = 2 a + b of the hand-off tile
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                dqt[j >> 1][j & 1] = has_prod ? *(const f32x4*)(stage + wu * 4096 + j * 1024 + lane * 16) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#else
             f32x16 dq_acc;
             if (has_prod) {
 #pragma unroll
@@ -936,39 +488,12 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
 #pragma unroll
                 for (int i = 0; i < 16; ++i) dq_acc[i] = 0.f;
             }
-#endif
-#if VT_PF
             if (has_prod) __builtin_amdgcn_s_waitcnt(0xc07f);                             // the stage has been read: the next DMA may land
             if (has_cons && t > 0) {
                 __builtin_amdgcn_s_waitcnt(0x0F70);                                       // vmcnt(0): tile t-1 is a step old
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + t), rfl, fl_ready_me, 0, CH_AUX);
             }
             prefetch(t + 1);
-#endif
-#if VT_PF && VT_DQM16
-            {
-                bf16x8 fa[2][2], fb[2][2];                    // [ring slot][tile]: two 32-key k-steps of operands in flight
-                auto rd_dq16 = [&](int s3) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a) {
-                        fa[s3 & 1][a] = tr_pair(dsimg + s3 * 4096 + trq16m[a][0], dsimg + s3 * 4096 + trq16m[a][1]);
-                        fb[s3 & 1][a] = tr_pair(smem + KIMG + s3 * 4096 + trk16m[a][0], smem + KIMG + s3 * 4096 + trk16m[a][1]);
-                    }
-                };
-                rd_dq16(0); rd_dq16(1);
-                FENCE();
-#pragma unroll
-                for (int s3 = 0; s3 < 8; ++s3) {
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int b2 = 0; b2 < 2; ++b2)
-                            dqt[a][b2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s3 & 1][a], fb[s3 & 1][b2], dqt[a][b2], 0, 0, 0);
-                    if (s3 + 2 < 8) rd_dq16(s3 + 2);
-                    FENCE();
-                }
-            }
-#elif VT_PF
             {
                 bf16x8 fa[DQ_RING], fb[DQ_RING];              // DQ_RING k-steps of operands in flight (the compiler's order: one, waited for at once)
                 auto rd_dq = [&](int s3) {
@@ -978,102 +503,36 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
 #pragma unroll
                 for (int s3 = 0; s3 < DQ_RING; ++s3) rd_dq(s3);
                 FENCE();
-#if VT_DQ2
-                f32x16 dq_odd;                    // two accumulation chains: a dependent MFMA waits for its predecessor's last pass
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dq_odd[i] = 0.f;
-#endif
 #pragma unroll
                 for (int s3 = 0; s3 < 16; ++s3) {
-#if VT_DQ2
-                    if (s3 & 1) dq_odd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s3 % DQ_RING], fb[s3 % DQ_RING], dq_odd, 0, 0, 0);
-                    else
-#endif
                     dq_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s3 % DQ_RING], fb[s3 % DQ_RING], dq_acc, 0, 0, 0);
                     if (s3 + DQ_RING < 16) rd_dq(s3 + DQ_RING);
                     FENCE();
                 }
-#if VT_DQ2
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dq_acc[i] += dq_odd[i];
-#endif
             }
-#else
-#pragma unroll
-            for (int s3 = 0; s3 < 16; ++s3) {
-                const bf16x8 fa = tr_pair(dsimg + s3 * 2048 + trQA[0], dsimg + s3 * 2048 + trQA[1]);
-                const bf16x8 fb = tr_pair(smem + KIMG + s3 * 2048 + trQB[0], smem + KIMG + s3 * 2048 + trQB[1]);
-                dq_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, dq_acc, 0, 0, 0);
-            }
-#endif
-#if !(VT_PF && VT_DQM16)
-            STAMP(10, dq_acc[15]);
-#endif
-            if (has_cons) {
+            if (has_cons) {       // hand-off: wait for a free ring slot, store the tile (published a step later, above)
                 const int a = base + t;
                 int need = a - CH_R + 1;
                 if (t < CH_R && need > cons_end) need = cons_end;
                 if (need > 0) fl_wait(fl_cons_next, need, s_cons, spins_c);
-#if !VT_PF
-                if (t > 0) {
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                                   // vmcnt(0): tile t-1 is a step old
-                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)a, rfl, fl_ready_me, 0, CH_AUX);
-                }
-#endif
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-#if VT_PF && VT_DQM16
-                    const f32x4 v = dqt[j >> 1][j & 1];
-#else
                     const f32x4 v = {dq_acc[4 * j], dq_acc[4 * j + 1], dq_acc[4 * j + 2], dq_acc[4 * j + 3]};
-#endif
                     if (l2_next)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rt_mine, tile_voff + j * 1024, (a % CH_R) * 16384, 0);
                     else
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rt_mine, tile_voff + j * 1024, (a % CH_R) * 16384, CH_AUX);
                 }
-            } else {
+            } else {              // end of a chain: add the tile to dQ
                 const int soff = (int)((long long)t * 64 * p.dq_rs * 4);
-#if VT_PF && VT_DQM16
-                // register e of tile (a, b) = q row 16 a + 4 g + e, d = 16 b + (lane & 15): one atomic would cover 4 rows x 64 B.  v_permlane16_swap
-                // of the two d-tiles' registers (odd 16-lane rows of the first <-> even rows of the second) makes every atomic cover 2 rows x 128 B
-                // again: first result q = 16 a + 8 (G >> 1) + e, second q = 16 a + 4 + 8 (G >> 1) + e, both d = 16 (G & 1) + (lane & 15), G = lane >> 4
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // (inline asm: hipcc 7.2 feeds the FIRST result of __builtin_amdgcn_permlane16_swap to both users here)
-                        float x0 = dqt[a][0][e] * p.scale, x1 = dqt[a][1][e] * p.scale;
-                        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(x0), "+v"(x1));
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(x0, rdq, dq_voff, soff + (16 * a + e) * dq_rowb, VT_ATOM_AUX);
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(x1, rdq, dq_voff, soff + (16 * a + 4 + e) * dq_rowb, VT_ATOM_AUX);
-                    }
-#elif VT_ABL == 2
-#pragma unroll
-                for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(dq_acc[i]));
-                (void)soff;
-#else
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
                     __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dq_acc[i] * p.scale, rdq, dq_voff,
-                                                                    soff + ((i & 3) + 8 * (i >> 2)) * dq_rowb, VT_ATOM_AUX);
-#endif
+                                                                    soff + ((i & 3) + 8 * (i >> 2)) * dq_rowb, 0);
             }
             if (has_prod) __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + t + 1), rfl, fl_cons_me, 0, CH_AUX);
-#if VT_DQPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-            STAMP(11, stamp_dummy);
         }
     }
-#endif
-#if VT_STAMP
-    if (slot == STAMP_SLOT && base == 0) {
-        __syncthreads();
-        if (tid < 128) VT_CAT(vt_bwd_stamps, VT_SUFFIX)[tid] = ((const unsigned*)(smem + 132096))[tid];
-        if (tid == 0) { VT_CAT(vt_bwd_stamps, VT_SUFFIX)[128] = (unsigned)ROLE; VT_CAT(vt_bwd_stamps, VT_SUFFIX)[129] = (unsigned)id; }
-    }
-#endif
     if (dqw) {
         if ((has_prod || has_cons) && lane == 0 && (spins_r | spins_c)) {
             if (spins_r) atomicAdd(p.chain_ctr + 9, spins_r);
@@ -1087,7 +546,6 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
 
     // ---- epilogue: dK^T, dV^T accumulators -> dk[key][d], dv[key][d] ----
     const float dk_mul = PRESCALED ? 0.6931471805599453f : p.scale;
-#if VT_M16
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
         const int key = key0 + 32 * w + 16 * kt + c15;
@@ -1106,684 +564,8 @@ __device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, cha
             }
         }
     }
-#else
-    {
-        const int key = key0 + 32 * w + r;
-        if (key < p.S) {
-            bf16_t* dkp = p.dk + (size_t)b * p.dk_bs + (size_t)key * p.dk_rs + head * 64;
-            bf16_t* dvp = p.dv + (size_t)b * p.dv_bs + (size_t)key * p.dv_rs + head * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    u32x2 a, c;
-                    a[0] = pack2(dk_acc[dt][4 * gg + 0] * dk_mul, dk_acc[dt][4 * gg + 1] * dk_mul);
-                    a[1] = pack2(dk_acc[dt][4 * gg + 2] * dk_mul, dk_acc[dt][4 * gg + 3] * dk_mul);
-                    c[0] = pack2(dv_acc[dt][4 * gg + 0], dv_acc[dt][4 * gg + 1]);
-                    c[1] = pack2(dv_acc[dt][4 * gg + 2], dv_acc[dt][4 * gg + 3]);
-                    *(u32x2*)(dkp + 32 * dt + 8 * gg + 4 * h) = a;
-                    *(u32x2*)(dvp + 32 * dt + 8 * gg + 4 * h) = c;
-                }
-        }
-    }
-#endif
 }
 
-#else
-// ROLE: bit 0 = has a chain predecessor (takes its running dQ tiles), bit 1 = has a successor (hands its tiles on instead of
-// adding them atomically).  A template parameter, not a runtime flag: each role gets its own register allocation -- with
-// runtime flags the atomic-only path of the same binary ran 26 % slower than the kernel without any chain code.
-template <bool RAGGED, bool PRESCALED, int ROLE>
-__device__ __forceinline__ void BWD_BODY(const AttnBwdParams& p, char* smem, char* stage, const int id, const int slot,
-                                         const int cons_end, const int base, const bool l2_prev, const bool l2_next,
-                                         bool& dead) {
-    constexpr bool has_prod = (ROLE & 1) != 0, has_cons = (ROLE & 2) != 0;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, g = lane >> 4, ql = (lane & 15) >> 2, pl = lane & 3;
-    const int nkb = (p.S + 255) / 256;
-    const int kblk = id % nkb, bh = id / nkb;
-    const int head = bh % p.H, b = bh / p.H;
-    const int key0 = kblk * 256;
-
-    const bf16_t* qb = p.q + (size_t)b * p.q_bs + head * 64;
-    const bf16_t* kb_ = p.k + (size_t)b * p.k_bs + head * 64;
-    const bf16_t* vb = p.v + (size_t)b * p.v_bs + head * 64;
-    const bf16_t* dob = p.dout + (size_t)b * p.do_bs + head * 64;
-    __amdgpu_buffer_rsrc_t rq = make_rsrc(qb, (unsigned)((long long)(p.S - 1) * p.q_rs * 2 + 128));
-    __amdgpu_buffer_rsrc_t rk = make_rsrc(kb_, (unsigned)((long long)(p.S - 1) * p.k_rs * 2 + 128));
-    __amdgpu_buffer_rsrc_t rv = make_rsrc(vb, (unsigned)((long long)(p.S - 1) * p.v_rs * 2 + 128));
-    __amdgpu_buffer_rsrc_t rdo = make_rsrc(dob, (unsigned)((long long)(p.S - 1) * p.do_rs * 2 + 128));
-    // dQ accumulation buffer of this (batch, head): rows >= S are out of range -> the atomics are dropped by hardware
-    __amdgpu_buffer_rsrc_t rdq = make_rsrc(p.dq + (size_t)b * p.dq_bs + head * 64, (unsigned)((long long)(p.S - 1) * p.dq_rs * 4 + 256));
-    const float* lse_b = p.lse2 + (size_t)bh * p.S;
-    const float* dl_b = p.delta + (size_t)bh * p.S;
-
-    // ---- K block image (B operand of dQ) : 256 keys x 8 chunks ----
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        int i = tid + 256 * j;
-        int key = i >> 3, c = i & 7;
-        u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, (int)((key0 + key) * p.k_rs * 2) + c * 16, 0, 0));
-        *(u32x4*)(smem + KIMG + swz_off(key, c)) = v;
-    }
-    // ---- K / V fragments of this wave's 64 keys (B operands of S and dP), resident for the whole kernel ----
-    bf16x8 kf[2][4], vf[2][4];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int key = key0 + 64 * w + 32 * kb + r;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            kf[kb][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rk, (int)(key * p.k_rs * 2) + (16 * s + 8 * h) * 2, 0, 0));
-            vf[kb][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rv, (int)(key * p.v_rs * 2) + (16 * s + 8 * h) * 2, 0, 0));
-        }
-    }
-    // keys past the end of the sequence: a -1e30 column constant in the S accumulator makes P exactly 0
-    float kmask[2] = {0.f, 0.f};
-    if (RAGGED) {
-        kmask[0] = (key0 + 64 * w + r) < p.S ? 0.f : -1.0e30f;
-        kmask[1] = (key0 + 64 * w + 32 + r) < p.S ? 0.f : -1.0e30f;
-    }
-
-#if VT_STATMFMA
-    // B operands of the constant MFMAs: key (lane & 31), k = 8h..8h+7: ones against the three terms, the key mask against
-    // the 1.0 (S only); lanes 32-63 (k = 8..15) carry zeros
-    bf16x8 bS[2], bP;
-    {
-        const unsigned one2 = h == 0 ? 0x3f803f80u : 0u, one1 = h == 0 ? 0x00003f80u : 0u;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            const unsigned km = (RAGGED && h == 0) ? (pack2(0.f, kmask[kb]) & 0xffff0000u) : 0u;
-            const u32x4 v = {one2, one1 | km, 0u, 0u};
-            bS[kb] = __builtin_bit_cast(bf16x8, v);
-        }
-        const u32x4 vp = {one2, one1, 0u, 0u};
-        bP = __builtin_bit_cast(bf16x8, vp);
-    }
-#endif
-
-    // ---- per-lane LDS offsets ----
-    int rowrd[4];                         // row read of the Q / dO tile (A operand of S / dP), k-step s
-#pragma unroll
-    for (int s = 0; s < 4; ++s) rowrd[s] = r * 128 + (((2 * s + h) ^ swz_f(r)) << 4);
-    int trA[2][2];                        // transposed read of the Q / dO tile, [dt][sec]
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int sec = 0; sec < 2; ++sec) {
-            int fx = ((ql >> 1) << 2) | (sec << 1) | h;
-            trA[dt][sec] = (4 * h + ql + 8 * sec) * 128 + (((4 * dt + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
-        }
-    const int qs_w = w & 1, dt_w = w >> 1;
-    int trQA[2], trQB[2];                 // dQ phase: dS image (A) and K image (B), [sec]
-#pragma unroll
-    for (int sec = 0; sec < 2; ++sec) {
-        int fx = ((ql >> 1) << 2) | (h << 1) | sec;
-        int row = (8 * h + ql + 4 * sec) * 128;
-        trQA[sec] = row + (((4 * qs_w + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
-        trQB[sec] = row + (((4 * dt_w + 2 * (g & 1) + (pl >> 1)) ^ fx) << 4) + (pl & 1) * 8;
-    }
-    const int fr = swz_f(r);
-    // dQ atomics: byte offset of (row 32qs_w + 4h, column 32dt_w + r) inside a 64-row step; register i adds
-    // ((i&3) + 8(i>>2)) rows
-    const int dq_voff = (int)((32 * qs_w + 4 * h) * p.dq_rs * 4) + (32 * dt_w + r) * 4;
-    const int dq_rowb = (int)(p.dq_rs * 4);
-
-    // ---- dQ hand-off chain (see the header comment): has_prod / has_cons are workgroup-uniform ----
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    __amdgpu_buffer_rsrc_t rfl = make_rsrc(p.chain_flags, (unsigned)gridDim.x * 64u);
-    __amdgpu_buffer_rsrc_t rt_mine = make_rsrc(p.chain_tiles + (size_t)slot * (CH_R * 4096), CH_R * 16384);
-    const int fl_ready_me = (slot * 16 + wu) * 4, fl_cons_me = (slot * 16 + 8 + wu) * 4;
-    const int fl_ready_prod = ((slot - 1) * 16 + wu) * 4, fl_cons_next = ((slot + 1) * 16 + 8 + wu) * 4;
-    const int tile_voff = (wu * 256 + lane) * 16;          // + j * 1024, j = 0..3: registers 4j..4j+3 of the 32x32 dQ tile
-    const unsigned stage_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)stage;
-    i32x4w rt_prod_w;                                      // the predecessor's ring as raw descriptor words (inline asm operand)
-    {
-        const unsigned long long a = (unsigned long long)(p.chain_tiles + (size_t)(has_prod ? slot - 1 : slot) * (CH_R * 4096));
-        rt_prod_w = (i32x4w){(int)(unsigned)a, (int)((a >> 32) & 0xffffu), CH_R * 16384, 0x00020000};
-    }
-    // counter loads stay in a VGPR until the end-of-step barrier has waited for them anyway; only then are they moved to
-    // an SGPR (a readfirstlane anywhere else makes the compiler drain every outstanding memory operation on the spot)
-    auto fl_load = [&](int off) -> int { return (int)__builtin_amdgcn_raw_buffer_load_b32(rfl, off, 0, CH_AUX); };
-    int spins_r = 0, spins_c = 0;      // diagnostics: polls spent waiting for the predecessor / the successor
-    auto fl_wait = [&](int off, int need, int have, int& spins) {
-        int it = 0;
-#ifdef CH_NOWAIT            // timing-only ablation: never wait (results are wrong)
-        return;
-#endif
-        while (have < need && !dead) {
-            ++spins;
-            __builtin_amdgcn_s_sleep(4);
-            have = __builtin_amdgcn_readfirstlane(fl_load(off));
-            if (++it > CH_SPIN_LIMIT) { dead = true; p.chain_ctr[8] = 1; atomicAdd(p.chain_ctr + 16, 1); }
-        }
-    };
-
-    // ---- staging of the Q / dO tiles (64 rows x 8 chunks each): 2 + 2 chunks per thread (branch free) ----
-    int st_voq[2], st_vodo[2], st_lds[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int i = tid + 256 * j;
-        st_voq[j] = (int)((i >> 3) * p.q_rs * 2) + (i & 7) * 16;
-        st_vodo[j] = (int)((i >> 3) * p.do_rs * 2) + (i & 7) * 16;
-        st_lds[j] = swz_off(i >> 3, i & 7);
-    }
-    // row constants, staged in the form the MFMA accumulators want:  S'' = Q K^T - lse2/c  and  dP' = dO V^T - delta.
-    // threads t and t+128 stage the same value (keeps the loop body free of divergent branches).
-    const int stat_i = tid & 63;
-    const bool stat_is_lse = (tid & 64) == 0;
-    const float* stat_src = stat_is_lse ? lse_b : dl_b;
-    const float stat_mul = stat_is_lse ? (PRESCALED ? -1.0f : -1.0f / p.scale_log2) : -1.0f;
-    const int stat_lds = LSEOFF + (tid & 127) * 4;
-    u32x4 gq[2], gdo[2];
-    float gstat = 0.f;
-    auto gload = [&](int t) {
-        const int q0 = t * 64;
-        const int sq = (int)((long long)q0 * p.q_rs * 2), sdo = (int)((long long)q0 * p.do_rs * 2);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            gq[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rq, st_voq[j], sq, 0));
-            gdo[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rdo, st_vodo[j], sdo, 0));
-        }
-        int qi = q0 + stat_i;
-        const bool ok = qi < p.S;
-        qi = ok ? qi : p.S - 1;
-        const float v = stat_src[qi] * stat_mul;
-        gstat = ok ? v : 0.f;
-    };
-    auto lstore = [&](int buf) {
-        char* base = smem + QTILE + buf * 16384;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            *(u32x4*)(base + st_lds[j]) = gq[j];
-            *(u32x4*)(base + 8192 + st_lds[j]) = gdo[j];
-        }
-        *(float*)(smem + stat_lds + buf * 512) = gstat;
-#if VT_STATMFMA
-        {   // A-operand row of the constant: k = 0..2 hold hi + mid + lo (exact to 24 bits), k = 3 holds 1.0 (it multiplies
-            // the key-mask column of the B operand); the second 16-byte chunk (k = 8..15, lanes 32-63) is zero
-            const float x0 = gstat;
-            const float h0 = bf2f(f2bf(x0));
-            const float x1 = x0 - h0;
-            const float h1 = bf2f(f2bf(x1));
-            const float x2 = x1 - h1;
-            const u32x4 c0 = {pack2(h0, h1), pack2(x2, 1.0f), 0u, 0u};
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            char* dst = smem + STATF + buf * 4096 + (stat_is_lse ? 0 : 2048) + stat_i * 32;
-            *(u32x4*)dst = c0;
-            *(u32x4*)(dst + 16) = z;
-        }
-#endif
-    };
-
-    f32x16 dk_acc[2][2], dv_acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { dk_acc[a][c][i] = 0.f; dv_acc[a][c][i] = 0.f; }
-
-    const float sc = p.scale_log2;
-    const int nsteps = (p.S + 63) / 64;
-    // dQ tile of the PREVIOUS step: its 16 atomics are drained one at a time between the MFMAs of the current step
-    // (a 16-deep burst per wave, from every CU at once, saturates the memory-side atomic units)
-    float dq_prev[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) dq_prev[i] = 0.f;
-    int pf_ready = 0;
-    if (has_prod) pf_ready = fl_load(fl_ready_prod);       // decides the tile-0 DMA; every later one is fetched a step ahead
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    int s_ready = has_prod ? __builtin_amdgcn_readfirstlane(pf_ready) : 0;
-    for (int t = 0; t < nsteps; ++t) {
-        const int buf = t & 1;
-        // chain traffic is issued a full step before its result is needed (one wave per SIMD: nothing hides a miss)
-        int pf_cons = 0;
-        if (has_prod) {
-            // predecessor's tile t must be public.  The counter at hand is a step old, and a consumer that passes with no
-            // margin is stopped again by the next hiccup of its producer, each time for a full uncached round trip that
-            // its own successors then inherit: when it does have to wait, it waits until the producer is CH_HYST tiles
-            // ahead, and then coasts on that slack.
-            if (s_ready < base + t + 1)
-                fl_wait(fl_ready_prod, base + (t + 1 + CH_HYST < nsteps ? t + 1 + CH_HYST : nsteps), s_ready, spins_r);
-            // LDS-DMA of the 4 x 1 KiB of this wave.  Issued through inline asm: the compiler orders every later LDS
-            // access of the step behind an LDS-DMA it knows about (s_waitcnt vmcnt(0) a few instructions into the step).
-            // Safe because these are the OLDEST memory operations of the step -- every wait the compiler computes for a
-            // younger load also covers them (vmcnt retires in order) -- and the end-of-step barrier drains the pipeline
-            // before the staging area is read.
-#ifndef CH_NODMA
-            // cache policy: the predecessor shares this XCD's L2 (l2_prev: its plain stores are there) -> agent-scope
-            // load, L1 bypassed; otherwise system scope against its write-through stores
-            if (l2_prev) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                                 :: "s"(stage_lds + wu * 4096 + j * 1024), "v"(tile_voff + j * 1024), "s"(rt_prod_w),
-                                    "s"(((base + t) % CH_R) * 16384) : "memory");
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc0 sc1 lds"
-                                 :: "s"(stage_lds + wu * 4096 + j * 1024), "v"(tile_voff + j * 1024), "s"(rt_prod_w),
-                                    "s"(((base + t) % CH_R) * 16384) : "memory");
-            }
-#endif
-            pf_ready = fl_load(fl_ready_prod);                                             // for step t + 1
-        }
-        if (has_cons) pf_cons = fl_load(fl_cons_next);                                     // for the ring check at the end of this step
-        gload(t + 1);                                  // past the end: bounds-checked loads return zeros
-        const char* qimg = smem + QTILE + buf * 16384;
-        const char* doimg = qimg + 8192;
-        const float* lsel = (const float*)(smem + LSEOFF + buf * 512);
-        char* dsimg = smem + DSIMG + buf * 32768;
-
-#if VT_PIPE
-        // ---- software-pipelined tile schedule -------------------------------------------------------------
-        // Tiles j = 0..3 = (qs, kb) = (0,0) (0,1) (1,0) (1,1).  With one wave per SIMD nothing else hides an MFMA's
-        // latency, so the VALU work of tile j (exp2, dS, bf16 packing: SM) is interleaved in program order with 16
-        // MFMAs that do not depend on it: the dV/dK products of tile j-1 (PV) and the S/dP products of tile j+1 (QK).
-        auto rowfrags = [&](int qs, bf16x8 (&qa)[4], bf16x8 (&doa)[4]) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                qa[s] = *(const bf16x8*)(qimg + qs * 4096 + rowrd[s]);
-                doa[s] = *(const bf16x8*)(doimg + qs * 4096 + rowrd[s]);
-            }
-        };
-        auto trfrags = [&](int qs, bf16x8 (&qT)[2][2], bf16x8 (&doT)[2][2]) {
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int ro = (32 * qs + 16 * s2) * 128;
-                    qT[s2][dt] = tr_pair(qimg + ro + trA[dt][0], qimg + ro + trA[dt][1]);
-                    doT[s2][dt] = tr_pair(doimg + ro + trA[dt][0], doimg + ro + trA[dt][1]);
-                }
-        };
-        // accumulator init = row constants straight from LDS:  S'' starts at -lse2/c (+ key mask), dP' at -delta;
-        // accumulator register 4g'+e <-> q = 32qs + 8g' + 4h + e
-#if VT_STATMFMA
-        // S'' and dP' start from ONE extra MFMA each: (row constant as an A operand) x (ones / key mask as a B operand), C = 0
-        const char* statf = smem + STATF + buf * 4096 + r * 32 + h * 16;
-        auto qk_init = [&](int qs, int kb, f32x16& sacc, f32x16& pacc) {
-            const bf16x8 al = *(const bf16x8*)(statf + qs * 1024);
-            const bf16x8 ad = *(const bf16x8*)(statf + 2048 + qs * 1024);
-            f32x16 z;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) z[i] = 0.f;
-            sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bS[kb], z, 0, 0, 0);
-            pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ad, bP, z, 0, 0, 0);
-        };
-#else
-        auto qk_init = [&](int qs, int kb, f32x16& sacc, f32x16& pacc) {
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                f32x4 a = *(const f32x4*)(lsel + 32 * qs + 8 * gg + 4 * h);
-                f32x4 c = *(const f32x4*)(lsel + 64 + 32 * qs + 8 * gg + 4 * h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { sacc[4 * gg + e] = RAGGED ? a[e] + kmask[kb] : a[e]; pacc[4 * gg + e] = c[e]; }
-            }
-        };
-#endif
-        // MFMA number m (0..7) of QK: k-step m>>1, S for even m, dP for odd m
-        auto qk_mfma = [&](int m, int kb, const bf16x8 (&qa)[4], const bf16x8 (&doa)[4], f32x16& sacc, f32x16& pacc) {
-            if ((m & 1) == 0) sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[m >> 1], kf[kb][m >> 1], sacc, 0, 0, 0);
-            else pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa[m >> 1], vf[kb][m >> 1], pacc, 0, 0, 0);
-        };
-        // MFMA number m (0..7) of PV: s2 = m>>2, dt = (m>>1)&1, dV for even m, dK for odd m
-        auto pv_mfma = [&](int m, int kb, const bf16x8 (&qT)[2][2], const bf16x8 (&doT)[2][2], const unsigned (&pw)[8],
-                           const unsigned (&dw)[8]) {
-            const int s2 = m >> 2, dt = (m >> 1) & 1;
-            if ((m & 1) == 0) {
-                const u32x4 pb4 = {pw[4 * s2], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-                dv_acc[kb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doT[s2][dt], __builtin_bit_cast(bf16x8, pb4), dv_acc[kb][dt], 0, 0, 0);
-            } else {
-                const u32x4 db4 = {dw[4 * s2], dw[4 * s2 + 1], dw[4 * s2 + 2], dw[4 * s2 + 3]};
-                dk_acc[kb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qT[s2][dt], __builtin_bit_cast(bf16x8, db4), dk_acc[kb][dt], 0, 0, 0);
-            }
-        };
-        auto sm_pair = [&](int i, const f32x16& sacc, const f32x16& pacc, unsigned (&pw)[8], unsigned (&dw)[8]) {
-#if VT_ABL == 3
-            const float p0 = sacc[2 * i], p1 = sacc[2 * i + 1];
-#else
-            const float p0 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i] : sacc[2 * i] * sc);
-            const float p1 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i + 1] : sacc[2 * i + 1] * sc);
-#endif
-            pw[i] = pack2(p0, p1);
-            dw[i] = pack2(p0 * pacc[2 * i], p1 * pacc[2 * i + 1]);
-        };
-        auto wr_ds = [&](int qs, int kb, const unsigned (&dw)[8]) {
-#if VT_ABL == 4
-            return;
-#endif
-            char* drow = dsimg + (64 * w + 32 * kb + r) * 128 + 8 * h;
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                u32x2 two = {dw[2 * gg], dw[2 * gg + 1]};
-                *(u32x2*)(drow + (((4 * qs + gg) ^ fr) << 4)) = two;
-            }
-        };
-        const int soff_prev = (int)((long long)(t - 1) * 64 * p.dq_rs * 4);     // t == 0: negative row offset -> dropped? no: guarded
-        auto drain = [&](int i) {
-#if VT_DRAIN && VT_ABL != 1 && VT_ABL != 2
-            if (t > 0)
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dq_prev[i], rdq, dq_voff + ((i & 3) + 8 * (i >> 2)) * dq_rowb,
-                                                                soff_prev, 0);
-#endif
-        };
-        f32x16 sA, pA, sB, pB;
-        bf16x8 qa[4], doa[4], qT[2][2], doT[2][2];
-        unsigned pwA[8], dwA[8], pwB[8], dwB[8];
-#if VT_DQSHIFT
-        // dQ tile of the PREVIOUS step (its dS image sits in the other buffer): 16 MFMAs that depend on nothing in this
-        // step, issued inside the two slots that have only 8 MFMAs for 8 softmax pairs (operands one k-step ahead)
-        const char* dsprev = smem + DSIMG + (buf ^ 1) * 32768;
-        f32x16 dqp;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dqp[i] = 0.f;
-        bf16x8 ra[2], rb[2];
-        auto dq_load = [&](int s3, int slot) {
-            ra[slot] = tr_pair(dsprev + s3 * 2048 + trQA[0], dsprev + s3 * 2048 + trQA[1]);
-            rb[slot] = tr_pair(smem + KIMG + s3 * 2048 + trQB[0], smem + KIMG + s3 * 2048 + trQB[1]);
-        };
-        dq_load(0, 0);
-#endif
-        rowfrags(0, qa, doa);
-        qk_init(0, 0, sA, pA);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) qk_mfma(m, 0, qa, doa, sA, pA);            // QK(0): exposed
-        trfrags(0, qT, doT);
-        // slot 0: QK(1) || SM(0)
-        qk_init(0, 1, sB, pB);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            qk_mfma(m, 1, qa, doa, sB, pB);
-#if VT_DQSHIFT
-            dq_load(m + 1, (m + 1) & 1);                  // k-step 8 is loaded here for slot 3
-            dqp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[m & 1], rb[m & 1], dqp, 0, 0, 0);
-#endif
-            sm_pair(m, sA, pA, pwA, dwA);
-            if (m & 1) drain(m >> 1);
-        }
-        rowfrags(1, qa, doa);
-        wr_ds(0, 0, dwA);
-        // slot 1: PV(0) + QK(2) || SM(1)
-        qk_init(1, 0, sA, pA);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            pv_mfma(m, 0, qT, doT, pwA, dwA);
-            qk_mfma(m, 0, qa, doa, sA, pA);
-            sm_pair(m, sB, pB, pwB, dwB);
-            if (m & 1) drain(4 + (m >> 1));
-        }
-        wr_ds(0, 1, dwB);
-        // slot 2: PV(1) + QK(3) || SM(2)
-        qk_init(1, 1, sB, pB);
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            pv_mfma(m, 1, qT, doT, pwB, dwB);
-            qk_mfma(m, 1, qa, doa, sB, pB);
-            sm_pair(m, sA, pA, pwA, dwA);
-            if (m & 1) drain(8 + (m >> 1));
-        }
-        wr_ds(1, 0, dwA);
-        trfrags(1, qT, doT);
-        // slot 3: PV(2) || SM(3)
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            pv_mfma(m, 0, qT, doT, pwA, dwA);
-#if VT_DQSHIFT
-            if (m + 1 < 8) dq_load(8 + m + 1, (m + 1) & 1);
-            dqp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[m & 1], rb[m & 1], dqp, 0, 0, 0);
-#endif
-            sm_pair(m, sB, pB, pwB, dwB);
-            if (m & 1) drain(12 + (m >> 1));
-        }
-        wr_ds(1, 1, dwB);
-        // PV(3): exposed
-#pragma unroll
-        for (int m = 0; m < 8; ++m) pv_mfma(m, 1, qT, doT, pwB, dwB);
-#else
-#pragma unroll
-        for (int qs = 0; qs < 2; ++qs) {
-            // row constants of this 32-query sub-slice: accumulator register 4g'+e <-> q = 32qs + 8g' + 4h + e
-            f32x16 lneg, dneg;
-#pragma unroll
-            for (int gg = 0; gg < 4; ++gg) {
-                f32x4 a = *(const f32x4*)(lsel + 32 * qs + 8 * gg + 4 * h);
-                f32x4 c = *(const f32x4*)(lsel + 64 + 32 * qs + 8 * gg + 4 * h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { lneg[4 * gg + e] = a[e]; dneg[4 * gg + e] = c[e]; }
-            }
-            bf16x8 qa[4], doa[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                qa[s] = *(const bf16x8*)(qimg + qs * 4096 + rowrd[s]);
-                doa[s] = *(const bf16x8*)(doimg + qs * 4096 + rowrd[s]);
-            }
-            bf16x8 qT[2][2], doT[2][2];   // [s'][dt]
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) {
-                    const int ro = (32 * qs + 16 * s2) * 128;
-                    qT[s2][dt] = tr_pair(qimg + ro + trA[dt][0], qimg + ro + trA[dt][1]);
-                    doT[s2][dt] = tr_pair(doimg + ro + trA[dt][0], doimg + ro + trA[dt][1]);
-                }
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                f32x16 sacc = lneg, pacc = dneg;
-                if (RAGGED) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) sacc[i] += kmask[kb];
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[s], kf[kb][s], sacc, 0, 0, 0);
-                    pacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doa[s], vf[kb][s], pacc, 0, 0, 0);
-                }
-                // P = exp2(c * S''), dS = P * dP'; both packed to bf16 pairs (B operands + dS image)
-                unsigned int pw[8], dw[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float p0 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i] : sacc[2 * i] * sc);
-                    const float p1 = __builtin_amdgcn_exp2f(PRESCALED ? sacc[2 * i + 1] : sacc[2 * i + 1] * sc);
-                    pw[i] = pack2(p0, p1);
-                    dw[i] = pack2(p0 * pacc[2 * i], p1 * pacc[2 * i + 1]);
-                }
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    const u32x4 pb4 = {pw[4 * s2], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-                    const u32x4 db4 = {dw[4 * s2], dw[4 * s2 + 1], dw[4 * s2 + 2], dw[4 * s2 + 3]};
-                    const bf16x8 pb = __builtin_bit_cast(bf16x8, pb4), dsb = __builtin_bit_cast(bf16x8, db4);
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        dv_acc[kb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(doT[s2][dt], pb, dv_acc[kb][dt], 0, 0, 0);
-                        dk_acc[kb][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qT[s2][dt], dsb, dk_acc[kb][dt], 0, 0, 0);
-                    }
-                }
-                // dS image: row = key (64w + 32kb + r), 8 bytes = q 32qs + 8g' + 4h + (0..3)
-                char* drow = dsimg + (64 * w + 32 * kb + r) * 128 + 8 * h;
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    u32x2 two = {dw[2 * gg], dw[2 * gg + 1]};
-                    *(u32x2*)(drow + (((4 * qs + gg) ^ fr) << 4)) = two;
-                }
-            }
-        }
-#endif
-        lstore(buf ^ 1);
-        __syncthreads();
-        // the barrier drained the memory pipeline: the counters fetched at the top of the step are free to read now
-        if (has_prod) s_ready = __builtin_amdgcn_readfirstlane(pf_ready);
-        const int s_cons = has_cons ? __builtin_amdgcn_readfirstlane(pf_cons) : 0;
-
-#if VT_ABL != 1
-#if VT_PIPE && VT_DQSHIFT
-        // ---- atomics of the dQ tile that was accumulated during this step (it belongs to step t-1) ----
-        if (t > 0)
-        {
-            const int soff = (int)((long long)(t - 1) * 64 * p.dq_rs * 4);
-#if VT_ABL == 2
-#pragma unroll
-            for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(dqp[i]));
-#else
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dqp[i] * p.scale, rdq,
-                                                                dq_voff + ((i & 3) + 8 * (i >> 2)) * dq_rowb, soff, 0);
-#endif
-        }
-#else
-        // ---- dQ tile (32 q x 32 d) of this wave over all 256 keys ----
-        f32x16 dq_acc;
-        if (has_prod) {
-            // running sum of the chain so far (landed in LDS by the DMA issued mid-step; the barrier above waited for it)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 v = *(const f32x4*)(stage + wu * 4096 + j * 1024 + lane * 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dq_acc[4 * j + e] = v[e];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) dq_acc[i] = 0.f;
-        }
-        {
-            // operands are fetched two k-steps ahead of the MFMA that consumes them (one wave per SIMD: nothing else
-            // hides the LDS latency)
-            bf16x8 fa[3], fb[3];
-#pragma unroll
-            for (int s3 = 0; s3 < 2; ++s3) {
-                fa[s3] = tr_pair(dsimg + s3 * 2048 + trQA[0], dsimg + s3 * 2048 + trQA[1]);
-                fb[s3] = tr_pair(smem + KIMG + s3 * 2048 + trQB[0], smem + KIMG + s3 * 2048 + trQB[1]);
-            }
-#pragma unroll
-            for (int s3 = 0; s3 < 16; ++s3) {
-                if (s3 + 2 < 16) {
-                    fa[(s3 + 2) % 3] = tr_pair(dsimg + (s3 + 2) * 2048 + trQA[0], dsimg + (s3 + 2) * 2048 + trQA[1]);
-                    fb[(s3 + 2) % 3] = tr_pair(smem + KIMG + (s3 + 2) * 2048 + trQB[0], smem + KIMG + (s3 + 2) * 2048 + trQB[1]);
-                }
-                dq_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s3 % 3], fb[s3 % 3], dq_acc, 0, 0, 0);
-            }
-        }
-        if (has_cons) {
-            // hand the running sum to the next key block.  Ring slot a % CH_R is free once its previous tile was consumed:
-            // tile a - CH_R, or -- in the first CH_R steps -- a tile of the last generation that had a successor
-            // (cons_end = absolute step count at the end of that generation, 0 if there was none).
-            const int a = base + t;
-            int need = a - CH_R + 1;
-            if (t < CH_R && need > cons_end) need = cons_end;
-            if (need > 0) fl_wait(fl_cons_next, need, s_cons, spins_c);
-            if (t > 0) {
-                // the stores of tile t-1 are a full step old: once acknowledged, tiles up to t-1 are public
-                __builtin_amdgcn_s_waitcnt(0x0F70);                                   // vmcnt(0)
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)a, rfl, fl_ready_me, 0, CH_AUX);
-            }
-#ifndef CH_NOST
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 v = {dq_acc[4 * j], dq_acc[4 * j + 1], dq_acc[4 * j + 2], dq_acc[4 * j + 3]};
-                // successor on this XCD: the tile only has to reach the shared L2; otherwise write through to memory
-                if (l2_next)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rt_mine, tile_voff + j * 1024,
-                                                           (a % CH_R) * 16384, 0);
-                else
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rt_mine, tile_voff + j * 1024,
-                                                           (a % CH_R) * 16384, CH_AUX);
-            }
-#else
-#pragma unroll
-            for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(dq_acc[i]));
-#endif
-        } else {
-            const int soff = (int)((long long)(t) * 64 * p.dq_rs * 4);
-#if VT_ABL == 2
-#pragma unroll
-            for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(dq_acc[i]));
-#else
-#pragma unroll
-            for (int i = 0; i < 16; ++i)      // the row of register i goes into the scalar offset: one address VGPR, not 16
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dq_acc[i] * p.scale, rdq, dq_voff,
-                                                                soff + ((i & 3) + 8 * (i >> 2)) * dq_rowb, 0);
-#endif
-        }
-        if (has_prod) __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + t + 1), rfl, fl_cons_me, 0, CH_AUX);   // tile t consumed
-#endif
-#endif
-    }
-    if ((has_prod || has_cons) && lane == 0 && (spins_r | spins_c)) {
-        if (spins_r) atomicAdd(p.chain_ctr + 9, spins_r);
-        if (spins_c) atomicAdd(p.chain_ctr + 10, spins_c);
-    }
-    if (has_cons) {     // the last tile
-        __builtin_amdgcn_s_waitcnt(0x0F70);
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)(base + nsteps), rfl, fl_ready_me, 0, CH_AUX);
-    }
-
-#if VT_PIPE && VT_DQSHIFT && VT_ABL != 1
-    {   // the last step's dQ tile: nobody computes it "one step later"
-        const char* dslast = smem + DSIMG + ((nsteps - 1) & 1) * 32768;
-        f32x16 dq_acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dq_acc[i] = 0.f;
-        {
-            // operands are fetched two k-steps ahead of the MFMA that consumes them (one wave per SIMD: nothing else
-            // hides the LDS latency)
-            bf16x8 fa[3], fb[3];
-#pragma unroll
-            for (int s3 = 0; s3 < 2; ++s3) {
-                fa[s3] = tr_pair(dslast + s3 * 2048 + trQA[0], dslast + s3 * 2048 + trQA[1]);
-                fb[s3] = tr_pair(smem + KIMG + s3 * 2048 + trQB[0], smem + KIMG + s3 * 2048 + trQB[1]);
-            }
-#pragma unroll
-            for (int s3 = 0; s3 < 16; ++s3) {
-                if (s3 + 2 < 16) {
-                    fa[(s3 + 2) % 3] = tr_pair(dslast + (s3 + 2) * 2048 + trQA[0], dslast + (s3 + 2) * 2048 + trQA[1]);
-                    fb[(s3 + 2) % 3] = tr_pair(smem + KIMG + (s3 + 2) * 2048 + trQB[0], smem + KIMG + (s3 + 2) * 2048 + trQB[1]);
-                }
-                dq_acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s3 % 3], fb[s3 % 3], dq_acc, 0, 0, 0);
-            }
-        }
-        {
-            const int soff = (int)((long long)(nsteps - 1) * 64 * p.dq_rs * 4);
-#if VT_ABL == 2
-#pragma unroll
-            for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(dq_acc[i]));
-#else
-#pragma unroll
-            for (int i = 0; i < 16; ++i)      // the row of register i goes into the scalar offset: one address VGPR, not 16
-                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(dq_acc[i] * p.scale, rdq, dq_voff,
-                                                                soff + ((i & 3) + 8 * (i >> 2)) * dq_rowb, 0);
-#endif
-        }
-    }
-#endif
-    // ---- epilogue: dK^T, dV^T accumulators -> dk[key][d], dv[key][d] ----
-    const float dk_mul = PRESCALED ? 0.6931471805599453f : p.scale;
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-        const int key = key0 + 64 * w + 32 * kb + r;
-        if (key < p.S) {
-            bf16_t* dkp = p.dk + (size_t)b * p.dk_bs + (size_t)key * p.dk_rs + head * 64;
-            bf16_t* dvp = p.dv + (size_t)b * p.dv_bs + (size_t)key * p.dv_rs + head * 64;
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-                for (int gg = 0; gg < 4; ++gg) {
-                    u32x2 a, c;
-                    a[0] = pack2(dk_acc[kb][dt][4 * gg + 0] * dk_mul, dk_acc[kb][dt][4 * gg + 1] * dk_mul);
-                    a[1] = pack2(dk_acc[kb][dt][4 * gg + 2] * dk_mul, dk_acc[kb][dt][4 * gg + 3] * dk_mul);
-                    c[0] = pack2(dv_acc[kb][dt][4 * gg + 0], dv_acc[kb][dt][4 * gg + 1]);
-                    c[1] = pack2(dv_acc[kb][dt][4 * gg + 2], dv_acc[kb][dt][4 * gg + 3]);
-                    *(u32x2*)(dkp + 32 * dt + 8 * gg + 4 * h) = a;
-                    *(u32x2*)(dvp + 32 * dt + 8 * gg + 4 * h) = c;
-                }
-        }
-    }
-}
-
-#endif   // VT_W8
 
 #if VT_CLK
 __device__ unsigned VT_CAT(vt_bwd_clk, VT_SUFFIX)[4];
@@ -1807,7 +589,6 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void BWD_KERNEL(AttnBwdParams p) {
     int cons_end = 0;
     int gen = 0;
     bool l2_prev = false, l2_next = false;
-#if VT_CHAIN
     if (L > 1) {
         // Which neighbours share this workgroup's XCD (and therefore its L2)?  Every slot publishes 1 + XCC_ID once; chain
         // neighbours on the same XCD exchange their tiles through the L2 (plain stores, agent-scope loads), any other
@@ -1832,17 +613,14 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void BWD_KERNEL(AttnBwdParams p) {
         }
         if ((j % L) != L - 1 && j != spx - 1 && slot + 1 < (int)gridDim.x) l2_next = peer(slot + 1) == xcc;
     }
-#endif
     for (int item = slot; item < nitems; item += gridDim.x, ++gen) {
         const int kblk = item % nkb;
         bool has_prod = false, has_cons = false;
-#if VT_CHAIN
         if (L > 1) {
             const int j = slot % spx;         // chains: same head, same XCD, at most L long, aligned to multiples of L
             has_prod = (j % L) != 0 && kblk != 0;
             has_cons = (j % L) != L - 1 && j != spx - 1 && kblk != nkb - 1 && item + 1 < nitems;
         }
-#endif
         // block-uniform: only the last key block of a head is ragged
         const bool ragged = (kblk + 1) * 256 > p.S;
         const int role = (has_prod ? 1 : 0) | (has_cons ? 2 : 0);
@@ -1852,16 +630,12 @@ __global__ __launch_bounds__(BWD_THREADS, 1) void BWD_KERNEL(AttnBwdParams p) {
         unsigned long long clk0, rt0;
         asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(clk0), "=s"(rt0) :: "memory");
 #endif
-#if VT_CHAIN
         switch (role) {
             case 0: if (ragged) VT_BWD_CALL(true, 0); else VT_BWD_CALL(false, 0); break;
             case 1: if (ragged) VT_BWD_CALL(true, 1); else VT_BWD_CALL(false, 1); break;     // a ragged block ends its head: never a producer
             case 2: VT_BWD_CALL(false, 2); break;
             default: VT_BWD_CALL(false, 3); break;
         }
-#else
-        if (ragged) VT_BWD_CALL(true, 0); else VT_BWD_CALL(false, 0);
-#endif
 #undef VT_BWD_CALL
 #if VT_CLK
         {
@@ -2006,11 +780,6 @@ extern "C" int BWD_ENTRY(const void* q, const void* k, const void* v, const void
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
-#if VT_STAMP
-extern "C" int VT_CAT(vt_attn_bwd_stamps, VT_SUFFIX)(unsigned* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(VT_CAT(vt_bwd_stamps, VT_SUFFIX)), 256 * sizeof(unsigned)) == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-}
-#endif
 // bytes of chain workspace vt_attn_bwd_hd64 wants for this problem (0: chains are disabled on this device / by VT_BWD_CHAIN=1)
 extern "C" long long VT_CAT(vt_attn_bwd_chain_ws_bytes, VT_SUFFIX)(int B, int H, int S) {
     if (B <= 0 || H <= 0 || S <= 0 || bwd_chain_len() <= 1) return 0;

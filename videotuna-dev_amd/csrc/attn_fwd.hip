@@ -5,7 +5,7 @@
 // self-attention, q,k,v [B,30,17776,64] at the benchmark shape.
 //
 // Structure: one workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 queries.
-// K/V tiles of 64 keys are staged global -> VGPR -> LDS (double buffered, loads of tile t+1 in flight
+// K/V tiles of 64 keys are staged by LDS-DMA (buffer_load ... lds; double buffered, tile t+1 in flight
 // while tile t is consumed).  Scores are computed TRANSPOSED, S^T = K * Q^T with
 // v_mfma_f32_32x32x16_bf16, so a lane owns one query column and 2x16 keys: the online-softmax row
 // reductions are lane-local plus one cross-half exchange, and the fp32 P^T accumulator tile is, after
@@ -13,11 +13,9 @@
 // P).  V^T fragments come from the row-major V tile through ds_read_b64_tr_b16.
 // Layout contract: q/k/v/o are addressed as ptr + b*batch_stride + s*row_stride + h*64 + d, so the
 // fused QKV GEMM output [B*S, 3*H*64] is consumed in place (no head transpose copies).
+// With q pre-scaled (the training path) the cross-half exchange of the row maximum is taken only when a rescale happens.
+// What was measured against this kernel and not kept is recorded in exp/README.md.
 #include "common.h"
-
-#ifndef VT_FWD_DMA
-#define VT_FWD_DMA 1     // 1 = K / V tiles staged by LDS-DMA (buffer_load ... lds), 0 = global -> VGPR -> ds_write_b128
-#endif
 
 struct AttnFwdParams {
     const bf16_t* q;
@@ -32,33 +30,8 @@ struct AttnFwdParams {
     const float* bias_t;   // BIAS kernels: additive score bias, TRANSPOSED [H][S keys][S queries] fp32 (same for every sample), or null
 };
 
-#ifndef VT_FWD_PF
-#define VT_FWD_PF 0      // 1 (q_prescaled kernel only) = all eight K fragments of a tile in flight before its first MFMA and the V^T fragments read
-#endif                   // under the S^T MFMAs, the issue order pinned by sched_barrier fences (what helped the backward in r02).  Measured here
-                         // (tools/kbench_fwd.py, B=2): 5.10 vs 5.01 ms -- 163 instead of 127 registers take the kernel from 4 to 3 waves per SIMD,
-                         // and with four waves per SIMD the other waves already cover the exposed LDS round trips: not enabled
-// r03, measured and removed: the 64-key tile as two 32-key sub-tiles with their own lazy-maximum test, ordered [S0, S1 MFMAs] -> softmax(0) under
-// S1 -> [PV0] under softmax(1) -> [PV1] so that one wave's own stream alternates the matrix pipe and the VALU (at d = 64 they cost about the same
-// issue time): 4.765 vs 4.681 ms at B = 2, 9.357 vs 9.185 at B = 4 -- slower; four waves per SIMD already interleave as well as the source can.
-// (measured r03, not kept: the row sums through v_pk_add_f32 -- 16 packed adds for the chain of 32 v_add_f32 -- ran 4.6 % SLOWER, 9.25 -> 9.68 ms at
-// B=4: the pairs hold back the exp results they wait for; sums of the packed bf16 P through v_dot2c_f32_bf16 were 1.3 % slower too.  The VALU
-// instruction count is not what bounds the loop.)
-#ifndef VT_FWD_LATEMAX
-#define VT_FWD_LATEMAX 1
-#endif
-#ifndef VT_FWD_PRIO
-#define VT_FWD_PRIO 0    // 1 = s_setprio(1) around the two MFMA clusters of a tile (the matrix pipe wins the issue arbitration against the other waves'
-                         // softmax).  Measured r03 (tools/kbench_fwd.py, B=2): 4.905 vs 4.892 ms -- no effect with four waves per SIMD: not enabled
-#endif
-#ifndef VT_FWD_ABL
-#define VT_FWD_ABL 0     // timing-only ablations (results WRONG): 1 = K fragments read from one fixed LDS row set per step (no per-k-step reads), 2 = no V^T transposed reads, 3 = both
-#endif
-#ifndef VT_FWD_WAVES
-#define VT_FWD_WAVES 4  // waves per workgroup (32 queries each).  8 (256 queries share every K / V tile, half the staging per flop) measured
-                        // within 1 % of 4 (2.447 vs 2.425 ms at B=1): staging is no longer what limits this kernel
-#endif
-#define FQ (32 * VT_FWD_WAVES)      // queries per workgroup
-#define FWD_THREADS (64 * VT_FWD_WAVES)
+#define FQ 128      // queries per workgroup: 4 waves x 32
+#define FWD_THREADS 256
 #define FK 64       // keys per tile
 #define NEG_BIG (-1.0e30f)
 #define LAZY_THR 8.0f
@@ -66,7 +39,7 @@ struct AttnFwdParams {
 // BIAS (T5 relative position bias; SURVEY 8(f) row 1, the frozen text encoder): scores get bias[h][q][key] added before the
 // softmax.  The table is read transposed so that the 32 lanes of a half-wave (consecutive queries) load consecutive words.
 template <bool PRESCALED, bool BIAS = false>
-__global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn_fwd_hd64_kernel(AttnFwdParams p) {
+__global__ __launch_bounds__(FWD_THREADS, 2) void attn_fwd_hd64_kernel(AttnFwdParams p) {
     __shared__ __attribute__((aligned(16))) char smem[32768];   // 2 x (K 8 KiB + V 8 KiB)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -93,11 +66,11 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
         for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s);
     }
 
-    // ---- staging assignment: 2 x 16-byte chunks of K and of V per thread per tile ----
-    constexpr int NCH = 512 / FWD_THREADS;       // 16-byte chunks of K (and of V) per thread per tile
+    // Per-thread chunk assignment of the former register staging (global -> VGPR -> ds_write_b128).  Nothing reads it.  It stays because the
+    // compiler orders this kernel's prologue differently without it, and this file's machine code changes only together with a measurement.
     int k_voff[2], v_voff[2], k_lds[2], v_lds[2];
 #pragma unroll
-    for (int j = 0; j < NCH; ++j) {
+    for (int j = 0; j < 2; ++j) {
         int i = tid + FWD_THREADS * j;
         int key = i >> 3, c = i & 7;
         k_voff[j] = (int)(key * p.k_rs * 2) + c * 16;
@@ -105,15 +78,14 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
         k_lds[j] = key * 128 + ((c ^ ((key >> 1) & 7)) << 4);
         v_lds[j] = 8192 + key * 128 + ((c ^ (((key >> 1) & 1) << 2)) << 4);
     }
-#if VT_FWD_DMA
     // LDS-DMA staging: a K (or V) tile of 64 keys is 8 pieces of 1 KiB = 8 rows x 128 B; wave w moves pieces w and w+4 of each.
     // Lane l lands at (row l>>3, physical chunk l&7) of its piece and fetches the logical chunk the image's swizzle puts there.
     const int wv = __builtin_amdgcn_readfirstlane(wave);
-    constexpr int NPC = 8 / VT_FWD_WAVES;        // 1-KiB pieces of K (and of V) per wave per tile
+    constexpr int NPC = 2;                       // 1-KiB pieces of K (and of V) per wave per tile
     int kd_voff[2], vd_voff[2];
 #pragma unroll
     for (int j = 0; j < NPC; ++j) {
-        const int key = 8 * (wv + VT_FWD_WAVES * j) + (lane >> 3);
+        const int key = 8 * (wv + 4 * j) + (lane >> 3);
         kd_voff[j] = (int)(key * p.k_rs * 2) + (((lane & 7) ^ ((key >> 1) & 7)) << 4);
         vd_voff[j] = (int)(key * p.v_rs * 2) + (((lane & 7) ^ (((key >> 1) & 1) << 2)) << 4);
     }
@@ -122,28 +94,9 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
         const int vs = (int)((long long)t * FK * p.v_rs * 2);
 #pragma unroll
         for (int j = 0; j < NPC; ++j) {
-            char* dst = smem + buf * 16384 + (wv + VT_FWD_WAVES * j) * 1024;
+            char* dst = smem + buf * 16384 + (wv + 4 * j) * 1024;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rk, (__attribute__((address_space(3))) void*)dst, 16, kd_voff[j], ks, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rv, (__attribute__((address_space(3))) void*)(dst + 8192), 16, vd_voff[j], vs, 0, 0);
-        }
-    };
-#endif
-    u32x4 gk[2], gv[2];
-    auto gload = [&](int t) {
-        const int ks = (int)((long long)t * FK * p.k_rs * 2);
-        const int vs = (int)((long long)t * FK * p.v_rs * 2);
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            gk[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rk, k_voff[j], ks, 0));
-            gv[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rv, v_voff[j], vs, 0));
-        }
-    };
-    auto lstore = [&](int buf) {
-        char* base = smem + buf * 16384;
-#pragma unroll
-        for (int j = 0; j < NCH; ++j) {
-            *(u32x4*)(base + k_lds[j]) = gk[j];
-            *(u32x4*)(base + v_lds[j]) = gv[j];
         }
     };
 
@@ -175,75 +128,26 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
     const float sc = p.scale_log2;
 
     const int nt = (p.S + FK - 1) / FK;
-#if VT_FWD_DMA
     dma(0, 0);
-#else
-    gload(0);
-    lstore(0);
-#endif
     __syncthreads();
     for (int t = 0; t < nt; ++t) {
         const int buf = t & 1;
-#if VT_FWD_DMA
         if (t + 1 < nt) dma(t + 1, buf ^ 1);
-#else
-        if (t + 1 < nt) gload(t + 1);
-#endif
         const char* base = smem + buf * 16384;
 
         f32x16 st[2];
-        bf16x8 vtf[4][2];          // VT_FWD_PF: V^T fragments of the four PV pairs, read ahead
-        (void)vtf;
         if constexpr (PRESCALED) {
             // ---- lazy-max online softmax (q carries softmax_scale*log2e): the accumulators START at -m_ref, so the
             // MFMA chain delivers s - m_ref and P = exp2(st) needs no subtraction; O and l are rescaled only when some
             // row's maximum grew by more than LAZY_THR (P then stays <= 2^LAZY_THR), which is rare after the first tiles.
-#if VT_FWD_PF
-            {
-                bf16x8 kfr[4][2];
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int kt2 = 0; kt2 < 2; ++kt2) kfr[s][kt2] = *(const bf16x8*)(base + kt2 * 4096 + kfo[s]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-#pragma unroll
-                    for (int kt2 = 0; kt2 < 2; ++kt2)
-                        st[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr[s][kt2], qf[s], s == 0 ? negm : st[kt2], 0, 0, 0);
-                    // the V^T fragments of PV pair (kt2p, s2p) = (s >> 1, s & 1), both d-tiles, ride under these MFMAs
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        const char* vp = base + vfo[dt] + ((s >> 1) * 32 + (s & 1) * 16) * 128;
-                        short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(vp));
-                        short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(vp + 8 * 128));
-                        typedef __attribute__((ext_vector_type(8))) short short8v;
-                        short8v v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                        vtf[s][dt] = __builtin_bit_cast(bf16x8, v8);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#else
-#if VT_FWD_PRIO
-            __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
 #pragma unroll
                 for (int kt2 = 0; kt2 < 2; ++kt2) {
-#if VT_FWD_ABL & 1
-                    bf16x8 kf = qf[(s + kt2) & 3];
-#else
                     bf16x8 kf = *(const bf16x8*)(base + kt2 * 4096 + kfo[s]);
-#endif
                     st[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], s == 0 ? negm : st[kt2], 0, 0, 0);
                 }
             }
-#if VT_FWD_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#endif
             if ((t + 1) * FK > p.S) {
 #pragma unroll
                 for (int kt2 = 0; kt2 < 2; ++kt2)
@@ -258,14 +162,9 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
             for (int i = 1; i < 16; ++i) mx = fmaxf(mx, st[0][i]);
 #pragma unroll
             for (int i = 0; i < 16; ++i) mx = fmaxf(mx, st[1][i]);
-#if !VT_FWD_LATEMAX
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-#endif
             if (t == 0 || !__all(mx <= LAZY_THR)) {            // wave-uniform (the two lane halves of a query each test their own keys)
-#if VT_FWD_LATEMAX
                 mx = fmaxf(mx, __shfl_xor(mx, 32, 64));       // the row maximum itself is needed only here: keep the cross-half exchange (an LDS
                                                                // round trip) off the common path
-#endif
                 const float delta = (t == 0) ? mx : fmaxf(mx, 0.f);
                 const float alpha = (t == 0) ? 1.0f : __builtin_amdgcn_exp2f(-delta);
                 m_run += delta;
@@ -349,9 +248,6 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
         }
 
         // ---- O^T += V^T P^T : 2 d-tiles x (2 key sub-tiles x 2 k-steps) ----
-#if VT_FWD_PRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2) {
 #pragma unroll
@@ -361,32 +257,16 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
                 for (int j = 0; j < 8; ++j) pf[j] = (bf16_t)st[kt2][8 * s2 + j];
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-#if VT_FWD_PF
-                    if constexpr (PRESCALED) {
-                        o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vtf[2 * kt2 + s2][dt], pf, o_acc[dt], 0, 0, 0);
-                        continue;
-                    }
-#endif
-#if VT_FWD_ABL & 2
-                    o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[(dt + s2 + kt2) & 3], pf, o_acc[dt], 0, 0, 0);
-#else
                     const char* vp = base + vfo[dt] + (kt2 * 32 + s2 * 16) * 128;
                     short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(vp));
                     short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)(vp + 8 * 128));
                     typedef __attribute__((ext_vector_type(8))) short short8v;
                     short8v v8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v8), pf, o_acc[dt], 0, 0, 0);
-#endif
                 }
             }
         }
-#if VT_FWD_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-#if !VT_FWD_DMA
-        if (t + 1 < nt) lstore(buf ^ 1);
-#endif
-        __syncthreads();       // (DMA build: its vmcnt(0) also retires the next tile's LDS-DMA)
+        __syncthreads();       // its vmcnt(0) also retires the next tile's LDS-DMA
     }
 
     // ---- finalize: O = O^T / l, LSE ----
@@ -408,15 +288,11 @@ __global__ __launch_bounds__(FWD_THREADS, (VT_FWD_WAVES == 8 ? 1 : 2)) void attn
     }
 }
 
-
-#ifndef VT_FWD_M16
-#define VT_FWD_M16 0     // 1 = the pre-scaled-q forward (the training path) runs attn_fwd_hd64_m16_kernel: both products on v_mfma_f32_16x16x32_bf16
-#endif                   // tiles (same cycles per flop as 32x32x16; the chip holds a higher clock on this shape under load -- gemm_big_bf16.hip).
-                         // Parity-clean.  Back to back in a loop (tools/kbench.py attn, B=1) it is 3.5 % FASTER than the 32x32x16 kernel (2.48 vs 2.57 ms);
-                         // inside the training step (bench.py, B=4, same box, two rounds) it is 1.5 % SLOWER (9.09-9.15 vs 8.94-9.03 ms per launch):
-                         // a 9-ms kernel between GEMMs does not sit in the clock regime of a sustained loop.  The step decides: off.
-
-// The lazy-max forward on 16 x 16 x 32 tiles.  A wave owns 32 queries = two q-tiles; S^T tile (key-tile kt, q-tile qt): lane (g = lane >> 4,
+// The lazy-max forward on 16 x 16 x 32 tiles, launched on request only (q_prescaled == 2, ops.attn_fwd(tiles16=True)).  Same cycles per flop
+// as 32x32x16 and parity-clean.  Back to back in a loop (tools/kbench.py attn, B=1) it is 3.5 % FASTER than the 32x32x16 kernel (2.48 vs 2.57 ms);
+// inside the training step (bench.py, B=4, same box, two rounds) it is 1.5 % SLOWER (9.09-9.15 vs 8.94-9.03 ms per launch): a 9-ms kernel
+// between GEMMs does not sit in the clock regime of a sustained loop.  The step decides, so the training path stays on the kernel above.
+// A wave owns 32 queries = two q-tiles; S^T tile (key-tile kt, q-tile qt): lane (g = lane >> 4,
 // c = lane & 15) holds query 16 qt + c and keys 16 kt + 4 g + (0..3), so the row statistics are lane-local up to the four lane groups
 // (combined only when a rescale happens and at the end).  P^T of two stacked key tiles, packed to bf16, is the B operand of
 // O^T += V^T P^T (k-slot j of group g = key 4 g + j for j < 4, 16 + 4 g + j - 4 above); the V^T fragments follow that order through two
@@ -615,7 +491,7 @@ extern "C" int vt_attn_fwd_hd64(const void* q, const void* k, const void* v, voi
     p.scale_log2 = softmax_scale * 1.4426950408889634f;
     p.bias_t = nullptr;
     const int nqt = (S + FQ - 1) / FQ;
-    if (q_prescaled && (VT_FWD_M16 || q_prescaled == 2) && VT_FWD_WAVES == 4 && VT_FWD_DMA)      // q_prescaled == 2: the 16x16x32 variant on request
+    if (q_prescaled == 2)      // the 16x16x32 variant on request (ops.attn_fwd(tiles16=True))
         hipLaunchKernelGGL(attn_fwd_hd64_m16_kernel, dim3(nqt * H * B), dim3(256), 0, (hipStream_t)stream, p);
     else if (q_prescaled) hipLaunchKernelGGL(attn_fwd_hd64_kernel<true>, dim3(nqt * H * B), dim3(FWD_THREADS), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(attn_fwd_hd64_kernel<false>, dim3(nqt * H * B), dim3(FWD_THREADS), 0, (hipStream_t)stream, p);

@@ -226,7 +226,7 @@ __device__ __forceinline__ void bwd4_body(const Bwd4Params& p, char* smem, const
     };
     int pf_ready = 0, pf_cons = 0;        // counters polled one step ahead of their use
     f32x16 dq_next;                       // the predecessor's tile of the NEXT dQ': loaded in s5, the initial accumulator one step later
-    // dS image: row = key, 8-byte unit u = query / 4 stored at unit u ^ swz4(row) (csrc/attn_bwd.hip VT_DS4: stores AND the dQ phase's
+    // dS image: row = key, 8-byte unit u = query / 4 stored at unit u ^ swz4(row) (the dS image format of csrc/attn_bwd.hip: stores AND the dQ phase's
     // transposed reads are conflict-free).  This lane writes units 8 qs + 2 gg + h of key rows 64 w + 32 kt + r.
     unsigned dsw[2][4];
 #pragma unroll
