@@ -472,7 +472,7 @@ int vt_quantize_fp8(const void* x, long long ldx, void* y, long long ldy, long l
 /* MX-scaled FP8 GEMM and delayed per-tensor scaling (csrc/gemm_mxfp8.hip; HunyuanVideo fp8="mfma").
  * vt_gemm_mxfp8: C = epilogue((Aq Wq^T) * scale_a * scale_w [+ At Wt^T] + bias) on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3, unit block
  * scales); epilogue EPI_BIAS / EPI_BIAS_GELU / EPI_GATED_RES with the operands of vt_gemm_bf16; optional bf16 tail At [M, Kt], Wt [N, Kt]
- * (Kt 0, 32 or 64); optional e4m3 copy Cq = e4m3(C / scale_out) with max |C| into amax.  K % 128 == 0, N % 4 == 0; scales on the device.
+ * (Kt 0 or a multiple of 32 up to 384, ldat / ldwt >= Kt; above 64 columns the tail is staged through LDS); optional e4m3 copy Cq = e4m3(C / scale_out) with max |C| into amax.  K % 128 == 0, N % 4 == 0; scales on the device.
  * vt_cast_fp8_scaled: x bf16 -> e4m3 with a device scale, max |x| into amax; row m reads x row (m / L) * Lj + off + m % L (L = 0: m) and
  * is optionally copied (bf16) to cp.  vt_ln_modulate_fwd_fp8: vt_ln_modulate_fwd plus an e4m3 copy of y and its amax.
  * vt_fp8_scale_update: per site, history [n, H] <- (amax, history[:, :-1]), scale = max(history) / 448 (1 if 0), amax cleared.

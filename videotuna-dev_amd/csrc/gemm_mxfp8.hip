@@ -25,6 +25,7 @@ struct GemmMxParams {
     unsigned char* Cq; int ldcq; const float* scale_out; unsigned int* amax;   // fp8 copy of the output (Cq = null: none)
 };
 
+enum { MX_MAX_KT = 384 };                          // widest bf16 tail: three rank-128 adapters (vt355.lora.extension_layout)
 enum { FMT_E4M3 = 0, FMT_E5M2 = 1 };               // the f8f6f4 format codes of v_mfma_scale (cbsz / blgp), OCP formats on gfx950
 
 __device__ __forceinline__ unsigned int e4m3x4(const float* v, float sc) {
@@ -62,7 +63,10 @@ __device__ __forceinline__ unsigned int fp8x4(const float* v, float sc) {
 }
 
 // FA: format of the A operand (activation: E4M3; output gradient: either), FO: format of the fp8 copy of the output.  W is always E4M3.
-template <int EPI, int FA = FMT_E4M3, int FO = FMT_E4M3>
+// WT: the wide bf16 tail (64 < Kt <= 384).  A 64-column step of the tail is 128 bytes per row, the geometry of an fp8 K-tile, so the
+// tail's [128, 64] A and W slabs go through the same two LDS stages with the same DMA pattern and swizzle: they are K-tiles nk, nk + 1, ...
+// of the one pipeline (the first one is requested during the last fp8 tile), each read back as two 32-deep bf16 k-steps.
+template <int EPI, int FA = FMT_E4M3, int FO = FMT_E4M3, bool WT = false>
 __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     __shared__ __attribute__((aligned(16))) char smem[65536];
     const GemmParams& g = p.g;
@@ -99,6 +103,24 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + 16384), 16, w_voff[j], soff, 0, 0);
         }
     };
+    // WT: the tail slabs.  The resource ends with the Kt columns of the last valid row: rows past M / N and the columns past Kt of that
+    // row come back as zeros, the columns past Kt of every other row are bytes of the wider buffer that no MFMA reads (Kt % 64 == 32).
+    const int nts = WT ? (p.Kt + 63) / 64 : 0;
+    auto dma_tail = [&](int s, int buf) {
+        const long long at_rem = ((long long)(g.M - row0 - 1) * p.ldat + p.Kt) * 2, wt_rem = ((long long)(g.N - col0 - 1) * p.ldwt + p.Kt) * 2;
+        __amdgpu_buffer_rsrc_t rat = make_rsrc(p.At + (size_t)row0 * p.ldat, (unsigned)(at_rem > 0x7fffffffLL ? 0x7fffffffLL : at_rem));
+        __amdgpu_buffer_rsrc_t rwt = make_rsrc(p.Wt + (size_t)col0 * p.ldwt, (unsigned)(wt_rem > 0x7fffffffLL ? 0x7fffffffLL : wt_rem));
+        const int soff = s * 128;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = 8 * (wv + 4 * j) + drl;
+            char* dst = smem + buf * 32768 + (wv + 4 * j) * 1024;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rat, (__attribute__((address_space(3))) void*)dst, 16,
+                                                     row * p.ldat * 2 + ((dcp ^ drl) << 4), soff, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rwt, (__attribute__((address_space(3))) void*)(dst + 16384), 16,
+                                                     row * p.ldwt * 2 + ((dcp ^ drl) << 4), soff, 0, 0);
+        }
+    };
     f32x4 acc[4][4];   // [tn][tm]
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -112,6 +134,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) dma(kt + 1, buf ^ 1);
+        else if (WT) dma_tail(0, buf ^ 1);
         const char* As = smem + buf * 32768;
         const char* Ws = As + 16384;
         i32x8 af[4], wf[4];
@@ -136,7 +159,41 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     for (int tn = 0; tn < 4; ++tn)
 #pragma unroll
         for (int tm = 0; tm < 4; ++tm) acc[tn][tm] *= sc;
-    if (p.Kt > 0) {
+    if (WT) {
+        // wide bf16 tail from LDS: step s (64 columns) sits in stage (nk + s) & 1; lane l holds row l & 15, k = 8 (l >> 4) .. + 7 of each of
+        // its two 32-deep k-steps, i.e. the 16-byte chunks (l >> 4) and 4 + (l >> 4) of its 128-byte row.  The next step's slabs are in
+        // flight while this step's MFMAs run.
+        const int t0 = ((fq ^ fx) << 4), t1 = (((4 + fq) ^ fx) << 4);
+        for (int s = 0; s < nts; ++s) {
+            const int buf = (nk + s) & 1;
+            if (s + 1 < nts) dma_tail(s + 1, buf ^ 1);
+            const char* As = smem + buf * 32768;
+            const char* Ws = As + 16384;
+            const bool two = 64 * s + 32 < p.Kt;
+            bf16x8 a8[4], w8[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                a8[t] = *(const bf16x8*)(As + (wm * 64 + t * 16 + frow) * 128 + t0);
+                w8[t] = *(const bf16x8*)(Ws + (wn * 64 + t * 16 + frow) * 128 + t0);
+            }
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn)
+#pragma unroll
+                for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w8[tn], a8[tm], acc[tn][tm], 0, 0, 0);
+            if (two) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    a8[t] = *(const bf16x8*)(As + (wm * 64 + t * 16 + frow) * 128 + t1);
+                    w8[t] = *(const bf16x8*)(Ws + (wn * 64 + t * 16 + frow) * 128 + t1);
+                }
+#pragma unroll
+                for (int tn = 0; tn < 4; ++tn)
+#pragma unroll
+                    for (int tm = 0; tm < 4; ++tm) acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w8[tn], a8[tm], acc[tn][tm], 0, 0, 0);
+            }
+            __syncthreads();
+        }
+    } else if (p.Kt > 0) {
         // bf16 tail, straight from global memory (Kt <= 64 columns): lane l holds row l & 15, k = 8 (l >> 4) .. + 7 of a 32-deep k-step.
         // Rows past M / N read the last row (their results are never stored).
         const bf16_t* at[4]; const bf16_t* wt[4];
@@ -221,9 +278,17 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp8_kernel(GemmMxParams p) {
     }
 }
 
+// Kt <= 64: the instantiation every call ran before the wide tail existed; above: the LDS-staged tail
+template <int EPI, int FA, int FO>
+static void launch_mxfp8(const GemmMxParams& p, int tiles, hipStream_t st) {
+    if (p.Kt > 64) hipLaunchKernelGGL((gemm_mxfp8_kernel<EPI, FA, FO, true>), dim3(tiles), dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((gemm_mxfp8_kernel<EPI, FA, FO>), dim3(tiles), dim3(256), 0, st, p);
+}
+
 // A, W: float8_e4m3fn [M, lda] / [N, ldw] (bytes; multiples of 16); scale_a, scale_w: device fp32 scalars; epilogue / bias / residual /
 // gates / pre_act_out as vt_gemm_bf16 (EPI_BIAS, EPI_BIAS_GELU, EPI_GATED_RES); C bf16 [M, ldc].  At / Wt: bf16 tail [M, ldat] / [N, ldwt]
-// of Kt columns (Kt = 0: none; else a multiple of 32, <= 64).  Cq: e4m3 copy of C [M, ldcq] (null: none) with scale_out (device fp32)
+// of Kt columns (Kt = 0: none; else a multiple of 32, <= 384; ldat / ldwt may exceed Kt: column slices of wider buffers; up to 64 the
+// kernel reads them straight from global memory, above that it stages them through LDS).  Cq: e4m3 copy of C [M, ldcq] (null: none) with scale_out (device fp32)
 // and max |C| into amax (device uint32 holding float bits; accumulated, not cleared).  K % 128 == 0, N % 4 == 0.
 extern "C" int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias,
                              const float* scale_a, const float* scale_w, int epilogue, const void* residual, int ldr,
@@ -239,7 +304,7 @@ extern "C" int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, voi
     if (epilogue == EPI_GATED_RES && pre_act_out != nullptr && (ldc2 < N || (ldc2 % 4))) return VT_ERR_BAD_SHAPE;
     if (gate_vid != nullptr && (gate_txt == nullptr || S <= 0 || (gate_bstride % 4) || (((uintptr_t)gate_txt | (uintptr_t)gate_vid) & 15)))
         return VT_ERR_BAD_SHAPE;
-    if (Kt < 0 || Kt > 64 || (Kt % 32)) return VT_ERR_BAD_SHAPE;
+    if (Kt < 0 || Kt > MX_MAX_KT || (Kt % 32)) return VT_ERR_BAD_SHAPE;
     if (Kt > 0 && (At == nullptr || Wt == nullptr || ldat < Kt || ldwt < Kt || (ldat % 8) || (ldwt % 8))) return VT_ERR_BAD_SHAPE;
     if (Kt > 0 && ((((uintptr_t)At) | ((uintptr_t)Wt)) & 15)) return VT_ERR_BAD_ALIGN;
     if (Cq != nullptr && (scale_out == nullptr || amax == nullptr || ldcq < N || (ldcq % 4))) return VT_ERR_BAD_SHAPE;
@@ -253,21 +318,17 @@ extern "C" int vt_gemm_mxfp8(const void* A, int lda, const void* W, int ldw, voi
     p.Cq = (unsigned char*)Cq; p.ldcq = ldcq; p.scale_out = scale_out; p.amax = amax;
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
     hipStream_t st = (hipStream_t)stream;
-    if (epilogue == EPI_BIAS) hipLaunchKernelGGL(gemm_mxfp8_kernel<EPI_BIAS>, dim3(tiles), dim3(256), 0, st, p);
-    else if (epilogue == EPI_BIAS_GELU) hipLaunchKernelGGL(gemm_mxfp8_kernel<EPI_BIAS_GELU>, dim3(tiles), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(gemm_mxfp8_kernel<EPI_GATED_RES>, dim3(tiles), dim3(256), 0, st, p);
+    if (epilogue == EPI_BIAS) launch_mxfp8<EPI_BIAS, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+    else if (epilogue == EPI_BIAS_GELU) launch_mxfp8<EPI_BIAS_GELU, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+    else launch_mxfp8<EPI_GATED_RES, FMT_E4M3, FMT_E4M3>(p, tiles, st);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
 // The input-gradient product of a Linear whose forward ran on vt_gemm_mxfp8: C[M, N] = epilogue((Gq[M, K] WqT[N, K]^T) scale_g scale_w
 // [+ At Wt^T]).  Gq: the quantised output gradient, fmt_g 0 = e4m3 / 1 = e5m2; WqT: e4m3 bytes of the transposed weight (a column or row
 // slice of it: ldw = its full row length).  epilogue: EPI_BIAS (plain store, there is no bias), EPI_DGELU (times gelu'(pre_act_in)),
-// EPI_GATED_RES (+ residual, no gates).  At / Wt: the bf16 tail (LoRA: dt [M, 64], A3^T [N, 64]).  Cq: fp8 copy of C in format fmt_out
+// EPI_GATED_RES (+ residual, no gates).  At / Wt: the bf16 tail as vt_gemm_mxfp8 (LoRA: dt [M, ext], A3^T [N, ext]).  Cq: fp8 copy of C in format fmt_out
 // (EPI_DGELU only: d(u) for the fc1 / linear1 product that follows) with scale_out and amax as vt_gemm_mxfp8.  K % 128 == 0, N % 4 == 0.
-template <int EPI, int FA, int FO>
-static void launch_mxfp8_dx(const GemmMxParams& p, int tiles, hipStream_t st) {
-    hipLaunchKernelGGL((gemm_mxfp8_kernel<EPI, FA, FO>), dim3(tiles), dim3(256), 0, st, p);
-}
 extern "C" int vt_gemm_mxfp8_dx(const void* G, int ldg, int fmt_g, const void* WT, int ldw, void* C, int ldc, int M, int N, int K,
                                 const float* scale_g, const float* scale_w, int epilogue, const void* residual, int ldr,
                                 const void* pre_act_in, int ldu, const void* At, int ldat, const void* Wt, int ldwt, int Kt,
@@ -279,7 +340,7 @@ extern "C" int vt_gemm_mxfp8_dx(const void* G, int ldg, int fmt_g, const void* W
     if (epilogue != EPI_BIAS && epilogue != EPI_DGELU && epilogue != EPI_GATED_RES) return VT_ERR_UNSUPPORTED;
     if (epilogue == EPI_DGELU && (pre_act_in == nullptr || ldu < N || (ldu % 4) || (((uintptr_t)pre_act_in) & 7))) return VT_ERR_BAD_SHAPE;
     if (epilogue == EPI_GATED_RES && (residual == nullptr || ldr < N || (ldr % 4) || (((uintptr_t)residual) & 7))) return VT_ERR_BAD_SHAPE;
-    if (Kt < 0 || Kt > 64 || (Kt % 32)) return VT_ERR_BAD_SHAPE;
+    if (Kt < 0 || Kt > MX_MAX_KT || (Kt % 32)) return VT_ERR_BAD_SHAPE;
     if (Kt > 0 && (At == nullptr || Wt == nullptr || ldat < Kt || ldwt < Kt || (ldat % 8) || (ldwt % 8))) return VT_ERR_BAD_SHAPE;
     if (Kt > 0 && ((((uintptr_t)At) | ((uintptr_t)Wt)) & 15)) return VT_ERR_BAD_ALIGN;
     if (Cq != nullptr && epilogue != EPI_DGELU) return VT_ERR_UNSUPPORTED;
@@ -295,13 +356,13 @@ extern "C" int vt_gemm_mxfp8_dx(const void* G, int ldg, int fmt_g, const void* W
     hipStream_t st = (hipStream_t)stream;
     const bool g5 = fmt_g == FMT_E5M2, o5 = fmt_out == FMT_E5M2;
     if (epilogue == EPI_BIAS) {
-        if (g5) launch_mxfp8_dx<EPI_BIAS, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8_dx<EPI_BIAS, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+        if (g5) launch_mxfp8<EPI_BIAS, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8<EPI_BIAS, FMT_E4M3, FMT_E4M3>(p, tiles, st);
     } else if (epilogue == EPI_GATED_RES) {
-        if (g5) launch_mxfp8_dx<EPI_GATED_RES, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8_dx<EPI_GATED_RES, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+        if (g5) launch_mxfp8<EPI_GATED_RES, FMT_E5M2, FMT_E4M3>(p, tiles, st); else launch_mxfp8<EPI_GATED_RES, FMT_E4M3, FMT_E4M3>(p, tiles, st);
     } else if (g5) {
-        if (o5) launch_mxfp8_dx<EPI_DGELU, FMT_E5M2, FMT_E5M2>(p, tiles, st); else launch_mxfp8_dx<EPI_DGELU, FMT_E5M2, FMT_E4M3>(p, tiles, st);
+        if (o5) launch_mxfp8<EPI_DGELU, FMT_E5M2, FMT_E5M2>(p, tiles, st); else launch_mxfp8<EPI_DGELU, FMT_E5M2, FMT_E4M3>(p, tiles, st);
     } else {
-        if (o5) launch_mxfp8_dx<EPI_DGELU, FMT_E4M3, FMT_E5M2>(p, tiles, st); else launch_mxfp8_dx<EPI_DGELU, FMT_E4M3, FMT_E4M3>(p, tiles, st);
+        if (o5) launch_mxfp8<EPI_DGELU, FMT_E4M3, FMT_E5M2>(p, tiles, st); else launch_mxfp8<EPI_DGELU, FMT_E4M3, FMT_E4M3>(p, tiles, st);
     }
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }

@@ -34,6 +34,7 @@ NOT built (recorded in DESIGN.md): the embedders / token refiner / final layer o
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 from typing import Dict, Optional
 
@@ -41,6 +42,7 @@ import torch
 import torch.distributed
 
 from . import ops
+from .lora import extension_layout
 from .ops import BF16, EPI_BIAS_GELU, EPI_DGELU, EPI_GATED_RES
 from .stdit import _STRun
 from .unet import F32, FlatParamModule, _Var
@@ -76,18 +78,31 @@ class _XVar(_Var):
 
 
 EXT = 64          # K-extension columns of a LoRA'd Linear: x_ext = [x | x A^T (3 r <= 64 columns) | 0], W_ext = [W | scaling * B | 0]
+MAX_R = 128       # ranks with 3 r > EXT: the wide layout of vt355.lora.extension_layout on the MFMA rank-side kernels (csrc/lora_wide.hip)
+
+
+def lora_layout(r: int):
+    """(rp, ext_qkv, ext_proj, wide) of the K-extension of a HunyuanVideo adapter of rank r.  3 r <= 64: the three adapters of a fused
+    projection sit side by side (column stride rp = r) in a fixed 64-column extension.  Above that -- or at any rank when VT355_LORA_WIDE=1
+    is set, a test / A-B knob -- the wide layout: rp = r rounded up to a multiple of 16, adapter j in columns [j rp, j rp + r), the
+    extension 3 rp (q | k | v projections) / rp (img_attn_proj) columns rounded up to a multiple of 64, every other column zero."""
+    if r <= 0 or r > MAX_R:
+        raise ValueError(f"rank {r}: HunyuanVideo LoRA ranks are 1..{MAX_R} (three adapters of {MAX_R} rank columns fill the widest K-extension)")
+    if 3 * r <= EXT and os.environ.get("VT355_LORA_WIDE", "0") in ("", "0"):
+        return r, EXT, EXT, False
+    return extension_layout(r, wide=True)
 
 
 class _HYLora(FlatParamModule):
     """rank-r adapters on the image stream's attention projections, the modules the shipped recipe targets (configs/007_hunyuanvideo/
     hunyuanvideo_t2v_diffuser_lora.yaml:59-64: r 4, alpha 1, target_modules to_q / to_k / to_v / to_out.0 of diffusers' attention): here the
     q / k / v row blocks of ``double_blocks.N.img_attn_qkv`` and of ``single_blocks.N.linear1`` and ``double_blocks.N.img_attn_proj``.
-    Parameter names: ``<module>.lora_A.{q,k,v}.weight [r, D]``, ``<module>.lora_B.{q,k,v}.weight [D, r]`` (proj: no q/k/v level)."""
+    Parameter names: ``<module>.lora_A.{q,k,v}.weight [r, D]``, ``<module>.lora_B.{q,k,v}.weight [D, r]`` (proj: no q/k/v level).
+    Ranks 1..128; the K-extension layout (narrow up to 3 r = 64, wide above) is lora_layout's and does not show in names or shapes."""
 
     def __init__(self, D: int, n_double: int, n_single: int, r: int, alpha: float):
         super().__init__()
-        if 3 * r > EXT:
-            raise ValueError(f"rank {r}: three adapters must fit the {EXT} extension columns")
+        self.rp, self.ext_qkv, self.ext_proj, self.wide = lora_layout(r)      # fixed at construction (VT355_LORA_WIDE is read here)
         self.r, self.scaling, self.D = r, alpha / r, D
         sh: Dict[str, tuple] = {}
         self.sites: Dict[str, list] = {}            # module name -> adapter tags
@@ -102,6 +117,10 @@ class _HYLora(FlatParamModule):
                 sh[f"{mod}.lora_A{dot}.weight"] = (r, D)
                 sh[f"{mod}.lora_B{dot}.weight"] = (D, r)
         self._setup_flat(sh)
+
+    def ext_of(self, mod: str) -> int:
+        """K-extension columns of the adapted Linear `mod`"""
+        return self.ext_qkv if len(self.sites[mod]) == 3 else self.ext_proj
 
     def init_weights(self, seed: int = 0, zero_b: bool = True):
         """peft's default: A random, B zero (the adapter starts as the identity); zero_b=False for tests"""
@@ -140,7 +159,8 @@ class HunyuanBlocks(FlatParamModule):
             sh.update(_single_shapes(hidden_size, heads_num, mlp_width_ratio, f"single_blocks.{i}."))
         self._setup_flat({**(shapes_before or {}), **sh, **(shapes_after or {})})
         # LoRA mode: the block weights stay frozen (no fp32 master, no gradients, no dW GEMMs); only the adapters train
-        self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha) if lora_rank > 0 else None
+        # lora_rank 0: no adapters; 1..MAX_R: _HYLora (which refuses anything else)
+        self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha) if lora_rank != 0 else None
         self.sp_group = None
         self.fp8_dgrad = fp8_dgrad
 
@@ -324,6 +344,8 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
     ver = -1 if L.train_state is None else L.train_state.version
     if L._packed is not None and L._packed_version == ver:
         return L._packed
+    if L.wide:
+        return _packed_lora_wide(model, ver)
     # The frozen base weight fills all but 64 columns of W_ext: when only the ADAPTERS changed (an optimizer step in LoRA mode: the base weights'
     # version stands still) the previous W_ext / W_ext^T are kept and only their extension columns / rows are rewritten -- re-copying and
     # re-transposing 3072 x 9216 base weights per site and step was 9 ms of the step.
@@ -404,6 +426,57 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
                     a = L._plist[f"{mod}.lora_A{dot}.weight"]                                           # [r, D]
                     a3[j * r:(j + 1) * r] = a
                     a3t[:, j * r:(j + 1) * r] = a.t()
+    L._packed_base = base_key
+    L._packed, L._packed_version = P, ver
+    return P
+
+
+def _packed_lora_wide(model: HunyuanBlocks, ver: int) -> SimpleNamespace:
+    """_packed_lora for the wide layout (lora_layout: 3 r > 64 or VT355_LORA_WIDE=1).  Per adapted Linear of n adapters and ext = L.ext_of(mod)
+    extension columns: W_ext [n D, D + ext] and W_ext^T [D + ext, n D] (fp8_dgrad: its ext extension rows only) with scaling B_j in rows
+    [j D, (j + 1) D) x extension columns [j rp, j rp + r) and zeros in every other extension element, written by vt_lora_pack_b(t)_wide;
+    the adapters' A rows stacked [n r, D] (the operand of vt_lora_down_wide / vt_lora_up_add_wide); under fp8_dgrad also A3^T [D, ext]
+    (column j rp + i = row i of A_j), the bf16 tail operand of the fp8 dX product.  There are no gradient staging stacks: the rank
+    gradients go straight into the adapters' flat fp32 gradient (vt_lora_tn_wide).  As in the narrow layout the frozen base columns are
+    kept when only the adapters changed."""
+    L = model.lora
+    base_key = (id(_packed_hy(model)), model.fp8, model.fp8_dgrad)
+    prev = L._packed if (L._packed is not None and getattr(L, "_packed_base", None) == base_key) else None
+    D, r, rp = L.D, L.r, L.rp
+    dev = L.flat_bf16.device
+    dg = model.fp8 == "mfma" and bool(model.fp8_dgrad)
+    to = 0 if dg else D
+    with torch.no_grad():
+        if prev is None:
+            P = SimpleNamespace(wext={}, wtext={}, a={}, a3t={}, regular=True)         # regular: nothing is left for lora_scatter
+            for mod, tags in L.sites.items():
+                n, ext = len(tags), L.ext_of(mod)
+                w = _packed_hy(model).w.get(mod + ".weight")                # fp8 mode: the de-quantised E4M3 weight
+                if w is None:
+                    w = model.flat(model.flat_bf16, mod + ".weight")
+                P.wext[mod] = torch.empty(n * D, D + ext, dtype=BF16, device=dev)
+                P.wext[mod][:, :D] = w[:n * D]                              # linear1: only its first 3 D rows (q | k | v) are adapted
+                P.wtext[mod] = torch.empty(to + ext, n * D, dtype=BF16, device=dev)
+                if to:
+                    P.wtext[mod][:D] = ops.transpose(w[:n * D])
+                P.a[mod] = torch.empty(n * r, D, dtype=BF16, device=dev)
+                if dg:
+                    P.a3t[mod] = torch.zeros(D, ext, dtype=BF16, device=dev)
+        else:
+            P = prev
+        for mod, tags in L.sites.items():
+            n, ext = len(tags), L.ext_of(mod)
+            dots = ["." + t if t else "" for t in tags]
+            A = [L._plist[f"{mod}.lora_A{d}.weight"] for d in dots]
+            torch.cat(A, 0, out=P.a[mod])
+            # the pack kernels take the adapters' B stacked [n D, r] in fp32: the bf16 compute copy widened (exact), so that a model loaded
+            # from a state dict packs the same bits as the one that trained them
+            bcat = torch.cat([L._plist[f"{mod}.lora_B{d}.weight"] for d in dots], 0).float()
+            ops.lora_pack_b_wide(bcat, P.wext[mod][:, D:], D + ext, n, D, r, rp, ext, L.scaling)        # the whole extension, zeros included
+            ops.lora_pack_bt_wide(bcat, P.wtext[mod][to:], n * D, n, D, r, rp, ext, L.scaling)
+            if dg:
+                for j, a in enumerate(A):
+                    P.a3t[mod][:, j * rp:j * rp + r] = a.t()
     L._packed_base = base_key
     L._packed, L._packed_version = P, ver
     return P
@@ -551,14 +624,17 @@ class _HYRun(_STRun):
         if self.ts is not None:
             ops.group_colsum(g, self.G(name), D=D)
 
-    def ext(self, M):
-        """activation buffer of an adapted Linear's input: [M, D + EXT], the Linear reads all of it, producers write [:, :D]"""
-        return self.E(M, self.m.hidden_size + EXT)
+    def ext(self, M, proj: bool = False):
+        """activation buffer of an adapted Linear's input: [M, D + ext] (ext: the K-extension of the fused q | k | v projections, or with
+        proj=True that of img_attn_proj), the Linear reads all of it, producers write [:, :D]"""
+        return self.E(M, self.m.hidden_size + (self.lora.ext_proj if proj else self.lora.ext_qkv))
 
     def lora_linear(self, xe, mod: str, bias, y=None, q8=None, **epi):
         """y = [x | x A3^T] W_ext^T + bias (+ epilogue) for the adapted Linear `mod`; xe: ext buffer whose [:, :D] holds x.  Returns
         (y, backward(g) -> dx [M, D]) -- the caller decides what g is (gated or not) and where dx goes.  q8 = (xq, site, wname, rows):
         the base product x W^T on vt_gemm_mxfp8 from the e4m3 input, the extension columns as its bf16 tail."""
+        if self.lora.wide:
+            return self._lora_linear_wide(xe, mod, bias, y, q8, epi)
         D = self.m.hidden_size
         M = xe.shape[0]
         wext, a3 = self.LP.wext[mod], self.LP.a3[mod]
@@ -600,6 +676,52 @@ class _HYRun(_STRun):
             dx = self.E(M, D)
             ops.gemm(dxe[:, D:], self.LP.a3t[mod], dx, None, epilogue=EPI_GATED_RES, residual=dxe[:, :D])     # dx + dt A3
             return dx
+        return y, backward
+
+    def _lora_linear_wide(self, xe, mod: str, bias, y, q8, epi):
+        """lora_linear in the wide layout: the rank-side products on the MFMA kernels of csrc/lora_wide.hip.  t = x A^T of all the
+        Linear's adapters in one pass over x (the call writes the whole extension, zeros included); the base product as in the narrow
+        layout; backward: the rank gradients of each adapter straight into its slice of the flat fp32 gradient (fp32 atomics: not
+        bitwise reproducible from run to run), dx += sum_j dt_j A_j in one pass -- or, under fp8_dgrad, through the bf16 tail of the fp8
+        dX product"""
+        L, D = self.lora, self.m.hidden_size
+        M, ext = xe.shape[0], xe.shape[1] - D
+        tags, r, rp = L.sites[mod], L.r, L.rp
+        n = len(tags)
+        wext, wtext, a = self.LP.wext[mod], self.LP.wtext[mod], self.LP.a[mod]
+        assert ext == L.ext_of(mod) and wext.shape[1] == D + ext
+        ops.lora_down_wide(xe, a, n, r, rp, ext, xe[:, D:], D)
+        if y is None:
+            y = self.E(M, wext.shape[0])
+        if q8 is not None:
+            xq, site, wname, rows = q8
+            self.mx_gemm(xq, site, wname, y, bias, rows=rows, tail=(xe[:, D:], wext[:, D:]), **epi)
+        else:
+            ops.gemm(xe, wext, y, bias, **epi)
+
+        def backward(g, gq=None, gsite=None):
+            fp8dx = self.dg and q8 is not None
+            assert fp8dx or not self.dg, "fp8_dgrad: every adapted Linear runs on vt_gemm_mxfp8 (W_ext^T holds no base rows)"
+            if fp8dx:
+                dt = self.E(M, ext)
+                ops.gemm(g, wtext, dt, None)                            # dt = g (scaling B): W_ext^T holds its extension rows only
+            else:
+                dxe = self.E(M, D + ext)
+                ops.gemm(g, wtext, dxe, None)                           # [dx | dt] = g W_ext
+                dt = dxe[:, D:]
+            if self.lts is not None:
+                for j, t in enumerate(tags):
+                    dot = "." + t if t else ""
+                    gB = L.flat(self.lts.grad, f"{mod}.lora_B{dot}.weight")         # [D, r]
+                    gA = L.flat(self.lts.grad, f"{mod}.lora_A{dot}.weight")         # [r, D]
+                    ops.lora_tn_wide(g[:, j * D:(j + 1) * D], xe[:, D + j * rp:], r, gB, r, 1, L.scaling, D)    # dB_j += scaling g_j^T t_j
+                    ops.lora_tn_wide(xe[:, :D], dt[:, j * rp:], r, gA, 1, D, 1.0, D)                            # dA_j += dt_j^T x
+            if fp8dx:
+                dx = self.E(M, D)
+                self.dx_gemm(self.grad_in(gsite, g, gq), gsite, q8[2], dx, cols=q8[3], tail=(dt, self.LP.a3t[mod]))
+                return dx
+            ops.lora_up_add_wide(dxe, dt, a, n, r, rp, D)               # dx += sum_j dt_j A_j, in place
+            return dxe[:, :D]                                           # a row-strided view
         return y, backward
 
     def _lora_scatter_one(self, mod):
@@ -906,13 +1028,13 @@ class _HYRun(_STRun):
             x, L, off, sl, dsl, qkv, rp, qs = streams[s]
             aq = None
             if q8:                          # this stream's rows of the joint output: the bf16 copy and the e4m3 proj input in one pass
-                ae = self.ext(B * L) if (self.lora is not None and s == "img") else None
+                ae = self.ext(B * L, proj=True) if (self.lora is not None and s == "img") else None
                 ad = ae[:, :C] if ae is not None else self.E(B * L, C)
                 aq = self.fp8_in(qs + 1, o, copy=ad, rows=(L, Lj, off), M=B * L)
                 av = _XVar(ad, ae) if ae is not None else _Var(ad)
             elif self.lora is not None and s == "img":                               # input of the adapted projection: extended buffer
-                ae = self.ext(B * L)
-                ae.view(B, L, C + EXT)[:, :, :C].copy_(o.view(B, Lj, C)[:, off:off + L])
+                ae = self.ext(B * L, proj=True)
+                ae.view(B, L, ae.shape[1])[:, :, :C].copy_(o.view(B, Lj, C)[:, off:off + L])
                 av = _XVar(ae[:, :C], ae)
             else:
                 av = _Var(o.view(B, Lj, C)[:, off:off + L].reshape(B * L, C))       # this stream's rows of the joint output (a copy)
@@ -920,7 +1042,8 @@ class _HYRun(_STRun):
                 def bwd_split(av=av, off=off, L=L, ov=ov):
                     if ov.g is None:
                         ov.g = self.E(B * Lj, C)              # both streams' splits fill all of it
-                    ov.g.view(B, Lj, C)[:, off:off + L].copy_(av.g.view(B, L, C))
+                    g = av.g                          # row-strided when an adapted projection's wide-layout backward left it
+                    ov.g.view(B, Lj, C)[:, off:off + L].copy_(g.view(B, L, C) if g.is_contiguous() else g.as_strided((B, L, C), (L * g.stride(0), g.stride(0), 1)))
                 self.tape.append(bwd_split)
             x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs, site=qs + 1, xq=aq,
                                gsite=qs + 1)

@@ -1217,8 +1217,8 @@ def gemm_mxfp8(aq, wq, out, scale_a, scale_w, bias=None, *, epilogue: int = EPI_
                pre_act_out: Optional[torch.Tensor] = None, tail=None, out_fp8=None):
     """out bf16 [M, N] = epilogue((aq [M, K] @ wq [N, K]^T) * scale_a * scale_w [+ At @ Wt^T] + bias) on the MX-scaled fp8 matrix cores
     (v_mfma_scale_f32_16x16x128_f8f6f4, unit block scales).  scale_a / scale_w: device fp32 scalars (views).  Epilogue keywords as gemm()
-    (EPI_BIAS, EPI_BIAS_GELU, EPI_GATED_RES).  tail = (At bf16 [M, Kt], Wt bf16 [N, Kt]), Kt 32 or 64: a bf16 K segment added into the same
-    accumulators.  out_fp8 = (Cq float8_e4m3fn [M, N], scale, amax): Cq = e4m3(out / scale), max |out| into the amax slot."""
+    (EPI_BIAS, EPI_BIAS_GELU, EPI_GATED_RES).  tail = (At bf16 [M, Kt], Wt bf16 [N, Kt]), Kt a multiple of 32 up to 384 (column slices of wider
+    buffers allowed): a bf16 K segment added into the same accumulators after the scaled fp8 sum.  out_fp8 = (Cq float8_e4m3fn [M, N], scale, amax): Cq = e4m3(out / scale), max |out| into the amax slot."""
     _req(aq, FP8, "aq", 2); _req(wq, FP8, "wq", 2); _req(out, BF16, "out", 2)
     M, K, N = aq.shape[0], aq.shape[1], wq.shape[0]
     if wq.shape[1] != K or out.shape[0] != M or out.shape[1] < N:
@@ -1299,7 +1299,7 @@ def gemm_mxfp8_dx(gq, wqt, out, scale_g, scale_w, *, epilogue: int = EPI_BIAS, r
     """the input-gradient product of a Linear on the MX-scaled fp8 matrix cores: out bf16 [M, N] = epilogue((gq [M, K] @ wqt [N, K]^T)
     * scale_g * scale_w [+ At @ Wt^T]).  gq: the quantised output gradient, float8_e5m2 or float8_e4m3fn; wqt: float8_e4m3fn, the
     byte-transposed weight (row-strided slices allowed).  epilogue: EPI_BIAS (plain), EPI_DGELU (times gelu'(pre_act_in)) or
-    EPI_GATED_RES (+ residual).  tail as gemm_mxfp8.  out_fp8 = (Cq fp8 [M, N] of either format, scale, amax): EPI_DGELU only."""
+    EPI_GATED_RES (+ residual).  tail as gemm_mxfp8 (Kt a multiple of 32 up to 384).  out_fp8 = (Cq fp8 [M, N] of either format, scale, amax): EPI_DGELU only."""
     fg = _fp8_code(gq, "gq")
     _req(wqt, FP8, "wqt", 2); _req(out, BF16, "out", 2)
     M, K, N = gq.shape[0], gq.shape[1], wqt.shape[0]
