@@ -323,6 +323,13 @@ int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small, int lds_, 
                          float alpha, long long M, int P, float p, unsigned long long seed, int site, void* stream);   /* one adapter */
 int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
                              long long M, int K, float p, unsigned long long seed, int site0, void* stream);
+/* the dgelu form of the two dropped dX corrections (an adapter whose input is gelu(U): ff.net.2 of the CogVideoX block):
+   dX[m,k] += gelu'(U[m,k]) / (1-p) * sum_j keep_j(m,k) sum_i dT[m, .] A[., k]; U bf16 [M, K] with row stride ldu; gelu' is the EPI_DGELU
+   epilogue's function and multiplies the fp32 sum before the add */
+int vt_lora_up_add_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int R, int n_adapters, const void* U,
+                              int ldu, long long M, int K, float p, unsigned long long seed, int site0, void* stream);
+int vt_lora_up_add_wide_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                   const void* U, int ldu, long long M, int K, float p, unsigned long long seed, int site0, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
  * VideoCrafter2 UNet path (BASELINE configs[3]): lvdm UNetModel.forward and its backward

@@ -30,6 +30,69 @@ SUSTAINED_GBPS = 5607.6          # profiles/gradclip_kbench.txt, vt_adamw at 1.4
 SUSTAINED_TFLOPS = 1090.0        # DESIGN 5, gemm_*_bf16 in the step
 
 
+def ff_section(args, ops, torch, dev, M, d, g, line, last, P, SEED):
+    """--ff: the single-adapter products of the feed-forward LoRA targets (ff.net.0.proj reads K = d, ff.net.2 reads K = 4 d), each rank in
+    the layout the engine picks for it (narrow up to 16, wide above): the three rank-side products at K = 4 d next to K = d, the dgelu_drop
+    form of the dX correction right after its _drop sibling ("vs_sibling": time ratio; its bytes add the read of U), and the W2^T product
+    with the dGELU epilogue at K = d + ext (the undropped correction folded in) against K = d.
+
+        python tools/kbench_lora_wide.py --ff --ranks 4,64 > profiles/lora_ff_kbench.txt"""
+    from vt355.lora import extension_layout
+    from vt355.ops import EPI_DGELU
+    BF = torch.bfloat16
+    for r in [int(v) for v in args.ranks.split(",")]:
+        rp, _, ext, wide = extension_layout(r)
+        path = "wide" if wide else "narrow"
+        for K in (d, 4 * d):
+            tag = f"K={K}"
+            x = torch.randn(M, K + ext, device=dev, generator=g).to(BF)
+            A = (torch.randn(r, K, device=dev, generator=g) * 0.02).to(BF)
+            gA, gB = torch.zeros(r, K, device=dev), torch.zeros(K, r, device=dev)
+            t = x[:, K:]
+            if wide:
+                down = lambda: ops.lora_down_wide(x, A, 1, r, rp, ext, t, K)
+                dB = lambda: ops.lora_tn_wide(x, t, r, gB, r, 1, 0.25, K)
+                dA = lambda: ops.lora_tn_wide(x, t, r, gA, 1, K, 1.0, K)
+                up = lambda: ops.lora_up_add_wide(x, t, A, 1, r, rp, K)
+                up_drop = lambda: ops.lora_up_add_wide_drop(x, t, A, 1, r, rp, K, P, SEED, 0)
+            else:
+                down = lambda: ops.lora_down(x, A, r, t, K)
+                dB = lambda: ops.skinny_tn(x, t, r, gB, r, 1, 0.25, K)
+                dA = lambda: ops.skinny_tn(x, t, r, gA, 1, K, 1.0, K)
+                up = lambda: ops.lora_up_add(x, t, A, r, K)
+                up_drop = lambda: ops.lora_up_add_drop(x, t, A, r, 1, K, P, SEED, 0)
+            tn_bytes, flops = 2.0 * (M * K + M * r) + 8.0 * K * r, 2.0 * M * K * r
+            up_bytes = 2.0 * (2 * M * K + M * rp + r * K)
+            line("down", r, f"{path} {tag}", down, 2.0 * (M * K + r * K + M * ext), flops)
+            line("tn_dB", r, f"{path} {tag}", dB, tn_bytes, flops)
+            line("tn_dA", r, f"{path} {tag}", dA, tn_bytes, flops)
+            t.mul_(0.01)                      # the in-place correction is repeated: keep the sum finite
+            line("up_add", r, f"{path} {tag}", up, up_bytes, flops)
+            args.drop = P
+            line("up_add", r, f"{path} {tag}+drop", up_drop, up_bytes, flops)
+            if K == 4 * d:                    # ff.net.2: the correction enters before the dGELU
+                u = torch.randn(M, K, device=dev, generator=g).to(BF)
+                if wide:
+                    fn = lambda: ops.lora_up_add_wide_dgelu_drop(x, t, A, 1, r, rp, u, K, P, SEED, 0)
+                else:
+                    fn = lambda: ops.lora_up_add_dgelu_drop(x, t, A, r, 1, u, K, P, SEED, 0)
+                rec = line("up_add", r, f"{path} {tag} dgelu_drop", fn, up_bytes + 2.0 * M * K, flops)
+                print(json.dumps({"kernel": "up_add", "rank": r, "path": f"{path} {tag} dgelu_drop", "lora_dropout": P,
+                                  "vs_drop_sibling": round(rec["median_ms"] / last[("up_add", f"{path} {tag}+drop")], 3)}), flush=True)
+                del u
+            del x, A, gA, gB, t
+        # the W2^T product with the dGELU epilogue: [tg | dT2] [W2^T | A2^T]^T at K = d + ext against tg W2 at K = d
+        tgx = torch.randn(M, d + ext, device=dev, generator=g).to(BF)
+        w2t = (torch.randn(4 * d, d + ext, device=dev, generator=g) * 0.02).to(BF)
+        u = torch.randn(M, 4 * d, device=dev, generator=g).to(BF)
+        du = torch.empty(M, 4 * d, dtype=BF, device=dev)
+        for K in (d, d + ext):
+            line("gemm_dgelu_w2t", r, f"K={K}", lambda: ops.gemm(tgx, w2t, du, None, epilogue=EPI_DGELU, pre_act_in=u, K=K),
+                 2.0 * (M * K + 4 * d * K + 2 * M * 4 * d), 2.0 * M * 4 * d * K)
+        del tgx, w2t, u, du
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=20)
@@ -38,6 +101,7 @@ def main():
     ap.add_argument("--dim", type=int, default=1920)
     ap.add_argument("--drop", type=float, default=0.0, help="P > 0: also time the lora_dropout siblings")
     ap.add_argument("--ranks", default="16,32,64,128", help="ranks <= 16 also run the narrow kernels")
+    ap.add_argument("--ff", action="store_true", help="the feed-forward targets' shapes instead (ff_section below)")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
@@ -83,6 +147,8 @@ def main():
                       "sustained_tflop_per_s": SUSTAINED_TFLOPS, "sustained_tflop_per_s_source": "DESIGN 5: gemm_*_bf16 in the training step",
                       "device": torch.cuda.get_device_name(0)}), flush=True)
     P = args.drop
+    if args.ff:
+        return ff_section(args, ops, torch, dev, M, d, g, line, last, P if P > 0 else 0.1, SEED)
     for r in [int(v) for v in args.ranks.split(",")]:
         force = r <= 16
         rp, eq, eo, _ = extension_layout(r, wide=True)

@@ -91,6 +91,8 @@ PROTOTYPES = {
     "vt_lora_down_wide_drop": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_tn_wide_drop": [_vp, _i, _vp, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_up_add_wide_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_up_add_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    "vt_lora_up_add_wide_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     # ---- VideoCrafter2 UNet path ----
     "vt_conv_cl": [_vp, _ll, _vp, _vp, _fp, _i, _vp, _ll, _vp, _ll] + [_i] * 13 + [_vp],
     "vt_conv_dw_cl": [_vp, _ll, _vp, _ll, _fp] + [_i] * 13 + [_i, _vp],

@@ -173,6 +173,16 @@ struct LoraDrop {
 };
 __device__ __forceinline__ LoraDrop lora_drop_arg() { return LoraDrop{}; }
 __device__ __forceinline__ LoraDrop lora_drop_arg(const LoraDrop& d) { return d; }
+// A second trailing argument selects the dgelu form of a dropped dX correction (the backward of an adapter whose input is a GELU
+// output, ff.net.2): the masked sum is multiplied by gelu'(U[m,k]) before it is added.  U: the saved pre-activation, row stride ldu.
+struct LoraDgelu {
+    const bf16_t* U;
+    int ldu;
+};
+__device__ __forceinline__ LoraDrop lora_drop_arg(const LoraDrop& d, const LoraDgelu&) { return d; }
+__device__ __forceinline__ LoraDgelu lora_dgelu_arg() { return LoraDgelu{nullptr, 0}; }
+__device__ __forceinline__ LoraDgelu lora_dgelu_arg(const LoraDrop&) { return LoraDgelu{nullptr, 0}; }
+__device__ __forceinline__ LoraDgelu lora_dgelu_arg(const LoraDrop&, const LoraDgelu& g) { return g; }
 static inline LoraDrop vt_lora_drop(float p, unsigned long long seed, int site0, int n = 0, int r = 0) {
     return LoraDrop{vt_keep_thresh(p), 1.0f / (1.0f - p), seed, site0, n, r, 0};
 }

@@ -283,11 +283,15 @@ extern "C" int vt_skinny_tn_drop(const void* Big, int ldb, const void* Small, in
 // ---------------- dX[m,k] += sum_r dT[m,r] * A[r,k]   (in place, bf16) ----------------
 // DROP: dX[m,k] += 1/(1-p) sum_j keep_j(m,k) sum_i dT[m, j r + i] * A[j r + i, k]: each adapter's partial sum is masked before the
 // adapters are added
+// DGELU (a LoraDrop and a LoraDgelu trail): dX[m,k] += gelu'(U[m,k]) 1/(1-p) sum_j keep_j(m,k) sum_i ..., the dropped correction of an adapter
+// whose input is gelu(U) (ff.net.2) added to a dX that already carries gelu'(U) (x) (dY W): the mask sits between dT A and the GELU, so
+// this term cannot ride in the W^T product's K-extension.  gelu' is the EPI_DGELU epilogue's function; it multiplies the fp32 sum.
 template <typename... D>
 __global__ __launch_bounds__(256) void lora_up_add_kernel(bf16_t* dX, int ldx, const bf16_t* dT, int ldt, const bf16_t* A, int lda,
                                                          int R, long long M, int K, D... drop) {
-    constexpr bool DROP = sizeof...(D) > 0;
+    constexpr bool DROP = sizeof...(D) > 0, DGELU = sizeof...(D) > 1;
     const LoraDrop dr = lora_drop_arg(drop...);
+    const LoraDgelu dg = lora_dgelu_arg(drop...);
     const int n = DROP ? dr.n : 1, r = DROP ? dr.r : R;          // no dropout: one group of all R rank rows
     const int nch = K >> 3;
     const long long total = M * nch;
@@ -296,6 +300,12 @@ __global__ __launch_bounds__(256) void lora_up_add_kernel(bf16_t* dX, int ldx, c
         const int c = (int)(i - m * nch);
         float v[8];
         unpack8(*(const u32x4*)(dX + (size_t)m * ldx + c * 8), v);
+        float g[8];
+        if constexpr (DGELU) {
+            unpack8(*(const u32x4*)(dg.U + (size_t)m * dg.ldu + c * 8), g);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) g[q] = dr.inv_keep * gelu_tanh_grad_f(g[q]);
+        }
         for (int j = 0; j < n; ++j) {
             float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             float(&acc)[8] = DROP ? s : v;          // without a mask the sum goes straight into v
@@ -312,7 +322,7 @@ __global__ __launch_bounds__(256) void lora_up_add_kernel(bf16_t* dX, int ldx, c
                 keep_words4(ctr, dr.seed, rnd);
                 keep_words4(ctr + 1, dr.seed, rnd + 4);
 #pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] += rnd[q] >= dr.thresh ? dr.inv_keep * s[q] : 0.f;
+                for (int q = 0; q < 8; ++q) v[q] += rnd[q] >= dr.thresh ? (DGELU ? g[q] : dr.inv_keep) * s[q] : 0.f;
             }
         }
         *(u32x4*)(dX + (size_t)m * ldx + c * 8) = pack8(v);
@@ -320,14 +330,21 @@ __global__ __launch_bounds__(256) void lora_up_add_kernel(bf16_t* dX, int ldx, c
 }
 // dr == nullptr: no dropout
 static int lora_up_add_launch(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int R, long long M, int K,
-                              const LoraDrop* dr, void* stream) {
+                              const LoraDrop* dr, void* stream, const LoraDgelu* dg = nullptr) {
     if (M <= 0 || K <= 0 || (K % 8) || R <= 0 || R > 16 || (ldx % 8) || (lda % 8)) return VT_ERR_BAD_SHAPE;
     if ((((uintptr_t)dX) | ((uintptr_t)A)) & 15) return VT_ERR_BAD_ALIGN;
+    if (dg != nullptr) {
+        if (dr == nullptr || dg->U == nullptr || (dg->ldu % 8) || dg->ldu < K || ldx < K || ldt < R) return VT_ERR_BAD_SHAPE;
+        if (((uintptr_t)dg->U) & 15) return VT_ERR_BAD_ALIGN;
+    }
     long long total = M * (K >> 3), b = (total + 255) / 256;
     const dim3 grid((unsigned)(b > 8192 ? 8192 : b));
     if (dr == nullptr)
         hipLaunchKernelGGL(lora_up_add_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt,
                            (const bf16_t*)A, lda, R, M, K);
+    else if (dg != nullptr)
+        hipLaunchKernelGGL((lora_up_add_kernel<LoraDrop, LoraDgelu>), grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)dX, ldx,
+                           (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, R, M, K, *dr, *dg);
     else
         hipLaunchKernelGGL(lora_up_add_kernel<LoraDrop>, grid, dim3(256), 0, (hipStream_t)stream, (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt,
                            (const bf16_t*)A, lda, R, M, K, *dr);
@@ -342,6 +359,14 @@ extern "C" int vt_lora_up_add_drop(void* dX, int ldx, const void* dT, int ldt, c
     if (lora_drop_args_bad(R, n_adapters, p, site0)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site0, n_adapters, R / n_adapters);
     return lora_up_add_launch(dX, ldx, dT, ldt, A, lda, R, M, K, &dr, stream);
+}
+extern "C" int vt_lora_up_add_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int R, int n_adapters,
+                                         const void* U, int ldu, long long M, int K, float p, unsigned long long seed, int site0,
+                                         void* stream) {
+    if (lora_drop_args_bad(R, n_adapters, p, site0)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0, n_adapters, R / n_adapters);
+    const LoraDgelu dg = {(const bf16_t*)U, ldu};
+    return lora_up_add_launch(dX, ldx, dT, ldt, A, lda, R, M, K, &dr, stream, &dg);
 }
 
 // ---------------- write (alpha/r) * B[n, r] into the K-extension columns of the packed weight ----------------

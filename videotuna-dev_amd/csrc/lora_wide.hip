@@ -307,8 +307,9 @@ extern "C" int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small,
 template <typename... D>
 __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int ldx, const bf16_t* dT, int ldt, const bf16_t* A, int lda,
                                                               int n, int r, int rp, long long M, int K, D... drop) {
-    constexpr bool DROP = sizeof...(D) > 0;
+    constexpr bool DROP = sizeof...(D) > 0, DGELU = sizeof...(D) > 1;
     const LoraDrop dr = lora_drop_arg(drop...);
+    const LoraDgelu dg = lora_dgelu_arg(drop...);
     extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int NC = n * rp, NCp = (NC + 31) & ~31, nks = NCp >> 5, LS = NCp + LW_PAD;
@@ -328,6 +329,17 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
         }
     }
     for (int k0 = 0; k0 < K; k0 += 64) {
+        // DGELU: this lane's pre-activations of the 64 columns, fetched ahead of the staging and the MFMA chain that hide their latency
+        u32x2 upre[DGELU ? 2 : 1][DGELU ? 4 : 1];
+        if constexpr (DGELU) {
+#pragma unroll
+            for (int rt = 0; rt < 2; ++rt) {
+                const long long m = row0 + rt * 16 + fr;
+#pragma unroll
+                for (int ct = 0; ct < 4; ++ct)
+                    upre[rt][ct] = m < M ? *(const u32x2*)(dg.U + (size_t)m * dg.ldu + k0 + ct * 16 + 4 * fq) : u32x2{0u, 0u};
+            }
+        }
         __syncthreads();
         for (int u = tid; u < NCp * 4; u += 256) {
             const int pc = u & 7, q = u >> 3;
@@ -410,7 +422,15 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
                     const float lo1 = __uint_as_float(old[1] << 16), hi1 = __uint_as_float(old[1] & 0xffff0000u);
                     const f32x4 a = acc[rt][ct];
                     u32x2 o;
-                    if constexpr (DROP) {          // one expression per element: the multiply and the add contract into an fma
+                    if constexpr (DGELU) {         // the masked sum times gelu'(U[m, k..k+3]) / (1 - p), then the one add and rounding
+                        const u32x2 u2 = upre[rt][ct];
+                        const float g0 = dr.inv_keep * gelu_tanh_grad_f(__uint_as_float(u2[0] << 16));
+                        const float g1 = dr.inv_keep * gelu_tanh_grad_f(__uint_as_float(u2[0] & 0xffff0000u));
+                        const float g2 = dr.inv_keep * gelu_tanh_grad_f(__uint_as_float(u2[1] << 16));
+                        const float g3 = dr.inv_keep * gelu_tanh_grad_f(__uint_as_float(u2[1] & 0xffff0000u));
+                        o[0] = pack2(lo0 + g0 * a[0], hi0 + g1 * a[1]);
+                        o[1] = pack2(lo1 + g2 * a[2], hi1 + g3 * a[3]);
+                    } else if constexpr (DROP) {          // one expression per element: the multiply and the add contract into an fma
                         o[0] = pack2(lo0 + dr.inv_keep * a[0], hi0 + dr.inv_keep * a[1]);
                         o[1] = pack2(lo1 + dr.inv_keep * a[2], hi1 + dr.inv_keep * a[3]);
                     } else {
@@ -425,12 +445,16 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
 }
 // dr == nullptr: no dropout
 static int lora_up_add_wide_launch(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
-                                   long long M, int K, const LoraDrop* dr, void* stream) {
+                                   long long M, int K, const LoraDrop* dr, void* stream, const LoraDgelu* dg = nullptr) {
     if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
         n_adapters * rp > 32 * LWU_MAXKS || (ldx % 4) || ldx < K || (ldt % 8) || ldt < n_adapters * rp || (lda % 8))
         return VT_ERR_BAD_SHAPE;
     if ((((uintptr_t)dT) | ((uintptr_t)A)) & 15) return VT_ERR_BAD_ALIGN;
     if (((uintptr_t)dX) & 7) return VT_ERR_BAD_ALIGN;
+    if (dg != nullptr) {
+        if (dr == nullptr || dg->U == nullptr || (dg->ldu % 4) || dg->ldu < K) return VT_ERR_BAD_SHAPE;
+        if (((uintptr_t)dg->U) & 7) return VT_ERR_BAD_ALIGN;
+    }
     const long long blocks = (M + 127) / 128;
     if (blocks > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
     const int NCp = (n_adapters * rp + 31) & ~31;
@@ -438,6 +462,9 @@ static int lora_up_add_wide_launch(void* dX, int ldx, const void* dT, int ldt, c
     if (dr == nullptr)
         hipLaunchKernelGGL(lora_wide_up_add_kernel<>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
                            (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K);
+    else if (dg != nullptr)
+        hipLaunchKernelGGL((lora_wide_up_add_kernel<LoraDrop, LoraDgelu>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream,
+                           (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr, *dg);
     else
         hipLaunchKernelGGL(lora_wide_up_add_kernel<LoraDrop>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
                            (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr);
@@ -452,6 +479,16 @@ extern "C" int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int l
     if (vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site0);
     return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, stream);
+}
+// the dgelu form (lora.hip, lora_up_add_kernel): the masked sum times gelu'(U[m,k]), U the saved pre-activation of the GELU whose
+// output the adapters read
+extern "C" int vt_lora_up_add_wide_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r,
+                                              int rp, const void* U, int ldu, long long M, int K, float p, unsigned long long seed,
+                                              int site0, void* stream) {
+    if (vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    const LoraDgelu dg = {(const bf16_t*)U, ldu};
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, stream, &dg);
 }
 
 // ---------------- write (alpha/r) * B into the ext-column K-extension of the packed weight and of its transpose ----------------

@@ -36,6 +36,14 @@ def _ext_widths(model):
     return (st.ext_qkv, st.ext_o) if st is not None else (EXT, EXT)
 
 
+def _ff_lora(model):
+    """(ff.net.0.proj adapted, ff.net.2 adapted, K-extension columns of either): the feed-forward LoRA targets"""
+    st = model.lora
+    if st is None or not (getattr(st, "ff1", False) or getattr(st, "ff2", False)):
+        return False, False, 0
+    return st.ff1, st.ff2, st.ext_ff
+
+
 def _ext_rows(w: torch.Tensor, ext: int) -> torch.Tensor:
     """[N,K] -> [N,K+ext] with a zero K-extension."""
     out = torch.zeros(w.shape[0], w.shape[1] + ext, dtype=BF16, device=w.device)
@@ -59,7 +67,8 @@ def pack(model) -> SimpleNamespace:
         if "lora" not in n and p.dtype != BF16:
             raise TypeError(f"parameter {n} is {p.dtype}; the MI355X engine computes in bf16 -- call .bfloat16()")
     eq, eo = _ext_widths(model)
-    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version, ext=(eq, eo))
+    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version, ext=(eq, eo), ff=_ff_lora(model))
+    ff1, ff2, ef = P.ff
     d = model.inner_dim
     with torch.no_grad():
         for i, blk in enumerate(model.transformer_blocks):
@@ -80,6 +89,14 @@ def pack(model) -> SimpleNamespace:
             w1, b1 = _lin(blk.ff.net[0].proj); w2, b2 = _lin(blk.ff.net[2])
             L.w1, L.b1, L.w1_t = w1, b1, w1.t().contiguous()
             L.w2, L.b2, L.w2_t = w2, b2, w2.t().contiguous()
+            if ff1:         # ff.net.0.proj adapted: both operands of W1 carry the K-extension, as the attention projections' do
+                L.w1, L.w1_t = _ext_rows(w1, ef), _ext_t(w1, ef)
+            if ff2:
+                # ff.net.2 adapted.  Forward: [W2 | s B2].  Backward: du = gelu'(u) (x) ([tg | dt2] [W2^T | A2^T]^T), the adapter's input-gradient
+                # correction as a K-extension of the product that carries the dGELU epilogue; dt2 = tg (s B2) from w2_bt [ext, d].
+                L.w2 = _ext_rows(w2, ef)
+                L.w2_t = _ext_rows(L.w2_t, ef)
+                L.w2_bt = torch.zeros(ef, w2.shape[0], dtype=BF16, device=w2.device)
             L.n1g, L.n1b = blk.norm1.norm.weight, blk.norm1.norm.bias
             L.n2g, L.n2b = blk.norm2.norm.weight, blk.norm2.norm.bias
             L.gq, L.bq, L.gk, L.bk = a.norm_q.weight, a.norm_q.bias, a.norm_k.weight, a.norm_k.bias
@@ -109,13 +126,30 @@ def pack(model) -> SimpleNamespace:
 def packed(model) -> SimpleNamespace:
     ft = getattr(model, "fullft", None)
     if (model._packed is None or (ft is not None and model._packed.ft_version != ft.version)
-            or model._packed.ext != _ext_widths(model)):
+            or model._packed.ext != _ext_widths(model) or model._packed.ff != _ff_lora(model)):
         model._packed = pack(model)          # full fine-tune: the transposed operand copies follow the updated weights
     P = model._packed
     st = model.lora
     if st is not None and P.lora_version != st.version:
         d, r, rp, eq, eo = model.inner_dim, st.r, st.rp, st.ext_qkv, st.ext_o
+        ff1, ff2, ef = P.ff
+        # feed-forward targets: one adapter per Linear, packed by the kernels that pack to_out.0's
+        if st.wide:
+            pack_b = lambda b, w, ld, n: ops.lora_pack_b_wide(b, w, ld, 1, n, r, rp, ef, st.scaling)
+            pack_bt = lambda b, w, ld, n: ops.lora_pack_bt_wide(b, w, ld, 1, n, r, rp, ef, st.scaling)
+        else:
+            pack_b = lambda b, w, ld, n: ops.lora_pack_b(b, w, ld, 1, n, r, st.scaling)
+            pack_bt = lambda b, w, ld, n: ops.lora_pack_bt(b, w, ld, 1, n, r, st.scaling)
         for i, L in enumerate(P.layers):
+            if ff1:
+                dff, b1 = L.w1.shape[0], st.view(st.flat, i, "B", 4)
+                pack_b(b1, L.w1[:, d:], d + ef, dff)
+                pack_bt(b1, L.w1_t[d:], dff, dff)
+            if ff2:
+                dff, b2 = L.w2_t.shape[0], st.view(st.flat, i, "B", 5)
+                pack_b(b2, L.w2[:, dff:], dff + ef, d)
+                pack_bt(b2, L.w2_bt, d, d)
+                L.w2_t[:, d:d + r].copy_(ops.transpose(st.view(st.flat_bf16, i, "A", 5)))       # A2^T: rank column i <- row i of A2
             if st.wide:
                 ops.lora_pack_b_wide(st.b_qkv(st.flat, i), L.w_qkv[:, d:], d + eq, 3, d, r, rp, eq, st.scaling)
                 ops.lora_pack_bt_wide(st.b_qkv(st.flat, i), L.w_qkv_t[d:], 3 * d, 3, d, r, rp, eq, st.scaling)
@@ -155,6 +189,10 @@ def _lora_proj(st, i, proj, buf):
     """(adapters, their stacked A rows [n r, d] in buf, K-extension width, site of the first adapter) of projection ``proj`` of layer i"""
     if proj == "qkv":
         return 3, st.a_qkv(buf, i), st.ext_qkv, 4 * i
+    if proj == "ff1":          # ff.net.0.proj / ff.net.2: their sites follow every attention site, so those masks do not move
+        return 1, st.view(buf, i, "A", 4), st.ext_ff, 4 * st.L + 2 * i
+    if proj == "ff2":
+        return 1, st.view(buf, i, "A", 5), st.ext_ff, 4 * st.L + 2 * i + 1
     return 1, st.a_out(buf, i), st.ext_o, 4 * i + 3
 
 
@@ -189,12 +227,13 @@ def _lora_down(st, i, proj, x, d, drop=None):
             ops.lora_down_drop(x, a[j * r:(j + nj) * r], nj * r, nj, x[:, d + j * r:], d, *drop, site + j, zero_cols=zc)
 
 
-def _lora_da(st, i, proj, x, dxe, d, drop=None):
-    """dA += dT^T x (drop: x under each adapter's mask); x: the projection's input, dT: the extension columns of dxe [M, d + ext]"""
+def _lora_da(st, i, proj, x, dxe, d, drop=None, dt0=None):
+    """dA += dT^T x (drop: x under each adapter's mask); x: the projection's input, dT: the extension columns of dxe [M, d + ext]
+    (dt0: dT where it lives elsewhere -- ff.net.2, whose dT sits beside the output gradient, not beside dx)"""
     n, ga, _, site = _lora_proj(st, i, proj, st.grad)
     r = st.r
     for j, nj in ([(j, 1) for j in range(n)] if st.wide else _narrow_calls(n, r)):          # lora_tn_wide: one adapter per call
-        dt, g = dxe[:, d + j * st.rp:], ga[j * r:(j + nj) * r]
+        dt, g = (dxe[:, d + j * st.rp:] if dt0 is None else dt0[:, j * st.rp:]), ga[j * r:(j + nj) * r]
         if st.wide and drop is None:
             ops.lora_tn_wide(x, dt, r, g, 1, d, 1.0, d)
         elif st.wide:
@@ -220,6 +259,16 @@ def _lora_dx(st, i, proj, dxe, d, drop=None):
             ops.lora_up_add(dxe, dxe[:, d + j * r:], a[j * r:(j + nj) * r], nj * r, d)
         else:
             ops.lora_up_add_drop(dxe, dxe[:, d + j * r:], a[j * r:(j + nj) * r], nj * r, nj, d, *drop, site + j)
+
+
+def _lora_dx_dgelu(st, i, du, dt, u, K, drop):
+    """du += gelu'(u) (x) keep (x) (dT A2) / (1 - p): ff.net.2's dX correction under lora_dropout.  The mask sits between dT A2 and the GELU, so
+    the term cannot ride in the K-extension of the W2^T product as it does without dropout; du already carries gelu'(u) (x) (tg W2)."""
+    _, a, _, site = _lora_proj(st, i, "ff2", st.flat_bf16)
+    if st.wide:
+        ops.lora_up_add_wide_dgelu_drop(du, dt, a, 1, st.r, st.rp, u, K, *drop, site)
+    else:
+        ops.lora_up_add_dgelu_drop(du, dt, a, st.r, 1, u, K, *drop, site)
 
 
 # Aliases that only tests/test_side_kernels_gpu.py calls; they go when its call sites move to the helpers above.
@@ -251,6 +300,8 @@ def saved_bytes_per_block(model, M: int) -> int:
     cols = 2 * d + ext2 + 3 * d + 2 * d + d + model.config.ff_mult * d + d         # x1, o | qkv | qkh | h1 | u | h_in
     if getattr(model, "fullft", None) is not None:
         cols += d + model.config.ff_mult * d + 2 * d                                  # x2 | g | ao, fo
+    ff1, ff2, ef = _ff_lora(model)             # an adapted feed-forward Linear keeps its input (dA) with the K-extension (dB)
+    cols += (d + ef if ff1 else 0) + (model.config.ff_mult * d + ef if ff2 else 0)
     return M * cols * 2
 
 
@@ -313,19 +364,25 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
     # --- feed-forward branch ---
     a.mean2, a.rstd2 = E(M, dt=torch.float32), E(M, dt=torch.float32)
     keep_ff = save and ft is not None                              # dW1 / dW2 need the FF inputs
-    x2 = E(M, d) if keep_ff else xg
-    gact = E(M, c.ff_mult * d) if keep_ff else gbuf
+    ff1, ff2, ef = _ff_lora(model)                                 # LoRA on ff.net.0.proj / ff.net.2: x2 / gact carry a K-extension
+    dff = c.ff_mult * d
+    x2 = E(M, d + ef if ff1 else d) if (keep_ff or (save and ff1)) else xg          # an adapted Linear's input is kept for dA, dB
+    gact = E(M, dff + ef if ff2 else dff) if (keep_ff or (save and ff2)) else gbuf
     ops.ln_modulate_fwd(h1, x2, Lw.n2g, Lw.n2b, (m2.shift_txt, m2.scale_txt, m2.shift_vid, m2.scale_vid, m2.bs),
                         a.mean2, a.rstd2, d, S, St, c.norm_eps)
-    u = E(M, c.ff_mult * d) if save else gbuf.new_empty(M, c.ff_mult * d)
-    ops.gemm(x2, Lw.w1, gact, Lw.b1, epilogue=EPI_BIAS_GELU, pre_act_out=u)
+    if ff1:
+        _lora_down(st, i, "ff1", x2, d, drop)
+    u = E(M, dff) if save else gbuf.new_empty(M, dff)
+    ops.gemm(x2, Lw.w1, gact, Lw.b1, epilogue=EPI_BIAS_GELU, pre_act_out=u, K=d + ef if ff1 else None)
+    if ff2:
+        _lora_down(st, i, "ff2", gact, dff, drop)
     h2 = E(M, d)
     fo = E(M, d) if keep_ff else None
     ops.gemm(gact, Lw.w2, h2, Lw.b2, epilogue=EPI_GATED_RES, residual=h1, gate_txt=m2.gate_txt, gate_vid=m2.gate_vid,
-             gate_bstride=m2.bs, S=S, St=St, pre_act_out=fo)
+             gate_bstride=m2.bs, S=S, St=St, pre_act_out=fo, K=dff + ef if ff2 else None)
     if save:
         a.x1, a.qkv, a.qkh, a.o, a.lse, a.h1, a.u = x1, qkv, qkh, o, lse, h1, u
-        a.x2, a.g, a.ao, a.fo = (x2, gact, ao, fo) if ft is not None else (None, None, None, None)
+        a.x2, a.g, a.ao, a.fo = (x2, gact, ao, fo) if ft is not None else (x2 if ff1 else None, gact if ff2 else None, None, None)
     return h2, a
 
 
@@ -372,7 +429,9 @@ def run_forward(model, x, text, t, save: bool, rope=None):
         rope = (rope[0], rope[1], S, St)
 
     dims = (B, Fr, C, Hh, Ww, S, St, Sv, M)
-    scratch = SimpleNamespace(xg=E(M, d), gbuf=E(M, c.ff_mult * d))     # transient: norm2 output, GELU output
+    ff1, ff2, ef = _ff_lora(model)
+    scratch = SimpleNamespace(xg=E(M, d + ef if ff1 else d),            # transient: norm2 output, GELU output (each with the K-extension
+                              gbuf=E(M, c.ff_mult * d + (ef if ff2 else 0)))           # of its Linear when that one is adapted)
     recompute = save and _use_recompute(model, dims)
     drop = lora_dropout_seed(model)         # None unless lora_dropout > 0 and model.training
     saved: List[SimpleNamespace] = []
@@ -436,9 +495,12 @@ def run_backward(model, ctx, dout: torch.Tensor):
                             model.norm_final.weight, None, None, dh[b * S + St:(b + 1) * S], d, Sv, 0)
 
     # ---- transient buffers shared by all blocks ----
+    ff1, ff2, ef = _ff_lora(model)
+    dff = c.ff_mult * d
     tg = E(M, d)
-    du = E(M, c.ff_mult * d)
-    dx2 = E(M, d)
+    tgf = E(M, d + ef) if ff2 else tg            # ff.net.2 adapted: the feed-forward branch's output gradient as [tg | dT2]
+    du = E(M, dff)
+    dx2 = E(M, d + ef) if ff1 else E(M, d)       # ff.net.0.proj adapted: [dx2 | dT1]
     dh1 = E(M, d)
     dO = E(M, d + eo)
     dq = E(B, S, d, dt=torch.float32)
@@ -454,9 +516,24 @@ def run_backward(model, ctx, dout: torch.Tensor):
             _, a = block_forward(model, i, a.h_in, mod, ctx.dims, ctx.rope, True, ctx.scratch, drop)
         m1, m2 = _mod(mod, 2 * i, d), _mod(mod, 2 * i + 1, d)
         # --- feed-forward branch:  h2 = h1 + gate_ff * W2 gelu(W1 x2 + b1) ---
-        ops.gate_mul(dh, tg, m2.gate_txt, m2.gate_vid, m2.bs, d, S, St)
-        ops.gemm(tg, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u)
-        ops.gemm(du, Lw.w1_t, dx2, None)
+        ops.gate_mul(dh, tgf, m2.gate_txt, m2.gate_vid, m2.bs, d, S, St)
+        if ff2:
+            # h2 = h1 + gate (x) [g | T2] [W2 | s B2]^T, g = gelu(u), T2 = (keep (x) g) A2^T / (1 - p)
+            ops.gemm(tgf, Lw.w2_bt, tgf[:, d:], None, K=d)                              # dT2 = tg (s B2)
+            tn(tgf, a.g[:, dff:], r, st.view(st.grad, i, "B", 5), r, 1, st.scaling, d)   # dB2 (reads the saved T2: no mask)
+            _lora_da(st, i, "ff2", a.g, None, dff, drop, dt0=tgf[:, d:])                # dA2
+            if drop is None:        # du = gelu'(u) (x) (tg W2 + dT2 A2): the correction rides in the K-extension, under the dGELU epilogue
+                ops.gemm(tgf, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u, K=d + ef)
+            else:                   # the mask sits between dT2 A2 and the GELU: the base product, then the dgelu form of the dX correction
+                ops.gemm(tgf, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u, K=d)
+                _lora_dx_dgelu(st, i, du, tgf[:, d:], a.u, dff, drop)
+        else:
+            ops.gemm(tg, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u)
+        ops.gemm(du, Lw.w1_t, dx2, None)                                  # ff.net.0.proj adapted: [M, d+ext]: dx2 | dT1
+        if ff1:
+            tn(du, a.x2[:, d:], r, st.view(st.grad, i, "B", 4), r, 1, st.scaling, dff)  # dB1
+            _lora_da(st, i, "ff1", a.x2, dx2, d, drop)                                  # dA1
+            _lora_dx(st, i, "ff1", dx2, d, drop)
         ops.ln_modulate_bwd(dx2, a.h1, a.mean2, a.rstd2, Lw.n2g, (m2.scale_txt, m2.scale_vid, m2.bs), dh, dh1, d, S, St)
         # --- attention branch:  h1 = h + gate_msa * (Wo' [O | T2]) ---
         ops.gate_mul(dh1, tg, m1.gate_txt, m1.gate_vid, m1.bs, d, S, St)

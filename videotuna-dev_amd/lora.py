@@ -8,6 +8,9 @@ State-dict keys follow peft 0.12: ``base_model.model.<path>.base_layer.weight``,
 ``base_model.model.<path>.lora_A.default.weight`` -- the reference only relies on the substring "lora"
 (cogvideo_pl.py:781-787, videotuna/utils/callbacks.py:44-46).
 
+``target_modules`` may name any of the six Linears of a block (TARGETS: the attention projections and the feed-forward pair
+ff.net.0.proj / ff.net.2), matched by peft's rule: a module is wrapped when its path equals a target or ends in "." + target.
+
 All adapter weights live in ONE flat fp32 master buffer (plus a flat fp32 gradient buffer and a flat bf16 compute
 copy) so the optimizer is one fused kernel launch and data-parallel training needs one all-reduce.
 """
@@ -15,13 +18,44 @@ from __future__ import annotations
 
 import math
 import os
+import re
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 
-TARGETS = ("to_q", "to_k", "to_v", "to_out.0")
+TARGETS = ("to_q", "to_k", "to_v", "to_out.0", "ff.net.0.proj", "ff.net.2")
+N_ATTN = 4             # TARGETS[:4]: the attention projections (adapter index j = 0..3); j = 4, 5: the feed-forward pair
+# module paths of the CogVideoX DiT (dit.py), for peft's target rule on a model that is not an nn.Module: the adaptable Linears of a
+# block (TARGETS order) and everything else a target could name
+_BLOCK_LINEARS = ("attn1.to_q", "attn1.to_k", "attn1.to_v", "attn1.to_out.0", "ff.net.0.proj", "ff.net.2")
+_OTHER_PATHS = ("patch_embed", "patch_embed.proj", "patch_embed.text_proj", "time_embedding", "time_embedding.linear_1",
+                "time_embedding.linear_2", "norm_final", "norm_out", "norm_out.linear", "norm_out.norm", "proj_out",
+                "transformer_blocks", "transformer_blocks.0", "transformer_blocks.0.norm1", "transformer_blocks.0.norm1.linear",
+                "transformer_blocks.0.norm1.norm", "transformer_blocks.0.norm2", "transformer_blocks.0.norm2.linear",
+                "transformer_blocks.0.norm2.norm", "transformer_blocks.0.attn1", "transformer_blocks.0.attn1.norm_q",
+                "transformer_blocks.0.attn1.norm_k", "transformer_blocks.0.attn1.to_out", "transformer_blocks.0.attn1.to_out.1",
+                "transformer_blocks.0.ff", "transformer_blocks.0.ff.net", "transformer_blocks.0.ff.net.0", "transformer_blocks.0.ff.net.1")
+_BLOCK_PATH = re.compile(r"transformer_blocks\.\d+\.(.+)$")
+
+
+def resolve_targets(model, target_modules) -> List[str]:
+    """The members of TARGETS that ``target_modules`` names by peft's rule -- a module is wrapped when its path equals a target or
+    ends in "." + target -- in TARGETS order.  A target that matches nothing, or anything but the six block Linears (bare "proj"
+    also matches patch_embed.proj, a convolution), raises."""
+    if hasattr(model, "named_modules"):
+        paths = [n for n, _ in model.named_modules() if n]
+    else:
+        paths = list(_OTHER_PATHS) + ["transformer_blocks.0." + b for b in _BLOCK_LINEARS]
+    hit = set()
+    for t in target_modules:
+        matched = [p for p in paths if p == t or p.endswith("." + t)]
+        subs = [_BLOCK_PATH.match(p) for p in matched]
+        if not matched or any(m is None or m.group(1) not in _BLOCK_LINEARS for m in subs):
+            raise ValueError(f"unsupported LoRA target {t!r}; the block Linears {TARGETS} of the CogVideoX DiT are supported")
+        hit.update(_BLOCK_LINEARS.index(m.group(1)) for m in subs)
+    return [TARGETS[j] for j in sorted(hit)]
 NARROW_MAX_R = 16      # up to here the adapters ride in a fixed 64-column K-extension (csrc/lora.hip)
 MAX_R = 128            # above NARROW_MAX_R: the wide layout on the MFMA rank-side kernels (csrc/lora_wide.hip)
 
@@ -96,7 +130,9 @@ class LoraLinear(nn.Module):
 
 
 class LoraState:
-    """Flat storage for every adapter of a DiT.  Per layer: A_qkv [3r,d] | A_o [r,d] | B_qkv [3d,r] | B_o [d,r]."""
+    """Flat storage for every adapter of a DiT.  Per layer: A_qkv [3r,d] | A_o [r,d] | B_qkv [3d,r] | B_o [d,r]; behind the L attention
+    slabs, only when a feed-forward Linear is targeted, per layer: A_ff1 [r,d] | B_ff1 [4d,r] (ff.net.0.proj) and / or A_ff2 [r,4d] |
+    B_ff2 [d,r] (ff.net.2) -- the attention part of the buffers is the same with and without them."""
 
     def __init__(self, model, cfg: LoraConfig):
         self.cfg = cfg
@@ -107,17 +143,21 @@ class LoraState:
         self.p = float(cfg.lora_dropout)      # lora_dropout: > 0 selects the _drop rank-side kernels in training mode
         self.d = model.inner_dim
         self.L = model.config.num_layers
-        tm = list(cfg.target_modules or TARGETS)
-        for t in tm:
-            if t not in TARGETS:
-                raise ValueError(f"unsupported LoRA target {t!r}; the attention projections {TARGETS} are supported")
-        self.targets = tm
+        self.targets = resolve_targets(model, list(cfg.target_modules or TARGETS[:N_ATTN]))
+        self.ff1, self.ff2 = "ff.net.0.proj" in self.targets, "ff.net.2" in self.targets
         r, d = self.r, self.d
         self.per_layer = 8 * r * d
+        # feed-forward adapters: one per Linear, so the K-extension is the single-adapter width of to_out.0
+        self.dff = (int(getattr(model.config, "ff_mult", 4)) * d) if (self.ff1 or self.ff2) else 0
+        self.ext_ff = self.ext_o
+        self.ff_base = self.L * self.per_layer
+        self.ff_off = {4: 0, 5: r * (d + self.dff) if self.ff1 else 0}         # offsets inside one layer's feed-forward slab
+        self.ff_per_layer = r * (d + self.dff) * (int(self.ff1) + int(self.ff2))
+        self.numel = self.L * (self.per_layer + self.ff_per_layer)
         dev = model.device
-        self.flat = torch.zeros(self.L * self.per_layer, dtype=torch.float32, device=dev)
+        self.flat = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.grad = torch.zeros_like(self.flat)
-        self.flat_bf16 = torch.zeros(self.L * self.per_layer, dtype=torch.bfloat16, device=dev)
+        self.flat_bf16 = torch.zeros(self.numel, dtype=torch.bfloat16, device=dev)
         self.version = 0              # bumped whenever the master weights change (optimizer step / load)
         self.params: List[nn.Parameter] = []
 
@@ -127,7 +167,14 @@ class LoraState:
     def off_B(self, j):
         return 4 * self.r * self.d + j * self.d * self.r
 
+    def ff_dims(self, j):     # (in_features, out_features) of feed-forward Linear j: 4 = ff.net.0.proj, 5 = ff.net.2
+        return (self.d, self.dff) if j == 4 else (self.dff, self.d)
+
     def view(self, buf, layer, kind, j):
+        if j >= N_ATTN:
+            fin, fout = self.ff_dims(j)
+            o = self.ff_base + layer * self.ff_per_layer + self.ff_off[j] + (0 if kind == "A" else self.r * fin)
+            return buf[o:o + self.r * (fin if kind == "A" else fout)].view((self.r, fin) if kind == "A" else (fout, self.r))
         o = layer * self.per_layer + (self.off_A(j) if kind == "A" else self.off_B(j))
         n = self.r * self.d
         return buf[o:o + n].view((self.r, self.d) if kind == "A" else (self.d, self.r))
@@ -151,13 +198,21 @@ class LoraState:
     def init(self, seed: int = 1):
         g = torch.Generator().manual_seed(seed)
         bound = 1.0 / math.sqrt(self.d)
-        host = torch.zeros(self.L * self.per_layer, dtype=torch.float32)
+        host = torch.zeros(self.numel, dtype=torch.float32)
         for layer in range(self.L):
-            for j, t in enumerate(TARGETS):
+            for j, t in enumerate(TARGETS[:N_ATTN]):
                 if t in self.targets:
                     a = (torch.rand((self.r, self.d), generator=g) * 2 - 1) * bound
                     o = layer * self.per_layer + self.off_A(j)
                     host[o:o + a.numel()] = a.reshape(-1)
+        # the feed-forward adapters draw after every attention adapter (a seed's attention init does not depend on the target list),
+        # each with peft's bound for its own in_features
+        for layer in range(self.L):
+            for j in range(N_ATTN, len(TARGETS)):
+                if TARGETS[j] in self.targets:
+                    fin = self.ff_dims(j)[0]
+                    a = (torch.rand((self.r, fin), generator=g) * 2 - 1) / math.sqrt(fin)
+                    self.view(host, layer, "A", j).copy_(a)
         with torch.no_grad():
             self.flat.copy_(host.to(self.flat.device))
         self.mark_changed()
@@ -178,7 +233,7 @@ class LoraState:
         if not self.params:
             return
         dev = self.params[0].device
-        new_flat = torch.zeros(self.L * self.per_layer, dtype=torch.float32, device=dev)
+        new_flat = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         for p, (layer, kind, j) in zip(self.params, self._index):
             self.view(new_flat, layer, kind, j).copy_(p.detach().to(torch.float32))
         self.flat = new_flat
@@ -203,6 +258,10 @@ def inject(model, cfg: LoraConfig, seed: int = 1) -> LoraState:
             if t == "to_out.0":
                 base = blk.attn1.to_out[0]
                 blk.attn1.to_out[0] = LoraLinear(base, a, b, st.scaling)
+            elif t == "ff.net.0.proj":
+                blk.ff.net[0].proj = LoraLinear(blk.ff.net[0].proj, a, b, st.scaling)
+            elif t == "ff.net.2":
+                blk.ff.net[2] = LoraLinear(blk.ff.net[2], a, b, st.scaling)
             else:
                 base = getattr(blk.attn1, t)
                 setattr(blk.attn1, t, LoraLinear(base, a, b, st.scaling))

@@ -776,6 +776,33 @@ def lora_up_add_wide_drop(dx, dt, a, n_adapters: int, r: int, rp: int, K: int, p
           "vt_lora_up_add_wide_drop")
 
 
+def _req_preact(u, dx, K: int, dt=None, a=None, rows: int = 0, cols: int = 0):
+    _req(u, BF16, "u", 2)
+    if u.shape[0] != dx.shape[0] or u.shape[1] < K or dx.shape[1] < K:
+        raise ValueError(f"u {tuple(u.shape)} / dx {tuple(dx.shape)}: expected {dx.shape[0]} rows of at least K = {K} columns")
+    if dt is not None and (dt.shape[0] != dx.shape[0] or dt.shape[1] < cols or a.shape[0] < rows or a.shape[1] < K):
+        raise ValueError(f"dt {tuple(dt.shape)} / a {tuple(a.shape)}: expected dt [{dx.shape[0]}, >= {cols}] and a [>= {rows}, >= {K}]")
+
+
+def lora_up_add_dgelu_drop(dx, dt, a, R: int, n_adapters: int, u, K: int, p: float, seed: int, site0: int):
+    """dx[:, :K] += gelu'(u[:, :K]) / (1-p) * sum_j keep_j * (dt[:, j r:(j+1) r] @ a[j r:(j+1) r]) in place: the dropped dX correction of
+    adapters whose input is gelu(u) (ff.net.2), added to a dx that already carries the factor gelu'(u)."""
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2); _req_preact(u, dx, K, dt, a, R, R)
+    check(load_library().vt_lora_up_add_dgelu_drop(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(), a.stride(0),
+                                                   R, n_adapters, u.data_ptr(), u.stride(0), dx.shape[0], K, float(p), int(seed) & _U64,
+                                                   site0, _stream()), "vt_lora_up_add_dgelu_drop")
+
+
+def lora_up_add_wide_dgelu_drop(dx, dt, a, n_adapters: int, r: int, rp: int, u, K: int, p: float, seed: int, site0: int):
+    """lora_up_add_dgelu_drop in the wide layout (adapter j = columns [j rp, j rp + r) of dt)."""
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    _req_preact(u, dx, K, dt, a, n_adapters * r, n_adapters * rp)
+    check(load_library().vt_lora_up_add_wide_dgelu_drop(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(),
+                                                        a.stride(0), n_adapters, r, rp, u.data_ptr(), u.stride(0), dx.shape[0], K,
+                                                        float(p), int(seed) & _U64, site0, _stream()),
+          "vt_lora_up_add_wide_dgelu_drop")
+
+
 # =====================================================================================================================
 # VideoCrafter2 UNet path (include/vt355.h, second half): channels-last [N, T, H, W, C] activations
 # =====================================================================================================================
