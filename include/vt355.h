@@ -331,6 +331,24 @@ int vt_lora_up_add_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const 
 int vt_lora_up_add_wide_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
                                    const void* U, int ldu, long long M, int K, float p, unsigned long long seed, int site0, void* stream);
 
+/* DoRA (peft 0.12 LoraConfig(use_dora=True), DoraLinearLayer without dropout): y = b + c (x) (W x + s B A x), c_j = m_j / norm_j,
+ * norm_j = ||W_j + s (B A)_j||_2 detached.  c is folded into the packed operands once per adapter version (csrc/dora.hip).
+ * vt_dora_norm: out[j] = norm_j (mag == NULL) or mag[j] / norm_j, j < n_adapters * d_out; W bf16 [n_adapters d_out, K] (row stride ldw),
+ *   A bf16 [n_adapters r, K] (lda), B bf16 [n_adapters d_out, r] contiguous -- adapter a owns rows [a d_out, (a+1) d_out) of W and B and
+ *   rows [a r, (a+1) r) of A.  fp32 sums in an order fixed by (K, r); B A is never written to memory.  1 <= r <= 128, n_adapters <= 3,
+ *   d_out % 8 == 0, K % 8 == 0, W and A 16-byte aligned.
+ * vt_dora_scale: dst[j, k] = bf16(c[by_col ? k : j] * src[j, k]) for rows x cols (cols % 8 == 0), one round-to-nearest-even of the fp32
+ *   product; src == dst allowed.  vt_dora_transpose_scale: dst[k, j] = bf16(c[j] * src[j, k]), src [rows, cols], both multiples of 8.
+ * vt_dora_db_add: G[j, i] += c[j] * S[j, i] over [N, r] fp32.  vt_dora_dm: dm[j] += (sum_gy[j] - bias[j] * sum_g[j]) / mag[j], the
+ *   magnitude gradient from vt_group_colsum(X = g, Y = y)'s two sums; bias bf16 [N] | NULL. */
+int vt_dora_norm(const void* W, int ldw, const void* A, int lda, const void* B, int n_adapters, int d_out, int r, int K, float scale,
+                 const float* mag, float* out, void* stream);
+int vt_dora_scale(const void* src, long long lds_, void* dst, long long ldd, const float* c, int rows, int cols, int by_col, void* stream);
+int vt_dora_transpose_scale(const void* src, long long src_ld, void* dst, long long dst_ld, const float* c, int rows, int cols,
+                            void* stream);
+int vt_dora_db_add(float* G, const float* S, const float* c, int N, int r, void* stream);
+int vt_dora_dm(const float* sum_g, const float* sum_gy, const void* bias, const float* mag, float* dm, int N, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * VideoCrafter2 UNet path (BASELINE configs[3]): lvdm UNetModel.forward and its backward
  * (videotuna/models/lvdm/modules/networks/openaimodel3d.py:650-694) on ONE channels-last layout [B, T, H, W, C].

@@ -13,6 +13,12 @@ added (a model each; the entry "<rank>+ff" carries the delta against the same ra
 
     python tools/bench_lora_rank.py --ranks 4,64 --lora-dropout 0.1 > profiles/lora_dropout_step.json
     python tools/bench_lora_rank.py --ranks 4,64 --targets attn,attn+ff --lora-dropout 0.1 > profiles/lora_ff_step.json
+--use-dora times every rank as LoRA and again with use_dora=True (a model each: the flat layouts differ; the blocks alternate like the
+others): the entry "<rank>+dora" carries the delta against the same rank and targets without DoRA, and both carry "repack_ms", the
+time of engine.packed() right after an adapter version bump (LoRA: the pack kernels; DoRA: those, the row norms and the scaled
+refresh of every operand) -- part of every step, measured alone.
+
+    python tools/bench_lora_rank.py --ranks 4,64 --use-dora > profiles/lora_dora_step.json
 """
 import argparse
 import json
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=4)
     ap.add_argument("--lora-dropout", type=float, default=0.0, help="P > 0: time lora_dropout = 0 and = P per rank, alternating")
     ap.add_argument("--targets", default="attn", help="comma list of attn | attn+ff: the adapted Linears (attn+ff adds ff.net.0.proj, ff.net.2)")
+    ap.add_argument("--use-dora", action="store_true", help="time every rank with use_dora False and True, alternating")
     ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 is not the benchmark's model")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -58,7 +65,7 @@ def main():
     dgen = torch.Generator(device=dev).manual_seed(20230211)
 
     runs = {}
-    for r, ts in [(r, ts) for r in ranks for ts in tsets]:
+    for r, ts, dora in [(r, ts, dora) for r in ranks for ts in tsets for dora in ([False, True] if args.use_dora else [False])]:
         model = CogVideoXTransformer3DModel(num_layers=args.layers).to(dev)
         gen = torch.Generator(device=dev).manual_seed(1234)            # bench.py's weights
         with torch.no_grad():
@@ -67,12 +74,12 @@ def main():
                 if name.endswith(("norm.weight", "norm_final.weight", "norm_q.weight", "norm_k.weight")):
                     p.add_(1.0)
         model.requires_grad_(False)
-        peft = get_peft_model(model, LoraConfig(r=r, lora_alpha=r / 4.0, target_modules=target_sets[ts]))
+        peft = get_peft_model(model, LoraConfig(r=r, lora_alpha=r / 4.0, target_modules=target_sets[ts], use_dora=dora))
         st = peft._lora_state
-        key = str(r) + ts[4:]                                      # "4", "4+ff"
+        key = str(r) + ts[4:] + ("+dora" if dora else "")          # "4", "4+ff", "4+dora"
         runs[key] = dict(peft=peft, st=st, opt=FusedAdamW(st.params, lr=1.2e-5, lora_state=st), ms=[], peak=0.0, loss=None, p=0.0, rank=r,
                          targets=ts, model=model)
-        if args.lora_dropout > 0:
+        if args.lora_dropout > 0 and not dora:
             LoraConfig(r=r, lora_dropout=args.lora_dropout)        # validates P
             runs[f"{key}+drop"] = dict(runs[key], ms=[], p=args.lora_dropout)
 
@@ -131,6 +138,22 @@ def main():
             if "attn" in tsets:
                 same =statistics.median(runs[str(run["rank"]) + ("+drop" if run["p"] > 0 else "")]["ms"])
                 res["ranks"][key].update({"delta_vs_attn_only_ms": round(med - same, 2), "delta_vs_attn_only_pct": round(100.0 * (med - same) / same, 2)})
+        if args.use_dora and run["p"] == 0:
+            from vt355 import engine
+            times = []
+            for _ in range(3):
+                st.version += 1
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                engine.packed(run["model"])
+                torch.cuda.synchronize()
+                times.append(1000.0 * (time.perf_counter() - t0))
+            res["ranks"][key]["repack_ms"] = round(statistics.median(times), 2)
+            if st.dora:
+                same = statistics.median(runs[key[:-5]]["ms"])
+                res["ranks"][key].update({"use_dora": True, "delta_vs_lora_ms": round(med - same, 2),
+                                          "delta_vs_lora_pct": round(100.0 * (med - same) / same, 2),
+                                          "spread_of_lora_ms": round(max(runs[key[:-5]]["ms"]) - min(runs[key[:-5]]["ms"]), 2)})
         if run["p"] > 0:
             same = statistics.median(runs[key[:-5]]["ms"])
             res["ranks"][key].update({"lora_dropout": run["p"], "delta_vs_no_dropout_ms": round(med - same, 2),

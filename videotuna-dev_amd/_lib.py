@@ -93,6 +93,12 @@ PROTOTYPES = {
     "vt_lora_up_add_wide_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_up_add_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_up_add_wide_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    # DoRA (use_dora): row norms / c = m / norm, the scaled operand refresh, the dB and dm finishes (csrc/dora.hip)
+    "vt_dora_norm": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _fp, _fp, _vp],
+    "vt_dora_scale": [_vp, _ll, _vp, _ll, _fp, _i, _i, _i, _vp],
+    "vt_dora_transpose_scale": [_vp, _ll, _vp, _ll, _fp, _i, _i, _vp],
+    "vt_dora_db_add": [_fp, _fp, _fp, _i, _i, _vp],
+    "vt_dora_dm": [_fp, _fp, _vp, _fp, _fp, _i, _vp],
     # ---- VideoCrafter2 UNet path ----
     "vt_conv_cl": [_vp, _ll, _vp, _vp, _fp, _i, _vp, _ll, _vp, _ll] + [_i] * 13 + [_vp],
     "vt_conv_dw_cl": [_vp, _ll, _vp, _ll, _fp] + [_i] * 13 + [_i, _vp],

@@ -14,6 +14,7 @@ from typing import List, Optional
 import torch
 
 from . import ops
+from .lora import TARGETS
 from .ops import BF16, EPI_BIAS, EPI_BIAS_GELU, EPI_DGELU, EPI_GATED_RES
 
 EXT = 64          # K-extension width without adapters and for LoRA ranks <= 16; wider ranks: LoraState.ext_qkv / ext_o
@@ -44,6 +45,12 @@ def _ff_lora(model):
     return st.ff1, st.ff2, st.ext_ff
 
 
+def _dora(model):
+    """the LoRA state when its adapters are weight-decomposed (LoraConfig.use_dora), else None"""
+    st = model.lora
+    return st if st is not None and getattr(st, "dora", False) else None
+
+
 def _ext_rows(w: torch.Tensor, ext: int) -> torch.Tensor:
     """[N,K] -> [N,K+ext] with a zero K-extension."""
     out = torch.zeros(w.shape[0], w.shape[1] + ext, dtype=BF16, device=w.device)
@@ -67,7 +74,8 @@ def pack(model) -> SimpleNamespace:
         if "lora" not in n and p.dtype != BF16:
             raise TypeError(f"parameter {n} is {p.dtype}; the MI355X engine computes in bf16 -- call .bfloat16()")
     eq, eo = _ext_widths(model)
-    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version, ext=(eq, eo), ff=_ff_lora(model))
+    P = SimpleNamespace(layers=[], lora_version=-1, ft_version=-1 if ft is None else ft.version, ext=(eq, eo), ff=_ff_lora(model),
+                        dora=_dora(model) is not None)
     ff1, ff2, ef = P.ff
     d = model.inner_dim
     with torch.no_grad():
@@ -86,6 +94,12 @@ def pack(model) -> SimpleNamespace:
                 wqkv = torch.cat([wq, wk, wv], 0)
                 L.w_qkv = _ext_rows(wqkv, eq); L.b_qkv = torch.cat([bq, bk, bv]).contiguous(); L.w_qkv_t = _ext_t(wqkv, eq)
                 L.w_o = _ext_rows(wo, eo); L.b_o = bo; L.w_o_t = _ext_t(wo, eo)
+                if P.dora:
+                    # DoRA rescales the operands from the pristine weights at every adapter version (_dora_refresh): the fused q | k | v
+                    # weight stays as one more copy (3 d^2 bf16 per layer; the other Linears' pristine weights are their parameters) beside
+                    # the factors c = m / ||W + s B A|| of each projection, 1 where a Linear is not adapted
+                    L.w_qkv0 = wqkv
+                    L.c_qkv, L.c_o = (torch.ones(n, dtype=torch.float32, device=wo.device) for n in (3 * d, d))
             w1, b1 = _lin(blk.ff.net[0].proj); w2, b2 = _lin(blk.ff.net[2])
             L.w1, L.b1, L.w1_t = w1, b1, w1.t().contiguous()
             L.w2, L.b2, L.w2_t = w2, b2, w2.t().contiguous()
@@ -97,6 +111,9 @@ def pack(model) -> SimpleNamespace:
                 L.w2 = _ext_rows(w2, ef)
                 L.w2_t = _ext_rows(L.w2_t, ef)
                 L.w2_bt = torch.zeros(ef, w2.shape[0], dtype=BF16, device=w2.device)
+            if P.dora:
+                L.c_1 = torch.ones(w1.shape[0], dtype=torch.float32, device=w1.device) if ff1 else None
+                L.c_2 = torch.ones(w2.shape[0], dtype=torch.float32, device=w2.device) if ff2 else None
             L.n1g, L.n1b = blk.norm1.norm.weight, blk.norm1.norm.bias
             L.n2g, L.n2b = blk.norm2.norm.weight, blk.norm2.norm.bias
             L.gq, L.bq, L.gk, L.bk = a.norm_q.weight, a.norm_q.bias, a.norm_k.weight, a.norm_k.bias
@@ -126,7 +143,8 @@ def pack(model) -> SimpleNamespace:
 def packed(model) -> SimpleNamespace:
     ft = getattr(model, "fullft", None)
     if (model._packed is None or (ft is not None and model._packed.ft_version != ft.version)
-            or model._packed.ext != _ext_widths(model) or model._packed.ff != _ff_lora(model)):
+            or model._packed.ext != _ext_widths(model) or model._packed.ff != _ff_lora(model)
+            or model._packed.dora != (_dora(model) is not None)):
         model._packed = pack(model)          # full fine-tune: the transposed operand copies follow the updated weights
     P = model._packed
     st = model.lora
@@ -160,8 +178,74 @@ def packed(model) -> SimpleNamespace:
             ops.lora_pack_bt(st.b_qkv(st.flat, i), L.w_qkv_t[d:], 3 * d, 3, d, r, st.scaling)
             ops.lora_pack_b(st.b_out(st.flat, i), L.w_o[:, d:], d + eo, 1, d, r, st.scaling)
             ops.lora_pack_bt(st.b_out(st.flat, i), L.w_o_t[d:], d, 1, d, r, st.scaling)
+        if P.dora:
+            for i, L in enumerate(P.layers):
+                _dora_refresh(model, st, i, L, P.ff)
         P.lora_version = st.version
     return P
+
+
+# DoRA (DESIGN 3 "DoRA"): y = b + c (x) (W x + s B A x), c_j = m_j / ||W_j + s (B A)_j|| with the norm detached.  The extended products
+# already compute W x + s B A x in one GEMM, so c is folded into the operands: forward [c W | c s B]; of the transposed operands that
+# multiply the output gradient g, the base part indexed by the output feature and the s B^T extension rows (w2_bt for ff.net.2), which
+# makes dx and dT = g' (s B), g' = c (x) g, and with them dA, the plain LoRA backward on g'.  Only dB = diag(c) s g^T T (_lora_db) and the
+# magnitude gradient (_dora_dm) need kernels of their own.  The fold runs here, once per adapter version (an optimizer step or a load).
+def _dora_fold(st, w0, a, b, n, mag, c, w_fwd, wt_base, wt_ext, not_adapted=()):
+    """c = mag / ||w0 + s b a|| (1 on the rows of not_adapted), then the four operand parts of one projection: the base columns of w_fwd and
+    the base part wt_base of the transposed operand from the pristine w0 [N, K], their extension parts (just written by the pack kernels
+    from the masters) in place"""
+    K = w0.shape[1]
+    ops.dora_norm(w0, a, b, n, st.r, st.scaling, c, mag=mag)
+    for rows in not_adapted:
+        c[rows].fill_(1.0)
+    ops.dora_scale(w0, w_fwd[:, :K], c)
+    ops.dora_scale(w_fwd[:, K:], w_fwd[:, K:], c)
+    ops.dora_transpose_scale(w0, wt_base, c)
+    ops.dora_scale(wt_ext, wt_ext, c, by_col=True)
+
+
+def _dora_refresh(model, st, i, L, ff):
+    d, bf = model.inner_dim, st.flat_bf16
+    ff1, ff2, _ = ff
+    blk = model.transformer_blocks[i]
+    qkv = [t in st.targets for t in ("to_q", "to_k", "to_v")]
+    if any(qkv):
+        _dora_fold(st, L.w_qkv0, st.a_qkv(bf, i), st.b_qkv(bf, i), 3, st.mag_qkv(st.flat, i), L.c_qkv, L.w_qkv, L.w_qkv_t[:d], L.w_qkv_t[d:],
+                   [slice(j * d, (j + 1) * d) for j in range(3) if not qkv[j]])
+    if "to_out.0" in st.targets:
+        _dora_fold(st, _lin(blk.attn1.to_out[0])[0], st.a_out(bf, i), st.b_out(bf, i), 1, st.view(st.flat, i, "M", 3), L.c_o, L.w_o,
+                   L.w_o_t[:d], L.w_o_t[d:])
+    if ff1:
+        _dora_fold(st, _lin(blk.ff.net[0].proj)[0], st.view(bf, i, "A", 4), st.view(bf, i, "B", 4), 1, st.view(st.flat, i, "M", 4), L.c_1,
+                   L.w1, L.w1_t[:d], L.w1_t[d:])
+    if ff2:         # the transposed operand is [W2^T | A2^T]: its extension columns multiply dT2 and stay; dT2 = tg (c s B2) comes from w2_bt
+        _dora_fold(st, _lin(blk.ff.net[2])[0], st.view(bf, i, "A", 5), st.view(bf, i, "B", 5), 1, st.view(st.flat, i, "M", 5), L.c_2,
+                   L.w2, L.w2_t[:, :d], L.w2_bt)
+
+
+def _lora_db(st, tn, big, small, gB, P, c=None):
+    """dB += s big^T small (small: the saved T).  DoRA (c: the projection's factors): dB += diag(c) s big^T small -- the tn kernels have no
+    row factor, so the product goes to a zeroed scratch and vt_dora_db_add adds it scaled.  gB [n P, r]: adapter j of a fused projection
+    (qkv: n = 3) owns columns [j P, (j+1) P) of big, the extension columns from j rp of small and rows [j P, (j+1) P) of gB."""
+    out = gB if c is None else st.dora_scratch(gB.numel()).view(gB.shape)
+    for j in range(gB.shape[0] // P):
+        tn(big[:, j * P:], small[:, j * st.rp:], st.r, out[j * P:], st.r, 1, st.scaling, P)
+    if c is not None:
+        ops.dora_db_add(gB, out, c)
+
+
+def _dora_dm(st, i, j, g, y, bias, n=1):
+    """dm += (sum_m g y - b sum_m g) / m for Linear j of layer i (n = 3: the fused q | k | v projection, from one pass over g and y; only
+    the adapted ones own a magnitude); g: the gradient of the Linear's output y [M, N], y with the bias"""
+    N = g.shape[1]
+    sums = st.dora_scratch(2 * N)
+    ops.group_colsum(g, sums[:N], y=y, out2=sums[N:])
+    d = N // n
+    for k in range(n):
+        if TARGETS[j + k] in st.targets:
+            cols = slice(k * d, (k + 1) * d)
+            ops.dora_dm(sums[:N][cols], sums[N:][cols], None if bias is None else bias[cols], st.view(st.flat, i, "M", j + k),
+                        st.view(st.grad, i, "M", j + k))
 
 
 # The rank-side products of the two adapted projections of a block -- "qkv": the three adapters of the fused q | k | v projection,
@@ -302,6 +386,9 @@ def saved_bytes_per_block(model, M: int) -> int:
         cols += d + model.config.ff_mult * d + 2 * d                                  # x2 | g | ao, fo
     ff1, ff2, ef = _ff_lora(model)             # an adapted feed-forward Linear keeps its input (dA) with the K-extension (dB)
     cols += (d + ef if ff1 else 0) + (model.config.ff_mult * d + ef if ff2 else 0)
+    dora = _dora(model)
+    if dora is not None:                       # dm of to_out.0 / ff.net.2 reads the branch output before gating: ao / fo
+        cols += (d if "to_out.0" in dora.targets else 0) + (d if ff2 else 0)
     return M * cols * 2
 
 
@@ -358,7 +445,8 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
     if st is not None:
         _lora_down(st, i, "out", o, d, drop)
     h1 = E(M, d)
-    ao = E(M, d) if (save and ft is not None) else None           # branch output before gating (gate gradient)
+    dora = _dora(model)                                            # DoRA: dm of to_out.0 / ff.net.2 needs their outputs y = ao / fo too
+    ao = E(M, d) if (save and (ft is not None or (dora is not None and "to_out.0" in dora.targets))) else None    # branch output before gating (gate gradient)
     ops.gemm(o, Lw.w_o, h1, Lw.b_o, epilogue=EPI_GATED_RES, residual=h, gate_txt=m1.gate_txt, gate_vid=m1.gate_vid,
              gate_bstride=m1.bs, S=S, St=St, K=KEo, pre_act_out=ao)
     # --- feed-forward branch ---
@@ -377,12 +465,12 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
     if ff2:
         _lora_down(st, i, "ff2", gact, dff, drop)
     h2 = E(M, d)
-    fo = E(M, d) if keep_ff else None
+    fo = E(M, d) if (keep_ff or (save and dora is not None and ff2)) else None
     ops.gemm(gact, Lw.w2, h2, Lw.b2, epilogue=EPI_GATED_RES, residual=h1, gate_txt=m2.gate_txt, gate_vid=m2.gate_vid,
              gate_bstride=m2.bs, S=S, St=St, pre_act_out=fo, K=dff + ef if ff2 else None)
     if save:
         a.x1, a.qkv, a.qkh, a.o, a.lse, a.h1, a.u = x1, qkv, qkh, o, lse, h1, u
-        a.x2, a.g, a.ao, a.fo = (x2, gact, ao, fo) if ft is not None else (x2 if ff1 else None, gact if ff2 else None, None, None)
+        a.x2, a.g, a.ao, a.fo = (x2, gact, ao, fo) if ft is not None else (x2 if ff1 else None, gact if ff2 else None, ao, fo)
     return h2, a
 
 
@@ -475,12 +563,12 @@ def run_backward(model, ctx, dout: torch.Tensor):
     B, Fr, C, Hh, Ww, S, St, Sv, M = ctx.dims
     p = c.patch_size
     dev = dout.device
-    r, rp = st.r, st.rp
     eq, eo = st.ext_qkv, st.ext_o
     tn = ops.lora_tn_wide if st.wide else ops.skinny_tn       # dB products (they read the saved T: no mask): MFMA kernel above rank 16
     E = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)
     mod = ctx.mod
     drop = ctx.lora_drop          # (p, seed) of this forward's lora_dropout masks, or None
+    dora = _dora(model) is not None          # DoRA: dB takes the row factor c (_lora_db), every adapted Linear a magnitude gradient (_dora_dm)
 
     # ---- final layers ----
     dtok = E(B * Sv, c.out_channels * p * p); ops.patchify(dout, dtok, p)
@@ -520,7 +608,9 @@ def run_backward(model, ctx, dout: torch.Tensor):
         if ff2:
             # h2 = h1 + gate (x) [g | T2] [W2 | s B2]^T, g = gelu(u), T2 = (keep (x) g) A2^T / (1 - p)
             ops.gemm(tgf, Lw.w2_bt, tgf[:, d:], None, K=d)                              # dT2 = tg (s B2)
-            tn(tgf, a.g[:, dff:], r, st.view(st.grad, i, "B", 5), r, 1, st.scaling, d)   # dB2 (reads the saved T2: no mask)
+            _lora_db(st, tn, tgf, a.g[:, dff:], st.view(st.grad, i, "B", 5), d, Lw.c_2 if dora else None)   # dB2 (reads the saved T2: no mask)
+            if dora:
+                _dora_dm(st, i, 5, tgf[:, :d], a.fo, Lw.b2)
             _lora_da(st, i, "ff2", a.g, None, dff, drop, dt0=tgf[:, d:])                # dA2
             if drop is None:        # du = gelu'(u) (x) (tg W2 + dT2 A2): the correction rides in the K-extension, under the dGELU epilogue
                 ops.gemm(tgf, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u, K=d + ef)
@@ -531,14 +621,19 @@ def run_backward(model, ctx, dout: torch.Tensor):
             ops.gemm(tg, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u)
         ops.gemm(du, Lw.w1_t, dx2, None)                                  # ff.net.0.proj adapted: [M, d+ext]: dx2 | dT1
         if ff1:
-            tn(du, a.x2[:, d:], r, st.view(st.grad, i, "B", 4), r, 1, st.scaling, dff)  # dB1
+            _lora_db(st, tn, du, a.x2[:, d:], st.view(st.grad, i, "B", 4), dff, Lw.c_1 if dora else None)  # dB1
+            if dora:
+                _dora_dm(st, i, 4, du, a.u, Lw.b1)
             _lora_da(st, i, "ff1", a.x2, dx2, d, drop)                                  # dA1
             _lora_dx(st, i, "ff1", dx2, d, drop)
         ops.ln_modulate_bwd(dx2, a.h1, a.mean2, a.rstd2, Lw.n2g, (m2.scale_txt, m2.scale_vid, m2.bs), dh, dh1, d, S, St)
         # --- attention branch:  h1 = h + gate_msa * (Wo' [O | T2]) ---
         ops.gate_mul(dh1, tg, m1.gate_txt, m1.gate_vid, m1.bs, d, S, St)
         ops.gemm(tg, Lw.w_o_t, dO, None)                                  # [M, d+ext_o]: dO | dT2
-        tn(tg, a.o[:, d:], r, st.b_out(st.grad, i), r, 1, st.scaling, d)            # dB_o (reads the saved T: no mask)
+        out_adapted = dora and "to_out.0" in st.targets
+        _lora_db(st, tn, tg, a.o[:, d:], st.b_out(st.grad, i), d, Lw.c_o if out_adapted else None)   # dB_o (reads the saved T: no mask)
+        if out_adapted:
+            _dora_dm(st, i, 3, tg, a.ao, Lw.b_o)
         _lora_da(st, i, "out", a.o, dO, d, drop)                                    # dA_o
         _lora_dx(st, i, "out", dO, d, drop)
         dq.zero_()
@@ -551,8 +646,10 @@ def run_backward(model, ctx, dout: torch.Tensor):
             ops.gemm(dqkv, Lw.w_qkv_t, dx1, None)                         # [M, d+ext_qkv]: dx1 | dT1
         else:
             ops.gemm(dqkv, Lw.w_qkv_t[d:], dx1[:, d:], None)              # the first block's input (frozen embeddings) needs no gradient: dT1 only
-        for j in range(3):
-            tn(dqkv[:, j * d:], a.x1[:, d + j * rp:], r, st.b_qkv(st.grad, i)[j * d:], r, 1, st.scaling, d)
+        qkv_adapted = dora and any(t in st.targets for t in TARGETS[:3])
+        _lora_db(st, tn, dqkv, a.x1[:, d:], st.b_qkv(st.grad, i), d, Lw.c_qkv if qkv_adapted else None)
+        if qkv_adapted:
+            _dora_dm(st, i, 0, dqkv, a.qkv, Lw.b_qkv, n=3)
         _lora_da(st, i, "qkv", a.x1, dx1, d, drop)
         if i > 0:
             _lora_dx(st, i, "qkv", dx1, d, drop)

@@ -6,7 +6,9 @@ videotuna/models/cogvideo_hf/cogvideo_pl.py:143-149 with configs/004_cogvideox/c
 
 State-dict keys follow peft 0.12: ``base_model.model.<path>.base_layer.weight``,
 ``base_model.model.<path>.lora_A.default.weight`` -- the reference only relies on the substring "lora"
-(cogvideo_pl.py:781-787, videotuna/utils/callbacks.py:44-46).
+(cogvideo_pl.py:781-787, videotuna/utils/callbacks.py:44-46).  ``use_dora=True`` adds one fp32 magnitude per adapted Linear,
+``base_model.model.<path>.lora_magnitude_vector.default.weight`` [out_features] (peft 0.12's DoraLinearLayer; the key is written from
+memory of that release, peft is not a dependency), which the same substring rule saves and loads.
 
 ``target_modules`` may name any of the six Linears of a block (TARGETS: the attention projections and the feed-forward pair
 ff.net.0.proj / ff.net.2), matched by peft's rule: a module is wrapped when its path equals a target or ends in "." + target.
@@ -91,9 +93,14 @@ class LoraConfig:
     init_lora_weights: bool = True
     bias: str = "none"
     task_type: Optional[str] = None
+    use_dora: bool = False           # weight-decomposed adapters: one trained magnitude per output feature (LoraState, DESIGN 3 "DoRA")
+    use_rslora: bool = False         # scaling = lora_alpha / sqrt(r) instead of lora_alpha / r
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
+        if self.use_dora and float(self.lora_dropout) > 0.0:
+            raise NotImplementedError("use_dora with lora_dropout > 0 is not supported: peft drops the input of the (c - 1) W x term as well, "
+                                      "and a dropped base product cannot ride in the extended [W | s B] operand that DoRA scales")
         if not 0.0 <= float(self.lora_dropout) < 1.0:
             raise ValueError(f"lora_dropout must be in [0, 1), got {self.lora_dropout}")
         if self.bias != "none":
@@ -112,11 +119,13 @@ class _W(nn.Module):
 
 
 class LoraLinear(nn.Module):
-    def __init__(self, base: nn.Module, a: nn.Parameter, b: nn.Parameter, scaling: float):
+    def __init__(self, base: nn.Module, a: nn.Parameter, b: nn.Parameter, scaling: float, m: Optional[nn.Parameter] = None):
         super().__init__()
         self.base_layer = base
         self.lora_A = nn.ModuleDict({"default": _W(a)})
         self.lora_B = nn.ModuleDict({"default": _W(b)})
+        if m is not None:          # use_dora: peft 0.12's DoraLinearLayer holds the magnitude as ``weight`` [out_features]
+            self.lora_magnitude_vector = nn.ModuleDict({"default": _W(m)})
         self.scaling = {"default": scaling}
         self.in_features, self.out_features = base.in_features, base.out_features
 
@@ -132,14 +141,17 @@ class LoraLinear(nn.Module):
 class LoraState:
     """Flat storage for every adapter of a DiT.  Per layer: A_qkv [3r,d] | A_o [r,d] | B_qkv [3d,r] | B_o [d,r]; behind the L attention
     slabs, only when a feed-forward Linear is targeted, per layer: A_ff1 [r,d] | B_ff1 [4d,r] (ff.net.0.proj) and / or A_ff2 [r,4d] |
-    B_ff2 [d,r] (ff.net.2) -- the attention part of the buffers is the same with and without them."""
+    B_ff2 [d,r] (ff.net.2) -- the attention part of the buffers is the same with and without them.  use_dora: behind all of these, per
+    layer, the fp32 magnitudes m_q | m_k | m_v | m_o [4d] | m_ff1 [4d] | m_ff2 [d] (the feed-forward ones only when targeted), kind "M" of
+    view(): the offsets of every A and B are the ones of a state without DoRA."""
 
     def __init__(self, model, cfg: LoraConfig):
         self.cfg = cfg
         self.r = cfg.r
         # K-extension layout (DESIGN 3): per-adapter column stride and the extension widths of the fused qkv / out operands
         self.rp, self.ext_qkv, self.ext_o, self.wide = extension_layout(cfg.r)
-        self.scaling = float(cfg.lora_alpha) / cfg.r
+        self.scaling = float(cfg.lora_alpha) / (math.sqrt(cfg.r) if cfg.use_rslora else cfg.r)
+        self.dora = bool(cfg.use_dora)
         self.p = float(cfg.lora_dropout)      # lora_dropout: > 0 selects the _drop rank-side kernels in training mode
         self.d = model.inner_dim
         self.L = model.config.num_layers
@@ -154,6 +166,11 @@ class LoraState:
         self.ff_off = {4: 0, 5: r * (d + self.dff) if self.ff1 else 0}         # offsets inside one layer's feed-forward slab
         self.ff_per_layer = r * (d + self.dff) * (int(self.ff1) + int(self.ff2))
         self.numel = self.L * (self.per_layer + self.ff_per_layer)
+        # use_dora: the magnitudes follow every A / B slab (FusedAdamW and the data-parallel all-reduce see one longer buffer)
+        self.mag_base = self.numel
+        self.mag_off = {4: 4 * d, 5: 4 * d + (self.dff if self.ff1 else 0)}
+        self.mag_per_layer = (4 * d + (self.dff if self.ff1 else 0) + (d if self.ff2 else 0)) if self.dora else 0
+        self.numel += self.L * self.mag_per_layer
         dev = model.device
         self.flat = torch.zeros(self.numel, dtype=torch.float32, device=dev)
         self.grad = torch.zeros_like(self.flat)
@@ -170,7 +187,13 @@ class LoraState:
     def ff_dims(self, j):     # (in_features, out_features) of feed-forward Linear j: 4 = ff.net.0.proj, 5 = ff.net.2
         return (self.d, self.dff) if j == 4 else (self.dff, self.d)
 
+    def mag_out(self, j):     # out_features of Linear j
+        return self.d if j < N_ATTN else self.ff_dims(j)[1]
+
     def view(self, buf, layer, kind, j):
+        if kind == "M":        # the magnitude of Linear j; j = 0..3 are adjacent: view(buf, layer, "M", 0)'s first 3d are the fused qkv's
+            o = self.mag_base + layer * self.mag_per_layer + (j * self.d if j < N_ATTN else self.mag_off[j])
+            return buf[o:o + self.mag_out(j)]
         if j >= N_ATTN:
             fin, fout = self.ff_dims(j)
             o = self.ff_base + layer * self.ff_per_layer + self.ff_off[j] + (0 if kind == "A" else self.r * fin)
@@ -195,6 +218,10 @@ class LoraState:
         o = layer * self.per_layer + 7 * self.r * self.d
         return buf[o:o + self.d * self.r].view(self.d, self.r)
 
+    def mag_qkv(self, buf, layer):    # [3d]: the magnitudes of to_q | to_k | to_v (use_dora)
+        o = self.mag_base + layer * self.mag_per_layer
+        return buf[o:o + 3 * self.d]
+
     def init(self, seed: int = 1):
         g = torch.Generator().manual_seed(seed)
         bound = 1.0 / math.sqrt(self.d)
@@ -217,6 +244,29 @@ class LoraState:
             self.flat.copy_(host.to(self.flat.device))
         self.mark_changed()
 
+    def init_magnitudes(self, model):
+        """peft's dora_init: m = ||W + s B A|| row by row.  On the device the norms come from the kernel that computes them in every later
+        refresh (ops.dora_norm), so c = m / norm is exactly 1.0f until an adapter or a magnitude changes; on a CPU model torch's fp32 norm."""
+        from . import ops
+        from .engine import _lin
+        with torch.no_grad():
+            if self.flat.is_cuda:
+                ops.cast_f32_bf16(self.flat, self.flat_bf16)
+            for layer, blk in enumerate(model.transformer_blocks):
+                a = blk.attn1
+                lins = (a.to_q, a.to_k, a.to_v, a.to_out[0], blk.ff.net[0].proj, blk.ff.net[2])
+                for j, t in enumerate(TARGETS):
+                    if t not in self.targets:
+                        continue
+                    w, m = _lin(lins[j])[0], self.view(self.flat, layer, "M", j)
+                    if self.flat.is_cuda:
+                        ops.dora_norm(w, self.view(self.flat_bf16, layer, "A", j), self.view(self.flat_bf16, layer, "B", j), 1, self.r,
+                                      self.scaling, m)
+                    else:
+                        A, Bm = self.view(self.flat, layer, "A", j), self.view(self.flat, layer, "B", j)
+                        m.copy_(torch.linalg.norm(w.float() + self.scaling * (Bm @ A), dim=1))
+        self.mark_changed()
+
     def mark_changed(self):
         from . import ops
         if self.flat.is_cuda:
@@ -227,6 +277,13 @@ class LoraState:
         """Point every adapter Parameter's .grad at its slice of the flat gradient buffer."""
         for p, (layer, kind, j) in zip(self.params, self._index):
             p.grad = self.view(self.grad, layer, kind, j)
+
+    def dora_scratch(self, n: int):
+        """a zeroed fp32 [n] scratch on the state's device (the backward pass: the unscaled dB products and the column sums of dm)"""
+        buf = getattr(self, "_scratch", None)
+        if buf is None or buf.numel() < n or buf.device != self.flat.device:
+            buf = self._scratch = torch.empty(n, dtype=torch.float32, device=self.flat.device)
+        return buf[:n].zero_()
 
     def on_module_moved(self):
         # nn.Module._apply moved / converted the Parameters individually: re-home them into one flat buffer
@@ -255,21 +312,27 @@ def inject(model, cfg: LoraConfig, seed: int = 1) -> LoraState:
                 continue
             a = nn.Parameter(st.view(st.flat, layer, "A", j), requires_grad=True)
             b = nn.Parameter(st.view(st.flat, layer, "B", j), requires_grad=True)
+            m = nn.Parameter(st.view(st.flat, layer, "M", j), requires_grad=True) if st.dora else None
             if t == "to_out.0":
                 base = blk.attn1.to_out[0]
-                blk.attn1.to_out[0] = LoraLinear(base, a, b, st.scaling)
+                blk.attn1.to_out[0] = LoraLinear(base, a, b, st.scaling, m)
             elif t == "ff.net.0.proj":
-                blk.ff.net[0].proj = LoraLinear(blk.ff.net[0].proj, a, b, st.scaling)
+                blk.ff.net[0].proj = LoraLinear(blk.ff.net[0].proj, a, b, st.scaling, m)
             elif t == "ff.net.2":
-                blk.ff.net[2] = LoraLinear(blk.ff.net[2], a, b, st.scaling)
+                blk.ff.net[2] = LoraLinear(blk.ff.net[2], a, b, st.scaling, m)
             else:
                 base = getattr(blk.attn1, t)
-                setattr(blk.attn1, t, LoraLinear(base, a, b, st.scaling))
+                setattr(blk.attn1, t, LoraLinear(base, a, b, st.scaling, m))
             st.params += [a, b]
             st._index += [(layer, "A", j), (layer, "B", j)]
+            if st.dora:
+                st.params.append(m)
+                st._index.append((layer, "M", j))
     model.lora = st
     if cfg.init_lora_weights:
         st.init(seed)
+    if st.dora:
+        st.init_magnitudes(model)
     st.attach_grads()
     return st
 

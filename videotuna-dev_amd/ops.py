@@ -803,6 +803,62 @@ def lora_up_add_wide_dgelu_drop(dx, dt, a, n_adapters: int, r: int, rp: int, u, 
           "vt_lora_up_add_wide_dgelu_drop")
 
 
+# ---- DoRA (use_dora, csrc/dora.hip): c = m / ||W + s B A|| per output feature, folded into the packed operands ----
+def dora_norm(w, a, b, n_adapters: int, r: int, scale: float, out, mag=None):
+    """out[j] = ||w[j] + scale * b[j] @ a||_2, or mag[j] / that norm when mag is given.  w bf16 [n d_out, K], a bf16 [n r, K], b bf16
+    [n d_out, r] contiguous (adapter j: rows [j d_out, (j+1) d_out) of w and b, rows [j r, (j+1) r) of a); out, mag fp32 [n d_out]."""
+    _req(w, BF16, "w", 2); _req(a, BF16, "a", 2); _req(b, BF16, "b", 2); _req(out, torch.float32, "out", 1)
+    N, K = w.shape
+    if mag is not None:
+        _req(mag, torch.float32, "mag", 1)
+    if (N % n_adapters or a.shape[0] < n_adapters * r or a.shape[1] < K or b.shape[0] != N or b.shape[1] != r or not b.is_contiguous()
+            or out.numel() < N or (mag is not None and mag.numel() < N)):
+        raise ValueError(f"dora_norm: w {tuple(w.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)}, out {tuple(out.shape)} do not fit "
+                         f"{n_adapters} adapter(s) of rank {r}")
+    check(load_library().vt_dora_norm(w.data_ptr(), w.stride(0), a.data_ptr(), a.stride(0), b.data_ptr(), n_adapters, N // n_adapters, r, K,
+                                      float(scale), _p(mag), out.data_ptr(), _stream()), "vt_dora_norm")
+
+
+def dora_scale(src, dst, c, by_col: bool = False):
+    """dst[j, k] = bf16(c[k if by_col else j] * src[j, k]), rounded once; dst may be src (2-d row-strided views of equal shape)"""
+    _req(src, BF16, "src", 2); _req(dst, BF16, "dst", 2); _req(c, torch.float32, "c", 1)
+    rows, cols = src.shape
+    if tuple(dst.shape) != (rows, cols) or c.numel() < (cols if by_col else rows):
+        raise ValueError(f"dora_scale: src {tuple(src.shape)}, dst {tuple(dst.shape)}, c {tuple(c.shape)}")
+    check(load_library().vt_dora_scale(src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0), c.data_ptr(), rows, cols, int(by_col),
+                                       _stream()), "vt_dora_scale")
+
+
+def dora_transpose_scale(src, dst, c):
+    """dst[k, j] = bf16(c[j] * src[j, k]): src [N, K], dst [K, N] (row-strided views allowed), c fp32 [N]"""
+    _req(src, BF16, "src", 2); _req(dst, BF16, "dst", 2); _req(c, torch.float32, "c", 1)
+    rows, cols = src.shape
+    if tuple(dst.shape) != (cols, rows) or c.numel() < rows:
+        raise ValueError(f"dora_transpose_scale: src {tuple(src.shape)}, dst {tuple(dst.shape)}, c {tuple(c.shape)}")
+    check(load_library().vt_dora_transpose_scale(src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0), c.data_ptr(), rows, cols,
+                                                 _stream()), "vt_dora_transpose_scale")
+
+
+def dora_db_add(g, s, c):
+    """g[j, i] += c[j] * s[j, i]: contiguous fp32 [N, r] pair, c fp32 [N]"""
+    _req(g, torch.float32, "g", 2); _req(s, torch.float32, "s", 2); _req(c, torch.float32, "c", 1)
+    if tuple(g.shape) != tuple(s.shape) or not g.is_contiguous() or not s.is_contiguous() or c.numel() < g.shape[0]:
+        raise ValueError(f"dora_db_add: g {tuple(g.shape)}, s {tuple(s.shape)}, c {tuple(c.shape)}")
+    check(load_library().vt_dora_db_add(g.data_ptr(), s.data_ptr(), c.data_ptr(), g.shape[0], g.shape[1], _stream()), "vt_dora_db_add")
+
+
+def dora_dm(sum_g, sum_gy, bias, mag, dm):
+    """dm[j] += (sum_gy[j] - bias[j] * sum_g[j]) / mag[j]; fp32 vectors of one length, bias bf16 or None"""
+    for n, t in (("sum_g", sum_g), ("sum_gy", sum_gy), ("mag", mag), ("dm", dm)):
+        _req(t, torch.float32, n, 1)
+    if bias is not None:
+        _req(bias, BF16, "bias", 1)
+    N = dm.numel()
+    if sum_g.numel() < N or sum_gy.numel() < N or mag.numel() < N or (bias is not None and bias.numel() < N):
+        raise ValueError("dora_dm: a vector is shorter than dm")
+    check(load_library().vt_dora_dm(sum_g.data_ptr(), sum_gy.data_ptr(), _p(bias), mag.data_ptr(), dm.data_ptr(), N, _stream()), "vt_dora_dm")
+
+
 # =====================================================================================================================
 # VideoCrafter2 UNet path (include/vt355.h, second half): channels-last [N, T, H, W, C] activations
 # =====================================================================================================================
