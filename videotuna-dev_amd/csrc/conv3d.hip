@@ -179,17 +179,13 @@ __global__ __launch_bounds__(256, 2) void conv3d_cl_kernel(Conv3dParams cp) {
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Producer / consumer version (the structure of gemm_pc_bf16.hip: 256 x 128 tile, waves 0..3 multiply 128 x 64 each with
-// v_mfma_f32_32x32x16_bf16, waves 4..7 only issue LDS-DMA two K-tiles ahead in a three-stage ring, persistent over the output
+// v_mfma_f32_16x16x32_bf16, waves 4..7 only issue LDS-DMA two K-tiles ahead in a three-stage ring, persistent over the output
 // tiles).  The address generation of the implicit GEMM -- decode of the output positions, per-tap validity and offsets -- runs in
 // the loader waves, which have nothing else to do, so the multipliers see an ordinary GEMM.
-#ifndef CP_MFMA16
-#define CP_MFMA16 1        // 16x16x32 MFMA body in the producer / consumer kernel (see gemm_big_bf16.hip GB_MFMA16)
-#endif
 #define CP_BM 256
 #define CP_STAGE 49152      // A 32 KiB | W 16 KiB
 #define CP_NS 3
 #define CP_PIECES 12        // LDS-DMA operations per loader wave and K-tile: 8 of A + 4 of W
-static __device__ __forceinline__ void cp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int KT, int STRIDE, int EPI>
 __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
@@ -285,10 +281,10 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
         for (int g = 0; g < total_kt; ++g) {
             if (issued > g + 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CP_PIECES) : "memory");     // K-tile g landed, g+1 may fly
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            cp_barrier();                        // (A) stage g % 3 is ready / stage (g-1) % 3 has been consumed
+            gemm_lds_barrier();                        // (A) stage g % 3 is ready / stage (g-1) % 3 has been consumed
             if ((g + 1) % nk == 0) {
 #pragma unroll 1
-                for (int i = 0; i < 17; ++i) cp_barrier();      // mirror the multipliers' epilogue barriers
+                for (int i = 0; i < 17; ++i) gemm_lds_barrier();      // mirror the multipliers' epilogue barriers
             }
             if (issued < total_kt) { issue(issued); ++issued; }
         }
@@ -297,13 +293,11 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
 
     // =================================== multiplier waves (an ordinary GEMM from here on) ===================================
     const int wm = wave & 1, wn = wave >> 1;
-    const int fr = lane & 31, fh = lane >> 5, fx = (fr >> 1) & 7;
     const int fr16 = lane & 15, fq = lane >> 4, fx16 = (fr16 >> 1) & 7;
     const int er = tid >> 5, ec = (tid & 31) * 4;
     int g = 0;
     for (int tile = slot; tile < ntiles; tile += gridDim.x) {
         const int row0 = (tile / nbn) * CP_BM, col0 = (tile % nbn) * CV_BN;
-#if CP_MFMA16
         // v_mfma_f32_16x16x32_bf16 body (gemm_pc_bf16.hip): 8 x 4 tiles of 16 x 16 per wave, two 32-deep k-steps per K-tile, reads one sub-step ahead
         f32x4 acc16[4][8];
 #pragma unroll
@@ -311,7 +305,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc16[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         for (int kt = 0; kt < nk; ++kt, ++g) {
-            cp_barrier();                    // (A) the loaders have landed stage g % 3
+            gemm_lds_barrier();                    // (A) the loaders have landed stage g % 3
             const char* As = smem + (g % CP_NS) * CP_STAGE + (wm * 128 + fr16) * 128;
             const char* Ws = smem + (g % CP_NS) * CP_STAGE + 32768 + (wn * 64 + fr16) * 128;
             bf16x8 af[2][8], wf[2][4];
@@ -348,40 +342,6 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
             mm(1, 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-#else
-        f32x16 acc[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-        for (int kt = 0; kt < nk; ++kt, ++g) {
-            cp_barrier();                    // (A) the loaders have landed stage g % 3
-            const char* As = smem + (g % CP_NS) * CP_STAGE + (wm * 128 + fr) * 128;
-            const char* Ws = smem + (g % CP_NS) * CP_STAGE + 32768 + (wn * 64 + fr) * 128;
-            bf16x8 af[2][4], wf[2][2];
-            auto frags = [&](int ks) {
-                const int coff = (((ks * 2 + fh) ^ fx) << 4);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) af[ks & 1][t] = *(const bf16x8*)(As + t * 4096 + coff);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) wf[ks & 1][t] = *(const bf16x8*)(Ws + t * 4096 + coff);
-            };
-            frags(0);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                if (ks + 1 < 4) frags(ks + 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < 2; ++tn)
-                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks & 1][tn], af[ks & 1][tm], acc[tn][tm], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#endif
         // ---------------- epilogue: eight 32-row slabs through the stage that was just consumed (17 barriers) ----------------
         float* Cs = (float*)(smem + ((g - 1) % CP_NS) * CP_STAGE);
         const int n = col0 + ec;
@@ -390,27 +350,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) bias4[j] = bf2f(p.bias[n + j]);
         }
-        cp_barrier();
+        gemm_lds_barrier();
 #pragma unroll
         for (int slab = 0; slab < 8; ++slab) {
             if (wm == (slab >> 2)) {
-#if CP_MFMA16
 #pragma unroll
                 for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
                     for (int tn = 0; tn < 4; ++tn)
                         *(f32x4*)(Cs + (t2 * 16 + fr16) * CV_CS_LD + wn * 64 + tn * 16 + 4 * fq) = acc16[tn][(slab & 3) * 2 + t2];
-#else
-                const int tm = slab & 3;
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        *(f32x4*)(Cs + fr * CV_CS_LD + wn * 64 + tn * 32 + 8 * q + 4 * fh) =
-                            (f32x4){acc[tn][tm][4 * q], acc[tn][tm][4 * q + 1], acc[tn][tm][4 * q + 2], acc[tn][tm][4 * q + 3]};
-#endif
             }
-            cp_barrier();
+            gemm_lds_barrier();
 #pragma unroll
             for (int pass = 0; pass < 4; ++pass) {
                 const int ml = pass * 8 + er;
@@ -420,7 +370,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
                     gemm_epilogue_store<EPI, false>(p, m, n, v, bias4);
                 }
             }
-            cp_barrier();
+            gemm_lds_barrier();
         }
     }
 }

@@ -5,26 +5,13 @@
 // backward dX = dY * W.  Reference ops replaced: every nn.Linear of diffusers' CogVideoXBlock that
 // the reference reaches through videotuna/models/cogvideo_hf/cogvideo_pl.py:865-871 (SURVEY 8(a) a4,a5).
 //
-// Structure (v1): 128x128x64 workgroup tile, 4 waves (2x2), each wave 64x64 = 4x4 tiles of
-// v_mfma_f32_16x16x32_bf16.  Operands are staged global -> VGPR -> LDS (XOR-swizzled 16-byte chunks,
+// Structure: 128x128x64 workgroup tile, 4 waves (2x2), each wave 64x64 = 4x4 tiles of
+// v_mfma_f32_16x16x32_bf16.  Operands are staged by LDS-DMA (buffer_load ... lds; XOR-swizzled 16-byte chunks,
 // conflict-free ds_read_b128), double-buffered so the loads of K-tile t+1 are in flight while tile t
-// is multiplied (issue-early / write-late).  Global loads are bounds-checked raw buffer loads, so
-// ragged M / N edges read zeros.  The MFMA is issued as (W-frag, A-frag) so each lane ends up with 4
+// is multiplied.  Global loads are bounds-checked raw buffer loads, so ragged M / N edges read zeros.  The MFMA is issued as (W-frag, A-frag) so each lane ends up with 4
 // consecutive output columns of one row; the accumulators go through LDS once so the epilogue reads
 // residual / writes C in row-contiguous, fully coalesced 128-B segments.
 #include "gemm_epilogue.h"
-
-// variant hooks (tools/build_variants.sh); the shipped build defines none of these
-#ifndef VT_SUFFIX
-#define VT_SUFFIX
-#endif
-#ifndef VT_GEMM_DMA
-#define VT_GEMM_DMA 1      // 1 = operands staged by LDS-DMA (buffer_load ... lds), 0 = global -> VGPR -> ds_write_b128
-#endif
-#define VT_CAT_(a, b) a##b
-#define VT_CAT(a, b) VT_CAT_(a, b)
-#define GEMM_KERNEL VT_CAT(gemm_tn_kernel, VT_SUFFIX)
-#define GEMM_ENTRY VT_CAT(vt_gemm_bf16, VT_SUFFIX)
 
 #define BM 128
 #define BN 128
@@ -32,7 +19,7 @@
 #define CS_LD 132   // fp32 row stride of the epilogue staging tile (64 rows x 132 floats = 33 KiB)
 
 template <int EPI, bool OUT_F32>
-__global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[65536];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave & 1, wn = wave >> 1;
@@ -54,7 +41,6 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
     __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A + (size_t)row0 * p.lda, (unsigned)(a_rem > 0x7fffffffLL ? 0x7fffffffLL : a_rem));
     __amdgpu_buffer_rsrc_t rw = make_rsrc(p.W + (size_t)col0 * p.ldw, (unsigned)(w_rem > 0x7fffffffLL ? 0x7fffffffLL : w_rem));
 
-#if VT_GEMM_DMA
     // ---- LDS-DMA staging: a K-tile of A (and of W) is 16 blocks of 1 KiB = 8 rows x 128 B; wave w moves blocks
     // w, w+4, w+8, w+12 of each operand.  One buffer_load..lds writes lane l at block + 16 l = (row l>>3, physical
     // chunk l&7), so the XOR swizzle is applied to the SOURCE chunk; out-of-range rows read zeros (bounds check).
@@ -76,35 +62,6 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + 16384), 16, w_voff[j], soff, 0, 0);
         }
     };
-#else
-    // staging assignment: 4 x 16-byte chunks of A and of W per thread per K-tile
-    int a_voff[4], w_voff[4], lds_off[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        int i = tid + 256 * j;
-        int r = i >> 3, c = i & 7;
-        a_voff[j] = r * p.lda * 2 + c * 16;
-        w_voff[j] = r * p.ldw * 2 + c * 16;
-        lds_off[j] = r * 128 + ((c ^ (r & 7)) << 4);
-    }
-    u32x4 ga[4], gw[4];
-    auto gload = [&](int kt) {
-        const int soff = kt * BK * 2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ga[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, a_voff[j], soff, 0));
-            gw[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, w_voff[j], soff, 0));
-        }
-    };
-    auto lstore = [&](int buf) {
-        char* base = smem + buf * 32768;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            *(u32x4*)(base + lds_off[j]) = ga[j];
-            *(u32x4*)(base + 16384 + lds_off[j]) = gw[j];
-        }
-    };
-#endif
 
     f32x4 acc[4][4];   // [tn][tm]
 #pragma unroll
@@ -113,23 +70,14 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     const int nk = p.K / BK;
-#if VT_GEMM_DMA
     dma(0, 0);
-#else
-    gload(0);
-    lstore(0);
-#endif
     __syncthreads();
     const int frow = lane & 15;            // row inside a 16-row fragment
     const int fq = lane >> 4;              // k-chunk inside a 32-deep k-step
     const int fx = lane & 7;               // == (row & 7) for every fragment row this lane reads
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
-#if VT_GEMM_DMA
         if (kt + 1 < nk) dma(kt + 1, buf ^ 1);
-#else
-        if (kt + 1 < nk) gload(kt + 1);
-#endif
         const char* As = smem + buf * 32768;
         const char* Ws = As + 16384;
 #pragma unroll
@@ -147,10 +95,7 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
                 for (int tm = 0; tm < 4; ++tm)
                     acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[tn], af[tm], acc[tn][tm], 0, 0, 0);
         }
-#if !VT_GEMM_DMA
-        if (kt + 1 < nk) lstore(buf ^ 1);
-#endif
-        __syncthreads();       // (DMA build: the barrier's vmcnt(0) also retires the next tile's LDS-DMA)
+        __syncthreads();       // the barrier's vmcnt(0) also retires the next tile's LDS-DMA
     }
 
     // ---------------- epilogue: two 64-row halves through LDS ----------------
@@ -190,21 +135,21 @@ __global__ __launch_bounds__(256, 2) void GEMM_KERNEL(GemmParams p) {
 }
 
 template <int EPI, bool F32>
-static int VT_CAT(launch, VT_SUFFIX)(const GemmParams& p, hipStream_t st) {
+static int launch(const GemmParams& p, hipStream_t st) {
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    hipLaunchKernelGGL((GEMM_KERNEL<EPI, F32>), dim3(nbm * nbn), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((gemm_tn_kernel<EPI, F32>), dim3(nbm * nbn), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
-static bool VT_CAT(al16, VT_SUFFIX)(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // 256x256-tile kernel (gemm_big_bf16.hip) for the token-sized problems; 0 = choose by shape, 1 = always 128x128, 2 = always 256x256
-int VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st);
-int VT_CAT(vt_gemm_pc_dispatch, VT_SUFFIX)(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st);     // gemm_pc_bf16.hip
-static int VT_CAT(g_gemm_tile, VT_SUFFIX) = 0;
-extern "C" int VT_CAT(vt_gemm_set_tile, VT_SUFFIX)(int mode) {
+int vt_gemm_big_dispatch(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st);
+int vt_gemm_pc_dispatch(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st);     // gemm_pc_bf16.hip
+static int g_gemm_tile = 0;
+extern "C" int vt_gemm_set_tile(int mode) {
     if (mode < 0 || mode > 3) return VT_ERR_BAD_SHAPE;
-    VT_CAT(g_gemm_tile, VT_SUFFIX) = mode;
+    g_gemm_tile = mode;
     return VT_OK;
 }
 // which tiling: 1 = 128x128 (this file), 2 = 256x256 (gemm_big_bf16.hip), 3 = 256x128 producer/consumer (gemm_pc_bf16.hip).
@@ -215,8 +160,8 @@ extern "C" int VT_CAT(vt_gemm_set_tile, VT_SUFFIX)(int mode) {
 //            N=1984 K=5760  938 / 1042 / 1085 | N=1920 K=1984 957 /  913 /  975 | N=1984 K=1920 931 /  961 /  983
 //   M=17776: N=5760 1015 / 1034 / 1043 | N=7680 968 / 1061 / 1024 | N=1920 K=7680 918 / 875 / 1018 | N=1984 K=5760 951 / 917 / 996
 //            N=1920 K=1984 901 / 825 / 907        8192^3: 1050 / 1236 / 1211
-static int VT_CAT(pick_tile, VT_SUFFIX)(int M, int N, int K) {
-    const int mode = VT_CAT(g_gemm_tile, VT_SUFFIX);
+static int pick_tile(int M, int N, int K) {
+    const int mode = g_gemm_tile;
     if (mode) return mode;
     const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256);
     const long long tpc = (long long)((M + 255) / 256) * ((N + 127) / 128);
@@ -239,24 +184,24 @@ static int VT_CAT(pick_tile, VT_SUFFIX)(int M, int N, int K) {
     return 1;
 }
 
-int VT_CAT(vt_gemm_pc_bm, VT_SUFFIX)(int M);     // gemm_pc_bf16.hip
+int vt_gemm_pc_bm(int M);     // gemm_pc_bf16.hip
 // which kernel vt_gemm_bf16 launches for an (M, N, K) problem under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128
 // producer / consumer, 4 = the producer / consumer kernel's 128-row instantiation.  The three kernels sum the same MFMA products in the
 // same K order, so their outputs are bit-identical and cannot tell which one ran (tests: dispatch coverage of the production shapes)
-extern "C" int VT_CAT(vt_gemm_bf16_kernel, VT_SUFFIX)(int M, int N, int K) {
+extern "C" int vt_gemm_bf16_kernel(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return VT_ERR_BAD_SHAPE;
-    const int tile = VT_CAT(pick_tile, VT_SUFFIX)(M, N, K);
-    return tile == 3 && VT_CAT(vt_gemm_pc_bm, VT_SUFFIX)(M) == 128 ? 4 : tile;
+    const int tile = pick_tile(M, N, K);
+    return tile == 3 && vt_gemm_pc_bm(M) == 128 ? 4 : tile;
 }
 
-extern "C" int GEMM_ENTRY(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+extern "C" int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
                             int M, int N, int K, const void* bias, int epilogue, int out_fp32,
                             const void* R, int ldr, int r_mod,
                             const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St,
                             void* C2, int ldc2, const void* U, int ldu, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || (N % 4) != 0) return VT_ERR_BAD_SHAPE;
     if ((lda % 8) || (ldw % 8) || (ldc % 4) || lda < K || ldw < K || ldc < N) return VT_ERR_BAD_SHAPE;
-    if (!VT_CAT(al16, VT_SUFFIX)(A) || !VT_CAT(al16, VT_SUFFIX)(W) || !VT_CAT(al16, VT_SUFFIX)(C)) return VT_ERR_BAD_ALIGN;
+    if (!al16(A) || !al16(W) || !al16(C)) return VT_ERR_BAD_ALIGN;
     GemmParams p;
     p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C; p.bias = (const bf16_t*)bias;
     p.R = (const bf16_t*)R; p.gate_txt = gate_txt; p.gate_vid = gate_vid;
@@ -264,33 +209,33 @@ extern "C" int GEMM_ENTRY(const void* A, int lda, const void* W, int ldw, void* 
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldc2 = ldc2; p.ldu = ldu;
     p.S = S > 0 ? S : 1; p.St = St; p.gate_bstride = gate_bstride; p.r_mod = r_mod; p.splits = 1;
     hipStream_t st = (hipStream_t)stream;
-    const int tile = VT_CAT(pick_tile, VT_SUFFIX)(M, N, K);
+    const int tile = pick_tile(M, N, K);
     const bool big = tile == 2;
     if (tile == 3) {                                     // producer / consumer kernel (256x128 tile)
-        if (epilogue == EPI_BIAS_GELU && (out_fp32 || C2 == nullptr || (ldc2 % 4) || !VT_CAT(al16, VT_SUFFIX)(C2))) return VT_ERR_BAD_SHAPE;
-        if (epilogue == EPI_GATED_RES && (out_fp32 || R == nullptr || (ldr % 4) || !VT_CAT(al16, VT_SUFFIX)(R))) return VT_ERR_BAD_SHAPE;
-        if (epilogue == EPI_DGELU && (out_fp32 || U == nullptr || (ldu % 4) || !VT_CAT(al16, VT_SUFFIX)(U))) return VT_ERR_BAD_SHAPE;
-        return VT_CAT(vt_gemm_pc_dispatch, VT_SUFFIX)(p, epilogue, out_fp32, st);
+        if (epilogue == EPI_BIAS_GELU && (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al16(C2))) return VT_ERR_BAD_SHAPE;
+        if (epilogue == EPI_GATED_RES && (out_fp32 || R == nullptr || (ldr % 4) || !al16(R))) return VT_ERR_BAD_SHAPE;
+        if (epilogue == EPI_DGELU && (out_fp32 || U == nullptr || (ldu % 4) || !al16(U))) return VT_ERR_BAD_SHAPE;
+        return vt_gemm_pc_dispatch(p, epilogue, out_fp32, st);
     }
     switch (epilogue) {
         case EPI_BIAS:
-            if (big) return VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(p, epilogue, out_fp32, st);
-            return out_fp32 ? VT_CAT(launch, VT_SUFFIX)<EPI_BIAS, true>(p, st) : VT_CAT(launch, VT_SUFFIX)<EPI_BIAS, false>(p, st);
+            if (big) return vt_gemm_big_dispatch(p, epilogue, out_fp32, st);
+            return out_fp32 ? launch<EPI_BIAS, true>(p, st) : launch<EPI_BIAS, false>(p, st);
         case EPI_BIAS_GELU:
-            if (out_fp32 || C2 == nullptr || (ldc2 % 4) || !VT_CAT(al16, VT_SUFFIX)(C2)) return VT_ERR_BAD_SHAPE;
-            if (big) return VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(p, epilogue, 0, st);
-            return VT_CAT(launch, VT_SUFFIX)<EPI_BIAS_GELU, false>(p, st);
+            if (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al16(C2)) return VT_ERR_BAD_SHAPE;
+            if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
+            return launch<EPI_BIAS_GELU, false>(p, st);
         case EPI_GATED_RES:
-            if (out_fp32 || R == nullptr || (ldr % 4) || !VT_CAT(al16, VT_SUFFIX)(R)) return VT_ERR_BAD_SHAPE;
-            if (C2 != nullptr && ((ldc2 % 4) || !VT_CAT(al16, VT_SUFFIX)(C2))) return VT_ERR_BAD_SHAPE;
-            if (gate_vid != nullptr && (gate_txt == nullptr || (gate_bstride % 4) || !VT_CAT(al16, VT_SUFFIX)(gate_vid) || !VT_CAT(al16, VT_SUFFIX)(gate_txt)))
+            if (out_fp32 || R == nullptr || (ldr % 4) || !al16(R)) return VT_ERR_BAD_SHAPE;
+            if (C2 != nullptr && ((ldc2 % 4) || !al16(C2))) return VT_ERR_BAD_SHAPE;
+            if (gate_vid != nullptr && (gate_txt == nullptr || (gate_bstride % 4) || !al16(gate_vid) || !al16(gate_txt)))
                 return VT_ERR_BAD_SHAPE;
-            if (big) return VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(p, epilogue, 0, st);
-            return VT_CAT(launch, VT_SUFFIX)<EPI_GATED_RES, false>(p, st);
+            if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
+            return launch<EPI_GATED_RES, false>(p, st);
         case EPI_DGELU:
-            if (out_fp32 || U == nullptr || (ldu % 4) || !VT_CAT(al16, VT_SUFFIX)(U)) return VT_ERR_BAD_SHAPE;
-            if (big) return VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(p, epilogue, 0, st);
-            return VT_CAT(launch, VT_SUFFIX)<EPI_DGELU, false>(p, st);
+            if (out_fp32 || U == nullptr || (ldu % 4) || !al16(U)) return VT_ERR_BAD_SHAPE;
+            if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
+            return launch<EPI_DGELU, false>(p, st);
         default:
             return VT_ERR_UNSUPPORTED;
     }

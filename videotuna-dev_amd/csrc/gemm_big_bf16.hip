@@ -6,90 +6,30 @@
 // Why a second tiling: a wave that owns a 64x64 output tile reads (64+64) x 64 bf16 = 16 KiB of LDS per 64-deep
 // K-tile for 512 Ki flop -- 32 flop per LDS byte, exactly the ratio of the CU's MFMA rate (4096 flop/clk) to its LDS
 // bandwidth (128 B/clk), so the 128x128 kernel can never run the matrix cores above ~50 %.  Here the workgroup tile is
-// 256x256x64 with 8 waves (2 x 4), each wave owning 128x64 = 4x2 tiles of v_mfma_f32_32x32x16_bf16 (128 accumulator
+// 256x256x64 with 8 waves (2 x 4), each wave owning 128x64 = 8x4 tiles of v_mfma_f32_16x16x32_bf16 (128 accumulator
 // registers, two waves per SIMD): 24 KiB of LDS reads per wave per K-tile for 1 Mi flop -> the LDS pipe is ~75 % busy
 // at full MFMA rate.  Operands are staged by LDS-DMA (buffer_load ... lds, XOR swizzle applied to the source chunk),
 // double-buffered (2 x 64 KiB); the accumulators leave through LDS in eight 32-row slabs so that the epilogue reads
 // residuals / writes C in row-contiguous 512-B segments.
 #include "gemm_epilogue.h"
 
-#ifndef VT_SUFFIX
-#define VT_SUFFIX
-#endif
-#define VT_CAT_(a, b) a##b
-#define VT_CAT(a, b) VT_CAT_(a, b)
-#define GEMM_BIG_KERNEL VT_CAT(gemm_tn_big_kernel, VT_SUFFIX)
-#define GEMM_BIG_ENTRY VT_CAT(vt_gemm_bf16_big, VT_SUFFIX)
-
 #define GB_BM 256
 #define GB_BN 256
 #define GB_BK 64
 #define GB_STAGE 65536      // A 32 KiB | W 32 KiB
-#ifndef GB_LOADERS
-#define GB_LOADERS 0        // 1 = four extra waves (one per SIMD) do nothing but issue the LDS-DMA pieces: an LDS-DMA piece costs its
-#endif                      // issuing wave 100-185 cycles inside an MFMA phase (8 per K-tile per wave = as much as the MFMAs themselves).
-                            // NOT usable as written: three waves per SIMD cap a wave at 168 registers and the 128 accumulators + two
-                            // fragment sets spill (816 dwords)
-#ifndef GB_STAGGER
-#define GB_STAGGER 1         // 1: waves 4..7 issue their LDS-DMA pieces in the middle of the K-tile, waves 0..3 at its start: the two waves
-#endif                      // of a SIMD are then never both busy issuing DMA (the issue cost of one hides under the MFMAs of the other): +2-5 %.
-                            // 2: one piece per k-step, interleaved with the MFMAs -- measured 10 % SLOWER than 1.
-                            // Ablations (wrong results, timing only; M=35552 N=5760 K=1984): no operand traffic after the first
-                            // K-tile 1404 TF/s, no barrier 1092, neither 1484, shipped 1032 -- staging, not the MFMA loop, is the limit
-#ifndef GB_MFMA16
-#define GB_MFMA16 1          // 1: the products are issued as v_mfma_f32_16x16x32_bf16 (8 x 4 tiles of 16 x 16 per wave, two 32-deep k-steps per
-#endif                      // K-tile) instead of v_mfma_f32_32x32x16_bf16 (4 x 2 tiles, four 16-deep k-steps): same LDS image, same LDS bytes per
-                            // flop, same cycles per flop -- but the chip holds a higher clock on the 16x16x32 shape under load
-                            // (MI355X_MICROARCH.md, DVFS item 7).  0 = the 32x32x16 body.
-#ifndef GB_W4
-#define GB_W4 0              // 1 (experiment): FOUR waves, one per SIMD, each owning 128 x 128 = 8 x 8 tiles of 16 x 16 (256 accumulator registers, the
-#endif                      // layout of the vendor library's 256 x 256 x 64 kernel): 16 KiB of LDS reads per wave per 32-deep k-step for 64 MFMAs
-                            // instead of 12 KiB for 32 -- a third fewer LDS bytes per flop; every wave issues 8 + 8 LDS-DMA pieces per K-tile itself,
-                            // one pair per 16 MFMAs.  Needs GB_MFMA16, no GB_LOADERS.  Compiles to 256 AGPRs + 88 VGPRs, no scratch; results equal.
-                            // Measured (r03, tools/kbench_gemm_w4.py, profiles/r03_gemm_w4_experiment.txt): 10-13 % SLOWER than the eight-wave body
-                            // on every block shape (e.g. 71104 x 7680 x 1920: 1064 vs 1194 TFLOP/s; 10456 x 21504 x 3072: 1116 vs 1262) -- with one
-                            // wave per SIMD nothing covers the LDS round trip after each K-tile barrier and the DMA issue slots.  The vendor
-                            // library's kernel of this shape (hand-scheduled, 1234 TFLOP/s on ff1) is at parity with the eight-wave body.
-#define GB_THREADS (GB_LOADERS ? 768 : (GB_W4 ? 256 : 512))
-#define GB_TN (GB_W4 ? 8 : 4)            // 16-column tiles per wave
-#define GB_EROWS (GB_W4 ? 4 : 8)         // rows one epilogue pass of the workgroup covers
-#define GB_EPASS (32 / GB_EROWS)
 #define GB_CS_LD 260        // fp32 row stride of the epilogue staging slab (32 rows x 260 floats = 32.5 KiB)
+// The products are issued as v_mfma_f32_16x16x32_bf16 (two 32-deep k-steps per K-tile), not as 4 x 2 tiles of v_mfma_f32_32x32x16_bf16:
+// same LDS image, same LDS bytes per flop, same cycles per flop -- but the chip holds a higher clock on the 16x16x32 shape under load
+// (MI355X_MICROARCH.md, DVFS item 7).
+// Staggered staging: waves 0..3 issue their LDS-DMA pieces at the start of a K-tile, waves 4..7 in its middle, so the two waves of a SIMD
+// are never both busy issuing DMA (the issue cost of one hides under the MFMAs of the other): +2-5 %.  The variants that were measured
+// against this body (four waves, loader waves, one piece per k-step, the 32x32x16 body, the timing ablations) are in csrc/exp/README.md.
 
 typedef int gb_i32x4 __attribute__((ext_vector_type(4)));
 
-// workgroup barrier that only orders LDS traffic (s_waitcnt lgkmcnt(0)); __syncthreads() would also drain vmcnt
-__device__ __forceinline__ void gb_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-struct GbTile {
-    int row0, col0;
-    const bf16_t* a;        // first row of the tile in A / W; the descriptors are bounded by the rest of the matrix
-    const bf16_t* w;
-    unsigned a_bytes, w_bytes;
-};
 __device__ __forceinline__ gb_i32x4 gb_words(const void* base, unsigned bytes) {     // raw descriptor words (inline-asm operand)
     const unsigned long long a = (unsigned long long)base;
     return (gb_i32x4){(int)(unsigned)a, (int)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-
-__device__ __forceinline__ GbTile gb_tile(const GemmParams& p, int id, int nbm, int nbn) {
-    // grouped ordering (4 row-tiles per group, column-tiles outer): the 32 workgroups of an XCD that run together share
-    // A row-panels / W column-panels in its L2
-    const int GM = 4;
-    const int in_group = GM * nbn;
-    const int group = id / in_group;
-    const int first_m = group * GM;
-    const int gsz = min(nbm - first_m, GM);
-    GbTile t;
-    t.row0 = (first_m + (id % in_group) % gsz) * GB_BM;
-    t.col0 = ((id % in_group) / gsz) * GB_BN;
-    const long long a_rem = (long long)(p.M - t.row0) * p.lda * 2;
-    const long long w_rem = (long long)(p.N - t.col0) * p.ldw * 2;
-    t.a = p.A + (size_t)t.row0 * p.lda;
-    t.w = p.W + (size_t)t.col0 * p.ldw;
-    t.a_bytes = (unsigned)(a_rem > 0x7fffffffLL ? 0x7fffffffLL : a_rem);
-    t.w_bytes = (unsigned)(w_rem > 0x7fffffffLL ? 0x7fffffffLL : w_rem);
-    return t;
 }
 
 // PERSISTENT: one workgroup per CU (128 KiB of LDS), slot = (XCD, index inside the XCD) under round-robin dispatch;
@@ -97,11 +37,11 @@ __device__ __forceinline__ GbTile gb_tile(const GemmParams& p, int id, int nbm, 
 // K-tile of the current one is multiplied and its epilogue runs, so neither a workgroup launch nor the first HBM round
 // trip of a tile is exposed.
 template <int EPI, bool OUT_F32>
-__global__ __launch_bounds__(GB_THREADS, 1) void GEMM_BIG_KERNEL(GemmParams p) {
+__global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * GB_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;                  // 2 x 4 waves: rows 128 wm .., columns 64 wn ..  (GB_W4: 2 x 2, columns 128 wn ..)
+    const int wm = wave & 1, wn = wave >> 1;                  // 2 x 4 waves: rows 128 wm .., columns 64 wn ..
     const int nbm = (p.M + GB_BM - 1) / GB_BM, nbn = (p.N + GB_BN - 1) / GB_BN;
     const int ntiles = nbm * nbn;
     const int spx = gridDim.x >> 3;
@@ -116,28 +56,20 @@ __global__ __launch_bounds__(GB_THREADS, 1) void GEMM_BIG_KERNEL(GemmParams p) {
     // period) and the same physical chunk, and (row >> 1) & 7 is distinct over the 8 same-parity rows of every group.
     // (row & 7, the 16-row-fragment swizzle of gemm_bf16.hip, gave 47 % conflict cycles here: rows 12 and 20 collide.)
     const int drl = lane >> 3, dcp = lane & 7;
-#if GB_LOADERS
-    const bool loader = wave >= 8;                 // waves 8..11: one per SIMD, 8 pieces of A and 8 of W per K-tile each
-    constexpr int NP = 8, PSTRIDE = 4;
-    const int pw = wave & 3;
-#else
-    constexpr bool loader = true;                  // every wave moves 4 (GB_W4: 8) pieces of A and of W per K-tile itself
-    constexpr int NP = GB_W4 ? 8 : 4, PSTRIDE = GB_W4 ? 4 : 8;
-    const int pw = wave;
-#endif
-    // piece j of this wave is block pw + PSTRIDE j = rows 8 (pw + PSTRIDE j) + drl: swz(row) does not depend on j (8 PSTRIDE j / 2
-    // is a multiple of 8), so one per-lane offset serves all pieces and the row step goes into the scalar offset
-    const int row0p = 8 * pw + drl;
+    // every wave moves 4 pieces of A and of W per K-tile itself: piece j of this wave is block wave + 8 j = rows 8 (wave + 8 j) + drl:
+    // swz(row) does not depend on j (8 * 8 j / 2 is a multiple of 8), so one per-lane offset serves all pieces and the row step goes into
+    // the scalar offset
+    const int row0p = 8 * wave + drl;
     const int sw = (row0p >> 1) & 7;
     const int a_voff0 = row0p * p.lda * 2 + ((dcp ^ sw) << 4);
     const int w_voff0 = row0p * p.ldw * 2 + ((dcp ^ sw) << 4);
-    const int a_pstep = 8 * PSTRIDE * p.lda * 2, w_pstep = 8 * PSTRIDE * p.ldw * 2;
-    auto dma = [&](const GbTile& t, int kt, int buf, int j0 = 0, int j1 = NP) {
+    const int a_pstep = 64 * p.lda * 2, w_pstep = 64 * p.ldw * 2;
+    auto dma = [&](const GemmTile& t, int kt, int buf) {
         const int soff = kt * GB_BK * 2;
         __amdgpu_buffer_rsrc_t ra = make_rsrc(t.a, t.a_bytes), rw = make_rsrc(t.w, t.w_bytes);
 #pragma unroll
-        for (int j = j0; j < j1; ++j) {
-            char* dst = smem + buf * GB_STAGE + (pw + PSTRIDE * j) * 1024;
+        for (int j = 0; j < 4; ++j) {
+            char* dst = smem + buf * GB_STAGE + (wave + 8 * j) * 1024;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void*)dst, 16, a_voff0, soff + j * a_pstep, 0, 0);
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (__attribute__((address_space(3))) void*)(dst + 32768), 16, w_voff0, soff + j * w_pstep, 0, 0);
         }
@@ -146,122 +78,67 @@ __global__ __launch_bounds__(GB_THREADS, 1) void GEMM_BIG_KERNEL(GemmParams p) {
     // an LDS-DMA it knows about, which would park the whole epilogue behind the fetch.  Safe: it is older than every memory
     // operation of the epilogue (vmcnt retires in order, so each wait the compiler computes there also covers it), and the
     // next tile starts with a full barrier (vmcnt(0)).
-    auto dma_hidden = [&](const GbTile& t, int buf, int j0 = 0, int j1 = NP) {
+    auto dma_hidden = [&](const GemmTile& t, int buf) {
         const gb_i32x4 ra = gb_words(t.a, t.a_bytes), rw = gb_words(t.w, t.w_bytes);
 #pragma unroll
-        for (int j = j0; j < j1; ++j) {
-            const unsigned dst = smem_lds + buf * GB_STAGE + (pw + PSTRIDE * j) * 1024;
+        for (int j = 0; j < 4; ++j) {
+            const unsigned dst = smem_lds + buf * GB_STAGE + (wave + 8 * j) * 1024;
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(dst), "v"(a_voff0), "s"(ra), "s"(j * a_pstep) : "memory");
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(dst + 32768), "v"(w_voff0), "s"(rw), "s"(j * w_pstep) : "memory");
         }
     };
 
     const int nk = p.K / GB_BK;
-    const int fr = lane & 31;             // row inside a 32-row fragment
-    const int fh = lane >> 5;             // which 8-element half of a 16-deep k-step
-    const int fx = (fr >> 1) & 7;         // swz(row) of every fragment row this lane reads (tile rows are 32-aligned)
-    const int fr16 = lane & 15, fq = lane >> 4, fx16 = (fr16 >> 1) & 7;   // the same for 16-row fragments (GB_MFMA16)
+    const int fr16 = lane & 15, fq = lane >> 4, fx16 = (fr16 >> 1) & 7;   // 16-row fragments: row, k-chunk of a 32-deep k-step, swz(row)
     const int er = tid >> 6;              // epilogue: 0..7, row inside an 8-row pass
     const int ec = (tid & 63) * 4;        // epilogue: first of this thread's 4 columns
 
     if (slot >= ntiles) return;
-    GbTile cur = gb_tile(p, slot, nbm, nbn);
+    GemmTile cur = gemm_tile<GB_BM, GB_BN>(p, slot, nbm, nbn);
     int buf = 0;
-    if (loader) dma(cur, 0, 0);
+    dma(cur, 0, 0);
     for (int tile = slot; tile < ntiles; tile += gridDim.x) {
         const bool has_next = tile + (int)gridDim.x < ntiles;
-        GbTile nxt = cur;
-        if (has_next) nxt = gb_tile(p, tile + gridDim.x, nbm, nbn);
+        GemmTile nxt = cur;
+        if (has_next) nxt = gemm_tile<GB_BM, GB_BN>(p, tile + gridDim.x, nbm, nbn);
 
-        // acc[tn][tm] = D[n][m] of (W-fragment, A-fragment): lane holds m = lane & 31 and, in register r, column
-        // n = 8 (r>>2) + 4 (lane>>5) + (r&3): four consecutive output columns per register quad
-#if GB_MFMA16
         // acc16[tn][tm] = D[n][m] of a 16 x 16 tile: lane holds m = lane & 15 and the four consecutive columns n = 4 (lane >> 4) + r
-        f32x4 acc16[GB_TN][8];
+        f32x4 acc16[4][8];
 #pragma unroll
-        for (int i = 0; i < GB_TN; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc16[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#else
-        f32x16 acc[2][4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-#endif
 
         __syncthreads();                  // vmcnt(0): the first K-tile (fetched during the previous tile) has landed
         for (int kt = 0; kt < nk; ++kt) {
             const bool last = kt + 1 == nk;
-            // GB_STAGGER 2: one piece of A and one of W per k-step; waves 0..3 issue theirs before the k-step's MFMAs, waves
-            // 4..7 (the other wave of each SIMD) half-way through them, so a SIMD never has both of its waves blocked on DMA issue
-            auto issue = [&](int j0, int j1) {
-#ifndef GB_ABL_NODMA      // timing-only ablation: no operand traffic after the first K-tile (results wrong)
-                if (loader) {
-                    if (!last) dma(cur, kt + 1, buf ^ 1, j0, j1);
-                    else if (has_next) dma_hidden(nxt, buf ^ 1, j0, j1);
-                }
-#endif
+            auto issue = [&]() {                // the next K-tile, or the first one of the next output tile
+                if (!last) dma(cur, kt + 1, buf ^ 1);
+                else if (has_next) dma_hidden(nxt, buf ^ 1);
             };
-            const bool late = GB_STAGGER && !GB_LOADERS && !GB_W4 && wave >= 4;
-            if (GB_STAGGER < 2 && !late && !GB_W4) issue(0, NP);
-#if GB_LOADERS
-            if (!loader)
-#endif
-            {
-#if GB_MFMA16
-                // 16-row fragments: lane reads row (lane & 15), logical chunk 4 ks + (lane >> 4) of the 8 chunks of a 64-deep row; swz(row) =
-                // (row >> 1) & 7 only depends on lane & 15 (tiles are 16-aligned) and the ds_read_b128 lane groups stay conflict-free
-                const char* As = smem + buf * GB_STAGE + (wm * 128 + fr16) * 128;
-                const char* Ws = smem + buf * GB_STAGE + 32768 + (wn * (16 * GB_TN) + fr16) * 128;
+            const bool late = wave >= 4;
+            if (!late) issue();
+            // 16-row fragments: lane reads row (lane & 15), logical chunk 4 ks + (lane >> 4) of the 8 chunks of a 64-deep row; swz(row) =
+            // (row >> 1) & 7 only depends on lane & 15 (tiles are 16-aligned) and the ds_read_b128 lane groups stay conflict-free
+            const char* As = smem + buf * GB_STAGE + (wm * 128 + fr16) * 128;
+            const char* Ws = smem + buf * GB_STAGE + 32768 + (wn * 64 + fr16) * 128;
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    if (GB_STAGGER == 1 && ks == 1 && late) issue(0, NP);
-                    if (GB_STAGGER == 2 && !late) issue(2 * ks, 2 * ks + 2);
-                    const int coff = (((ks * 4 + fq) ^ fx16) << 4);
-                    bf16x8 af[8], wf[GB_TN];
+            for (int ks = 0; ks < 2; ++ks) {
+                if (ks == 1 && late) issue();
+                const int coff = (((ks * 4 + fq) ^ fx16) << 4);
+                bf16x8 af[8], wf[4];
 #pragma unroll
-                    for (int t = 0; t < 8; ++t) af[t] = *(const bf16x8*)(As + t * 2048 + coff);
+                for (int t = 0; t < 8; ++t) af[t] = *(const bf16x8*)(As + t * 2048 + coff);
 #pragma unroll
-                    for (int t = 0; t < GB_TN; ++t) wf[t] = *(const bf16x8*)(Ws + t * 2048 + coff);
+                for (int t = 0; t < 4; ++t) wf[t] = *(const bf16x8*)(Ws + t * 2048 + coff);
 #pragma unroll
-                    for (int tm = 0; tm < 8; ++tm) {
-                        if (GB_STAGGER == 2 && late && tm == 4) issue(2 * ks, 2 * ks + 2);
-                        if (GB_W4 && !(tm & 1)) issue(4 * ks + (tm >> 1), 4 * ks + (tm >> 1) + 1);       // one piece pair per 16 MFMAs
+                for (int tm = 0; tm < 8; ++tm)
 #pragma unroll
-                        for (int tn = 0; tn < GB_TN; ++tn)
-                            acc16[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[tn], af[tm], acc16[tn][tm], 0, 0, 0);
-                    }
-                }
-#else
-                const char* As = smem + buf * GB_STAGE + (wm * 128 + fr) * 128;
-                const char* Ws = smem + buf * GB_STAGE + 32768 + (wn * 64 + fr) * 128;
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    if (GB_STAGGER == 1 && ks == 2 && late) issue(0, NP);
-                    if (GB_STAGGER == 2 && !late) issue(ks, ks + 1);
-                    const int coff = (((ks * 2 + fh) ^ fx) << 4);
-                    bf16x8 af[4], wf[2];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) af[t] = *(const bf16x8*)(As + t * 4096 + coff);
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) wf[t] = *(const bf16x8*)(Ws + t * 4096 + coff);
-#pragma unroll
-                    for (int tm = 0; tm < 4; ++tm) {
-                        if (GB_STAGGER == 2 && late && tm == 2) issue(ks, ks + 1);
-#pragma unroll
-                        for (int tn = 0; tn < 2; ++tn)
-                            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[tn], af[tm], acc[tn][tm], 0, 0, 0);
-                    }
-                }
-#endif
+                    for (int tn = 0; tn < 4; ++tn)
+                        acc16[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[tn], af[tm], acc16[tn][tm], 0, 0, 0);
             }
-#ifndef GB_ABL_NOBAR      // timing-only ablation: no barrier between K-tiles (results wrong)
             if (!last) __syncthreads();   // its vmcnt(0) also retires the next K-tile's LDS-DMA (in the waves that issued it)
-            else gb_lds_barrier();        // the cross-tile prefetch keeps flying
-#endif
+            else gemm_lds_barrier();        // the cross-tile prefetch keeps flying
             buf ^= 1;
         }
 
@@ -275,12 +152,13 @@ __global__ __launch_bounds__(GB_THREADS, 1) void GEMM_BIG_KERNEL(GemmParams p) {
         }
         // second operand of the epilogue (residual / saved pre-activation): fetched one slab ahead of its use
         constexpr bool HAS_AUX = EPI == EPI_GATED_RES || EPI == EPI_DGELU;
-        u32x2 aux[GB_EPASS], auxn[GB_EPASS];
+        u32x2 aux[4], auxn[4];
         auto aux_fetch = [&](int slab, u32x2* dst) {
 #pragma unroll
-            for (int pass = 0; pass < GB_EPASS; ++pass) {
-                const int m = cur.row0 + slab * 32 + pass * GB_EROWS + er;
+            for (int pass = 0; pass < 4; ++pass) {
+                const int m = cur.row0 + slab * 32 + pass * 8 + er;
                 dst[pass] = (u32x2){0u, 0u};
+                // (wave < 8 here and below is always true with 512 threads; removing it changes the generated code, so it stays)
                 if (HAS_AUX && wave < 8 && m < p.M && n < p.N) dst[pass] = gemm_epilogue_aux_load<EPI>(p, m, n);
             }
         };
@@ -290,45 +168,33 @@ __global__ __launch_bounds__(GB_THREADS, 1) void GEMM_BIG_KERNEL(GemmParams p) {
 #pragma unroll
         for (int slab = 0; slab < 8; ++slab) {
             if (wave < 8 && wm == (slab >> 2)) {
-#if GB_MFMA16
 #pragma unroll
                 for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
-                    for (int tn = 0; tn < GB_TN; ++tn)
-                        *(f32x4*)(Cs + (t2 * 16 + fr16) * GB_CS_LD + wn * (16 * GB_TN) + tn * 16 + 4 * fq) = acc16[tn][(slab & 3) * 2 + t2];
-#else
-                const int tm = slab & 3;
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int nl = wn * 64 + tn * 32 + 8 * q + 4 * fh;
-                        *(f32x4*)(Cs + fr * GB_CS_LD + nl) =
-                            (f32x4){acc[tn][tm][4 * q], acc[tn][tm][4 * q + 1], acc[tn][tm][4 * q + 2], acc[tn][tm][4 * q + 3]};
-                    }
-#endif
+                    for (int tn = 0; tn < 4; ++tn)
+                        *(f32x4*)(Cs + (t2 * 16 + fr16) * GB_CS_LD + wn * 64 + tn * 16 + 4 * fq) = acc16[tn][(slab & 3) * 2 + t2];
             }
-            gb_lds_barrier();
+            gemm_lds_barrier();
             if (slab < 7) aux_fetch(slab + 1, auxn);
 #pragma unroll
-            for (int pass = 0; pass < GB_EPASS; ++pass) {
-                const int ml = pass * GB_EROWS + er;
+            for (int pass = 0; pass < 4; ++pass) {
+                const int ml = pass * 8 + er;
                 const int m = cur.row0 + slab * 32 + ml;
                 if (wave < 8 && m < p.M && n < p.N) {
                     const f32x4 v = *(const f32x4*)(Cs + ml * GB_CS_LD + ec);
                     gemm_epilogue_store_aux<EPI, OUT_F32>(p, m, n, v, bias4, aux[pass], EPI == EPI_GATED_RES ? &gctx : nullptr);
                 }
             }
-            gb_lds_barrier();
+            gemm_lds_barrier();
 #pragma unroll
-            for (int pass = 0; pass < GB_EPASS; ++pass) aux[pass] = auxn[pass];
+            for (int pass = 0; pass < 4; ++pass) aux[pass] = auxn[pass];
         }
         cur = nxt;
     }
 }
 
 template <int EPI, bool F32>
-static int VT_CAT(launch_big, VT_SUFFIX)(const GemmParams& p, hipStream_t st) {
+static int launch_big(const GemmParams& p, hipStream_t st) {
     const int nbm = (p.M + GB_BM - 1) / GB_BM, nbn = (p.N + GB_BN - 1) / GB_BN;
     static int slots = 0;                 // persistent grid: one workgroup per CU, a multiple of 8
     if (slots == 0) {
@@ -338,18 +204,18 @@ static int VT_CAT(launch_big, VT_SUFFIX)(const GemmParams& p, hipStream_t st) {
     }
     const int ntiles = nbm * nbn;
     const int grid = ntiles < slots ? (ntiles + 7) / 8 * 8 : slots;
-    hipLaunchKernelGGL((GEMM_BIG_KERNEL<EPI, F32>), dim3(grid), dim3(GB_THREADS), 0, st, p);
+    hipLaunchKernelGGL((gemm_tn_big_kernel<EPI, F32>), dim3(grid), dim3(512), 0, st, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
 // same validation as vt_gemm_bf16 (gemm_bf16.hip), which calls this for large problems
-int VT_CAT(vt_gemm_big_dispatch, VT_SUFFIX)(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st) {
+int vt_gemm_big_dispatch(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st) {
     switch (epilogue) {
         case EPI_BIAS:
-            return out_fp32 ? VT_CAT(launch_big, VT_SUFFIX)<EPI_BIAS, true>(p, st) : VT_CAT(launch_big, VT_SUFFIX)<EPI_BIAS, false>(p, st);
-        case EPI_BIAS_GELU: return VT_CAT(launch_big, VT_SUFFIX)<EPI_BIAS_GELU, false>(p, st);
-        case EPI_GATED_RES: return VT_CAT(launch_big, VT_SUFFIX)<EPI_GATED_RES, false>(p, st);
-        case EPI_DGELU: return VT_CAT(launch_big, VT_SUFFIX)<EPI_DGELU, false>(p, st);
+            return out_fp32 ? launch_big<EPI_BIAS, true>(p, st) : launch_big<EPI_BIAS, false>(p, st);
+        case EPI_BIAS_GELU: return launch_big<EPI_BIAS_GELU, false>(p, st);
+        case EPI_GATED_RES: return launch_big<EPI_GATED_RES, false>(p, st);
+        case EPI_DGELU: return launch_big<EPI_DGELU, false>(p, st);
         default: return VT_ERR_UNSUPPORTED;
     }
 }

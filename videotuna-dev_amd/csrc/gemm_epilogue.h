@@ -1,5 +1,6 @@
-// Shared by the TN GEMM kernels (gemm_bf16.hip: 128x128 tile, gemm_big_bf16.hip: 256x256 tile): problem descriptor and
-// the fused epilogue applied to 4 consecutive output columns of one row.
+// Shared by the TN GEMM kernels (gemm_bf16.hip: 128x128 tile, gemm_big_bf16.hip: 256x256 tile, gemm_pc_bf16.hip: 256x128 producer /
+// consumer) and the implicit-GEMM convolution (conv3d.hip): problem descriptor, the fused epilogue applied to 4 consecutive output
+// columns of one row, and the tile order / barrier of the persistent kernels.
 #pragma once
 #include "common.h"
 
@@ -21,6 +22,37 @@ struct GemmParams {
 };
 
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_GATED_RES = 2, EPI_DGELU = 3 };
+
+// workgroup barrier that only orders LDS traffic (s_waitcnt lgkmcnt(0)); __syncthreads() would also drain vmcnt
+static __device__ __forceinline__ void gemm_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Output tile `id` of a persistent kernel with BM x BN tiles.
+struct GemmTile {
+    int row0, col0;
+    const bf16_t* a;        // first row of the tile in A / W; the descriptors are bounded by the rest of the matrix
+    const bf16_t* w;
+    unsigned a_bytes, w_bytes;
+};
+template <int BM, int BN>
+static __device__ __forceinline__ GemmTile gemm_tile(const GemmParams& p, int id, int nbm, int nbn) {
+    // grouped ordering (4 row-tiles per group, column-tiles outer): the 32 workgroups of an XCD that run together share
+    // A row-panels / W column-panels in its L2
+    const int GM = 4;
+    const int in_group = GM * nbn;
+    const int group = id / in_group;
+    const int first_m = group * GM;
+    const int gsz = min(nbm - first_m, GM);
+    GemmTile t;
+    t.row0 = (first_m + (id % in_group) % gsz) * BM;
+    t.col0 = ((id % in_group) / gsz) * BN;
+    const long long a_rem = (long long)(p.M - t.row0) * p.lda * 2;
+    const long long w_rem = (long long)(p.N - t.col0) * p.ldw * 2;
+    t.a = p.A + (size_t)t.row0 * p.lda;
+    t.w = p.W + (size_t)t.col0 * p.ldw;
+    t.a_bytes = (unsigned)(a_rem > 0x7fffffffLL ? 0x7fffffffLL : a_rem);
+    t.w_bytes = (unsigned)(w_rem > 0x7fffffffLL ? 0x7fffffffLL : w_rem);
+    return t;
+}
 
 
 // The epilogues that read a second operand (EPI_GATED_RES: residual R, EPI_DGELU: saved pre-activation U) take its four
