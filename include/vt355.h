@@ -439,6 +439,25 @@ int vt_attn_small_bwd(const void* q, const void* k, const void* v, const void* o
                       long long o_rs, long long o_bs, long long do_rs, long long do_bs, long long dq_rs, long long dq_bs,
                       long long dk_rs, long long dv_rs, float softmax_scale, int mask_block, void* stream);
 
+/* Packed temporal self-attention with learned relative-position tables, head_dim 64 (csrc/attn_relpos.hip): both attentions of
+ * TemporalTransformer under use_relative_position (lvdm/modules/attention.py:19-42, 126-149; the VideoCrafter1 / LVDM layout).
+ * Row space as vt_attn_small_* with mask_block = T: q, k, v, o are R rows = R / T consecutive sequences of T rows (32 % T == 0), element
+ * (row s, head h, d) at base + s*rs + h*64 + d.  rel_k, rel_v: bf16 [2P+1, 64], shared by all heads.  With idx(i, j) =
+ * clamp(j - i, -P, P) + P: S[i,j] = scale (q_i.k_j + q_i.rel_k[idx]), p = softmax_j S, o_i = sum_j p[i,j] (v_j + rel_v[idx]).
+ * lse2: fp32 [H, R], base-2 log-sum-exp of the total scaled score.  Backward: dq, dk, dv bf16 in the row space, written whole;
+ * d_rel_k, d_rel_v fp32 [2P+1, 64], the gradients summed over all sequences and heads are ADDED into them (fp32 atomics on the way: not
+ * bitwise reproducible from run to run); either may be NULL, with both NULL no table-gradient work is done and workspace may be NULL,
+ * otherwise workspace: vt_attn_relpos_workspace_bytes() bytes (a constant; zeroed by the call).  A refused call writes nothing. */
+long long vt_attn_relpos_workspace_bytes(void);
+int vt_attn_relpos_fwd(const void* q, const void* k, const void* v, const void* rel_k, const void* rel_v, void* o, float* lse2,
+                       int R, int H, int T, int P, long long q_rs, long long k_rs, long long v_rs, long long o_rs,
+                       float softmax_scale, void* stream);
+int vt_attn_relpos_bwd(const void* q, const void* k, const void* v, const void* rel_k, const void* rel_v, const void* o,
+                       const void* dout, const float* lse2, void* dq, void* dk, void* dv, float* d_rel_k, float* d_rel_v,
+                       void* workspace, int R, int H, int T, int P, long long q_rs, long long k_rs, long long v_rs,
+                       long long o_rs, long long do_rs, long long dq_rs, long long dk_rs, long long dv_rs,
+                       float softmax_scale, void* stream);
+
 /* Dual-context cross-attention, head_dim 64 (csrc/attn_dual.hip): o = softmax(q K^T s) V + img_scale * softmax(q K_ip^T s) V_ip, two
  * separate softmaxes over the text keys of the sample (k, v [B, Sa <= 96, .]) and the image keys of the query's frame (k_ip, v_ip
  * [B * Sq / rows_per_frame, Sb <= 32, .]; rows [f*rows_per_frame, (f+1)*rows_per_frame) of sample b meet item b * Sq / rows_per_frame + f)

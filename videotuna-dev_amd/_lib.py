@@ -137,10 +137,14 @@ PROTOTYPES = {
     "vt_attn_dual_ws_floats": [_i] * 6,
     "vt_attn_dual_fwd": [_vp] * 6 + [_fp] + [_i] * 6 + [_ll] * 12 + [_f, _f, _vp],
     "vt_attn_dual_bwd": [_vp] * 6 + [_fp, _vp] + [_fp] * 5 + [_ll] + [_i] * 6 + [_ll] * 14 + [_f, _f, _vp],
+    # ---- VideoCrafter1: temporal attention with relative-position tables ----
+    "vt_attn_relpos_workspace_bytes": [],
+    "vt_attn_relpos_fwd": [_vp] * 6 + [_fp] + [_i] * 4 + [_ll] * 4 + [_f, _vp],
+    "vt_attn_relpos_bwd": [_vp] * 7 + [_fp] + [_vp] * 3 + [_fp, _fp, _vp] + [_i] * 4 + [_ll] * 8 + [_f, _vp],
 }
 _RESTYPE = {"vt_arch": C.c_char_p, "vt_error_string": C.c_char_p, "vt_skinny_tn_workspace_bytes": C.c_longlong,
              "vt_attn_bwd_chain_ws_bytes": C.c_longlong, "vt_groupnorm_ws_bytes": C.c_longlong,
-             "vt_attn_dual_ws_floats": C.c_longlong}
+             "vt_attn_dual_ws_floats": C.c_longlong, "vt_attn_relpos_workspace_bytes": C.c_longlong}
 
 
 def load_library():

@@ -1151,6 +1151,52 @@ def attn_small_bwd(q, k, v, o, do, lse2, dq, dk, dv, H: int, scale: float, mask_
                                            dk.stride(1), dv.stride(1), scale, mask_block, _stream()), "vt_attn_small_bwd")
 
 
+_RELPOS_WS = {}
+
+
+def _relpos_args(H: int, T: int, rel_k, rel_v, rows):
+    for n, t in rows:
+        _req(t, BF16, n, 2)
+        if t.stride(1) != 1 or t.shape[1] < H * 64:
+            raise ValueError(f"attn_relpos: {n} must be a [R, >= H*64] view with unit column stride")
+    _req(rel_k, BF16, "rel_k", 2); _req(rel_v, BF16, "rel_v", 2)
+    if rel_k.shape != rel_v.shape or rel_k.shape[1] != 64 or rel_k.shape[0] % 2 != 1 or not (rel_k.is_contiguous() and rel_v.is_contiguous()):
+        raise ValueError("attn_relpos: rel_k / rel_v must be contiguous [2P+1, 64] tables")
+    return rows[0][1].shape[0], (rel_k.shape[0] - 1) // 2
+
+
+def attn_relpos_fwd(q, k, v, rel_k, rel_v, o, lse2, H: int, T: int, scale: float):
+    """packed temporal self-attention with relative-position tables: q, k, v, o [R, >= H*64] views of one row space (R / T sequences of
+    T rows), rel_k / rel_v bf16 [2P+1, 64], lse2 fp32 [H, R]"""
+    R, P = _relpos_args(H, T, rel_k, rel_v, (("q", q), ("k", k), ("v", v), ("o", o)))
+    _req(lse2, torch.float32, "lse2")
+    check(load_library().vt_attn_relpos_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), rel_k.data_ptr(), rel_v.data_ptr(), o.data_ptr(),
+                                            lse2.data_ptr(), R, H, T, P, q.stride(0), k.stride(0), v.stride(0), o.stride(0), scale,
+                                            _stream()), "vt_attn_relpos_fwd")
+
+
+def attn_relpos_bwd(q, k, v, rel_k, rel_v, o, do, lse2, dq, dk, dv, d_rel_k, d_rel_v, H: int, T: int, scale: float):
+    """dq, dk, dv bf16 like q, k, v (written whole); d_rel_k / d_rel_v fp32 [2P+1, 64] or None: the table gradients are ADDED into them
+    (fp32 atomics: not bitwise reproducible); both None (frozen tables) skips the table-gradient pass"""
+    R, P = _relpos_args(H, T, rel_k, rel_v, (("q", q), ("k", k), ("v", v), ("o", o), ("do", do), ("dq", dq), ("dk", dk), ("dv", dv)))
+    _req(lse2, torch.float32, "lse2")
+    lib = load_library()
+    for n, t in (("d_rel_k", d_rel_k), ("d_rel_v", d_rel_v)):
+        if t is not None:
+            _req(t, torch.float32, n, 2)
+            if tuple(t.shape) != tuple(rel_k.shape) or not t.is_contiguous():
+                raise ValueError(f"attn_relpos: {n} must be a contiguous fp32 [2P+1, 64] accumulator")
+    ws = None
+    if d_rel_k is not None or d_rel_v is not None:
+        if q.device not in _RELPOS_WS:              # per-device scratch of the table-gradient reduction, reused across calls (stream-ordered)
+            _RELPOS_WS[q.device] = torch.empty(lib.vt_attn_relpos_workspace_bytes() // 4, dtype=torch.float32, device=q.device)
+        ws = _RELPOS_WS[q.device]
+    check(lib.vt_attn_relpos_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), rel_k.data_ptr(), rel_v.data_ptr(), o.data_ptr(), do.data_ptr(),
+                                 lse2.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _p(d_rel_k), _p(d_rel_v), _p(ws),
+                                 R, H, T, P, q.stride(0), k.stride(0), v.stride(0), o.stride(0), do.stride(0), dq.stride(0),
+                                 dk.stride(0), dv.stride(0), scale, _stream()), "vt_attn_relpos_bwd")
+
+
 def attn_dual_ws_floats(B: int, H: int, Sq: int, rows_per_frame: int, Sa: int, Sb: int) -> int:
     n = load_library().vt_attn_dual_ws_floats(B, H, Sq, rows_per_frame, Sa, Sb)
     if n < 0:

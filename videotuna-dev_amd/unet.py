@@ -93,7 +93,7 @@ def _param_shapes(c, st) -> Dict[str, tuple]:
         sh[n + ".0.weight"] = (te, mc); sh[n + ".0.bias"] = (te,)
         sh[n + ".2.weight"] = (te, te); sh[n + ".2.bias"] = (te,)
 
-    def transformer(l, ctx_dim, img=False):
+    def transformer(l, ctx_dim, img=False, rel=False):
         pre, cc, inner = l.pre, l.c, l.inner
         k1 = (1,) if getattr(l, "conv1d", False) else ()
         sh[pre + ".norm.weight"] = (cc,); sh[pre + ".norm.bias"] = (cc,)
@@ -105,6 +105,9 @@ def _param_shapes(c, st) -> Dict[str, tuple]:
             sh[b + a + ".to_out.0.weight"] = (inner, inner); sh[b + a + ".to_out.0.bias"] = (inner,)
             if ip:          # CrossAttention(img_cross_attention=True) registers the image projections after to_out (attention.py:82-84)
                 sh[b + a + ".to_k_ip.weight"] = (inner, kd); sh[b + a + ".to_v_ip.weight"] = (inner, kd)
+            if rel:         # CrossAttention(relative_position=True): two RelativePosition tables shared by the heads (attention.py:19-42, 87-95)
+                for t in ("relative_position_k", "relative_position_v"):
+                    sh[b + a + "." + t + ".embeddings_table"] = (2 * c.temporal_length + 1, c.num_head_channels)
         attn("attn1", inner)
         sh[b + "ff.net.0.proj.weight"] = (8 * inner, inner); sh[b + "ff.net.0.proj.bias"] = (8 * inner,)
         sh[b + "ff.net.2.weight"] = (inner, 4 * inner); sh[b + "ff.net.2.bias"] = (inner,)
@@ -135,7 +138,7 @@ def _param_shapes(c, st) -> Dict[str, tuple]:
         elif l.kind == "st":
             transformer(l, c.context_dim, c.img_cross_attention)
         elif l.kind == "tt":
-            transformer(l, None)
+            transformer(l, None, rel=c.use_relative_position)
         elif l.kind == "down":
             sh[pre + ".op.weight"] = (l.c, l.c, 3, 3); sh[pre + ".op.bias"] = (l.c,)
         elif l.kind == "up":
@@ -343,14 +346,15 @@ class UNetModel(FlatParamModule):
         if in_channels > 8:
             raise NotImplementedError("the input convolution takes up to 8 channels (4 latent + 4 conditioning-frame channels)")
         unsupported = dict(use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown, tempspatial_aware=tempspatial_aware,
-                           use_relative_position=use_relative_position, use_causal_attention=use_causal_attention,
-                           use_image_attention=use_image_attention, not_use_linear=not use_linear, not_conv_resample=not conv_resample,
+                           use_causal_attention=use_causal_attention, use_image_attention=use_image_attention,
+                           not_use_linear=not use_linear, not_conv_resample=not conv_resample,
                            not_selfatt_only=not temporal_selfatt_only, depth=transformer_depth != 1 or temporal_transformer_depth != 1,
                            dims=dims != 2, num_heads=num_heads != -1)
         bad = [k for k, v in unsupported.items() if v]
         if bad:
-            raise NotImplementedError(f"vt355 UNetModel implements the VideoCrafter2 and DynamiCrafter recipes (configs/001_videocrafter2, "
-                                      f"configs/002_dynamicrafter); unsupported options: {bad}")
+            raise NotImplementedError(f"vt355 UNetModel implements the VideoCrafter1, VideoCrafter2 and DynamiCrafter recipes "
+                                      f"(configs/000_videocrafter, configs/001_videocrafter2, configs/002_dynamicrafter); "
+                                      f"unsupported options: {bad}")
         if num_head_channels != 64:
             raise NotImplementedError("the attention kernels are built for num_head_channels = 64")
         if model_channels % 64 or context_dim is None or context_dim % 64:
@@ -364,7 +368,8 @@ class UNetModel(FlatParamModule):
                                       addition_attention=addition_attention, fps_cond=fps_cond, use_checkpoint=use_checkpoint,
                                       text_context_len=text_context_len, img_cross_attention=bool(img_cross_attention),
                                       img_cross_attention_scale=1.0, img_context_len=16, default_fs=int(default_fs),
-                                      fs_condition=bool(fs_condition), dropout=float(dropout))
+                                      fs_condition=bool(fs_condition), dropout=float(dropout),
+                                      use_relative_position=bool(use_relative_position and temporal_attention))
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.tconv_dropout_p = 0.1          # TemporalConvBlock(dropout=0.1), hard-coded in ResBlock (openaimodel3d.py:205-210)
         self.dropout_seed: Optional[int] = None      # None: a fresh seed per training forward from torch's CPU generator
@@ -431,6 +436,8 @@ class UNetModel(FlatParamModule):
                 shp = self.shapes[n]
                 if len(shp) == 1:
                     w = torch.randn(shp, generator=g) * 0.1 + (1.0 if n.endswith("weight") else 0.0)
+                elif n.endswith(".embeddings_table"):       # RelativePosition: xavier_uniform_ (attention.py:29), here its standard deviation
+                    w = torch.randn(shp, generator=g) * math.sqrt(2.0 / (shp[0] + shp[1]))
                 else:
                     w = torch.randn(shp, generator=g) * (0.7 / math.sqrt(math.prod(shp[1:])))
                 p.copy_(w.to(p.device, BF16))
@@ -906,6 +913,8 @@ class _Run:
         o = self.E(M, C)
         lse = self.E(1, heads, M, dt=F32)
         q3 = qkv.d.view(1, M, 3 * C)
+        if self.c.use_relative_position:
+            return self._attention_relpos(qkv, o, lse, pre, heads, T, residual)
         ops.attn_small_fwd(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], o.view(1, M, C), lse, heads, 0.125, mask_block=T)
         ov = _Var(o)
         if self.save:
@@ -914,6 +923,23 @@ class _Run:
                 d3 = dqkv.view(1, M, 3 * C)
                 ops.attn_small_bwd(q3[:, :, :C], q3[:, :, C:2 * C], q3[:, :, 2 * C:], o.view(1, M, C), ov.g.view(1, M, C), lse,
                                    d3[:, :, :C], d3[:, :, C:2 * C], d3[:, :, 2 * C:], heads, 0.125, mask_block=T)
+                qkv.g = dqkv
+            self.tape.append(bwd)
+        return self.linear(ov, pre + ".to_out.0.weight", pre + ".to_out.0.bias", residual=residual)
+
+    def _attention_relpos(self, qkv: _Var, o, lse, pre: str, heads: int, T: int, residual: _Var) -> _Var:
+        """attention_packed with CrossAttention(relative_position=True)'s two tables (attention.py:126-149; csrc/attn_relpos.hip).  The
+        tables are parameters: their gradients are added into the flat gradient buffer (full fine-tune) or skipped (frozen base, LoRA)"""
+        M, C = o.shape
+        tk, tv = pre + ".relative_position_k.embeddings_table", pre + ".relative_position_v.embeddings_table"
+        q, k, v = qkv.d[:, :C], qkv.d[:, C:2 * C], qkv.d[:, 2 * C:]
+        ops.attn_relpos_fwd(q, k, v, self.W(tk), self.W(tv), o, lse.view(heads, M), heads, T, 0.125)
+        ov = _Var(o)
+        if self.save:
+            def bwd():
+                dqkv = self.E(M, 3 * C)
+                ops.attn_relpos_bwd(q, k, v, self.W(tk), self.W(tv), o, ov.g, lse.view(heads, M), dqkv[:, :C], dqkv[:, C:2 * C],
+                                    dqkv[:, 2 * C:], self.G(tk), self.G(tv), heads, T, 0.125)
                 qkv.g = dqkv
             self.tape.append(bwd)
         return self.linear(ov, pre + ".to_out.0.weight", pre + ".to_out.0.bias", residual=residual)
