@@ -23,6 +23,11 @@ def test_qk_rmsnorm_rope128_matches_torch(dev, L, Lout, off, rope):
     """vt_qk_rmsnorm_rope128 fwd / bwd vs a torch fp64 statement of RMSNorm (norm_layers.py:5-58) + apply_rotary_emb (posemb_layers.py:133-188)
     + the placement into the joint sequence; the rope covers the first S_rope = L - 3 positions when L == Lout (single block: text rows at
     the end are not rotated)"""
+    qk_rmsnorm_rope128_case(dev, L, Lout, off, rope)
+
+
+def qk_rmsnorm_rope128_case(dev, L, Lout, off, rope, rows=None):
+    """rows: (B L 3 H, 128, generator) -> the bf16-representable 128-wide head rows, in place of the randn ones (tests/test_conditioning_gpu.py)"""
     import hunyuan_oracle as HO
     from vt355 import ops
     gen = torch.Generator().manual_seed(5)
@@ -30,6 +35,8 @@ def test_qk_rmsnorm_rope128_matches_torch(dev, L, Lout, off, rope):
     C = H * 128
     S_rope = (L - 3 if L == Lout else L) if rope else 0
     qkv = torch.randn(B * L, 3 * C, generator=gen).to(BF)
+    if rows is not None:
+        qkv = rows(B * L * 3 * H, 128, gen).view(B * L, 3 * C).to(BF)
     gq = (1 + 0.1 * torch.randn(128, generator=gen)).to(BF); gk = (1 + 0.1 * torch.randn(128, generator=gen)).to(BF)
     cos, sin = _rope_tables(max(S_rope, 1), gen)
     dout = torch.randn(B * Lout, 3 * C, generator=gen).to(BF)
@@ -271,11 +278,20 @@ def test_sp_device_core_matches_dense_attention(dev):
 def test_attn128_matches_dense_attention(dev, B, S, H, lens):
     """vt_attn128_fwd / _bwd (long-sequence head_dim-128 kernels) vs dense fp64 attention with per-sample valid lengths: output, log-sum-exp,
     dQ, dK, dV; ragged tiles (S not a multiple of 64 / 128), a one-key sample, keys past the valid length get zero gradients"""
-    from vt355 import ops
     gen = torch.Generator().manual_seed(S + H)
     C = H * 128
     qkv = torch.randn(B, S, 3 * C, generator=gen).to(BF)
     g = torch.randn(B, S, C, generator=gen).to(BF)
+    attn128_case(dev, qkv, g, H, lens)
+
+
+def attn128_case(dev, qkv, g, H, lens):
+    """qkv: bf16 [B, S, 3 H 128] fused q | k | v rows, g: bf16 [B, S, H 128] upstream gradient, lens: valid keys per sample or None.
+    Forward, the one-pass (fp32 atomic dQ) and the two-pass (bf16 dQ) backward against dense fp64 attention (shared with
+    tests/test_conditioning_gpu.py, which feeds it inputs that move the running maximum late in the key loop)"""
+    from vt355 import ops
+    B, S, C = g.shape
+    g = g.clone()
     kv = None if lens is None else torch.tensor(lens, dtype=torch.int32)
     if kv is not None:
         for b in range(B):

@@ -139,11 +139,18 @@ def test_cast_fp8_scaled_exact(dev):
 
 def test_ln_modulate_fwd_fp8_exact(dev):
     """the bf16 output equals vt_ln_modulate_fwd's bit for bit; the fp8 copy is the CPU cast of it; the amax exact"""
+    ln_modulate_fwd_fp8_case(dev)
+
+
+def ln_modulate_fwd_fp8_case(dev, rows=None):
+    """rows: (M, D, generator) -> the bf16-representable input rows, in place of the randn ones (tests/test_conditioning_gpu.py)"""
     from vt355 import ops
     gen = torch.Generator().manual_seed(5)
     B, L, D = 2, 70, 3072
     M = B * L
     x = torch.randn(M, D, generator=gen).to(BF).to(dev)
+    if rows is not None:
+        x = rows(M, D, gen).to(BF).to(dev)
     modv = torch.randn(B, 6 * D, generator=gen).to(dev) * 0.3
     sh, sc = modv[:, :D], modv[:, D:2 * D]
     mod = (sh, sc, sh, sc, 6 * D)

@@ -280,13 +280,16 @@ def test_attn_bwd_timeout_is_repaired_by_redoing_the_launch_without_chains(dev):
 
 
 # ------------------------------------------------------------------ norms
-def _ln_modulate_case(dev, D, B=2, S=37, St=5, affine=True):
+def _ln_modulate_case(dev, D, B=2, S=37, St=5, affine=True, rows=None):
     """vt_ln_modulate_fwd / _bwd on a strided [M, D + 64] pair of buffers: y, mean, rstd and dx are written whole (poisoned before the
-    launch), the 64 pad columns of y are never written; then the plain LayerNorm call (no modulation) when there is an affine part"""
+    launch), the 64 pad columns of y are never written; then the plain LayerNorm call (no modulation) when there is an affine part.
+    rows: (M, D, generator) -> the bf16-representable input rows, in place of the randn ones (tests/test_conditioning_gpu.py)"""
     from vt355 import ops
     g = torch.Generator().manual_seed(D)
     M = B * S
     x = rb(torch.randn(M, D, generator=g) * 2 + 0.5)
+    if rows is not None:
+        x = rows(M, D, g)
     ga = rb(1 + 0.1 * torch.randn(D, generator=g)); be = rb(0.1 * torch.randn(D, generator=g))
     mod = torch.randn(B, 6 * D, generator=g) * 0.3          # shift, scale, gate, eshift, escale, egate
     rows_b = torch.arange(M) // S
@@ -349,11 +352,18 @@ def test_ln_modulate_refuses_rows_wider_than_4096(dev):
 
 
 def test_qk_layernorm(dev):
+    _qk_layernorm_case(dev)
+
+
+def _qk_layernorm_case(dev, rows=None):
+    """rows: (M * 3 H, 64, generator) -> the bf16-representable 64-wide head rows, in place of the randn ones (tests/test_conditioning_gpu.py)"""
     from vt355 import ops
     g = torch.Generator().manual_seed(11)
     M, H = 203, 3
     D = H * 64
     qkv = rb(torch.randn(M, 3 * D, generator=g) * 1.5)
+    if rows is not None:
+        qkv = rows(M * 3 * H, 64, g).view(M, 3 * D)
     gq, bq, gk, bk = [rb(t) for t in (1 + 0.2 * torch.randn(64, generator=g), 0.2 * torch.randn(64, generator=g),
                                        1 + 0.2 * torch.randn(64, generator=g), 0.2 * torch.randn(64, generator=g))]
     x = qkv.clone().requires_grad_(True)
@@ -679,9 +689,16 @@ def test_abi_rejects_bad_arguments(dev):
 @pytest.mark.parametrize("M,D", [(5, 64), (452, 4096), (300, 1032)])
 def test_rmsnorm(dev, M, D):
     """T5LayerNorm (transformers modeling_t5.T5LayerNorm): x * rsqrt(mean(x^2) + eps) * w, fp32 statistics, strided rows"""
+    _rmsnorm_case(dev, M, D)
+
+
+def _rmsnorm_case(dev, M, D, rows=None):
+    """rows: (M, D, generator) -> the bf16-representable input rows, in place of the randn ones (tests/test_conditioning_gpu.py)"""
     from vt355 import ops
     g = torch.Generator().manual_seed(M + D)
     xb = rb(torch.randn(M, D + 8, generator=g) * 3.0); w = rb(1.0 + 0.2 * torch.randn(D, generator=g))
+    if rows is not None:
+        xb[:, :D] = rows(M, D, g)
     x = xb[:, :D]
     ref = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6) * w
     X = xb.to(dev, BF)

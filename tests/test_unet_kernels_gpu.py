@@ -465,18 +465,21 @@ def test_attn_small_packed_sequences(dev, R, T, H):
 
 
 # ------------------------------------------------------------------------------------------------ generic-head-dim attention
-def _gen_case(dev, NB, H, Sq, Sk, hd, hstride, kv_len=None, mask_block=0, seed=0, bf16_out=False):
+def _gen_case(dev, NB, H, Sq, Sk, hd, hstride, kv_len=None, mask_block=0, seed=0, bf16_out=False, shape_keys=None):
     """every output is poisoned first.  Written whole: the head_dim (80 | 128) columns of every head of o and dq, lse, dk / dv in the packed
     and the bf16 forms (the fp32 dk / dv accumulators are zeroed by the binding and summed into).  Never written: the columns between
-    head_dim and hstride of every head.  bf16 dk / dv rows at and past a sample's kv_len come back exactly 0."""
+    head_dim and hstride of every head.  bf16 dk / dv rows at and past a sample's kv_len come back exactly 0.
+    shape_keys: applied to the randn keys [NB, Sk, H, hstride] in place before they are rounded to bf16 (tests/test_conditioning_gpu.py)."""
     from vt355 import ops
     g = torch.Generator().manual_seed(seed + Sq + Sk + hd)
     hp = 80 if hd == 72 else 128
-    def mk(S):
+    def mk(S, shape=None):
         t = torch.zeros(NB, S, H, hstride)
         t[..., :hd] = torch.randn(NB, S, H, hd, generator=g)
+        if shape is not None:
+            shape(t)
         return rb(t)
-    q, k, v, do = mk(Sq), mk(Sk), mk(Sk), mk(Sq)
+    q, k, v, do = mk(Sq), mk(Sk, shape_keys), mk(Sk), mk(Sq)
     scale = hd ** -0.5
     qr, kr, vr = [t[..., :hd].double().permute(0, 2, 1, 3).clone().requires_grad_(True) for t in (q, k, v)]
     s = torch.einsum("bhid,bhjd->bhij", qr, kr) * scale

@@ -7,10 +7,14 @@
 // which is also what an implicit-GEMM convolution wants for its K dimension.
 //
 // HBM-bound: x is read twice (statistics, apply) and y written once = 6 bytes per element.  Three launches:
-//   1. per-CHANNEL sums and sums of squares: a thread owns 8 consecutive channels and strides over the positions, block reduction
-//      through LDS, one fp32 atomic per channel and block into ws (any channels-per-group works, e.g. 320 / 32 = 10);
+//   1. per-CHANNEL sums and sums of squares of x - k_c about the pivot k_c = x[n, 0, c] (every block reads it for itself): a thread owns 8
+//      consecutive channels and strides over the positions, block reduction through LDS, one fp32 atomic per channel and block into ws
+//      (any channels-per-group works, e.g. 320 / 32 = 10);
 //   2. fold channels into groups -> per-channel affine  y = x * a[n,c] + b[n,c]  (a = rstd*gamma, b = beta - mean*rstd*gamma);
 //   3. apply (+ SiLU).
+// Why the pivot: sums of x and x^2 give var = E[x^2] - mean^2, which is rounding noise in fp32 once |mean| >> std (a plateau at 100 with a
+// spread of 0.05 came back with rstd off by 14 % .. 50 x).  About a sample of the channel itself the sums are of the size of the spread, and
+// the pass over x stays a single one.  The group's variance is the parallel-variance fold of its channels (gn_finalize_kernel).
 #include "common.h"
 
 #define GN_THREADS 256
@@ -29,16 +33,18 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const bf16_t* x, l
         const int lanes = GN_THREADS / ncl * ncl;         // threads that take part (a whole number of positions per pass)
         if (tid < lanes) {
             const int c = c0 + tid % ncl, row = tid / ncl, rows = lanes / ncl;
-            float s[8], q[8];
+            float s[8], q[8], k[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
             const bf16_t* xb = x + ((long long)n * P) * ldx + c * 8;
+            const u32x4 kraw = *(const u32x4*)xb;                           // the pivots: position 0 of the sample
+            unpack8(kraw, k);
             for (long long p = p0 + row; p < p1; p += 4 * rows) {          // four positions in flight per thread
                 u32x4 r[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const long long pp = p + (long long)u * rows;
-                    r[u] = (u32x4){0u, 0u, 0u, 0u};
+                    r[u] = kraw;                                            // past the slab: x - k = 0 adds nothing
                     if (pp < p1) r[u] = *(const u32x4*)(xb + pp * ldx);
                 }
 #pragma unroll
@@ -46,7 +52,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const bf16_t* x, l
                     float v[8];
                     unpack8(r[u], v);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+                    for (int j = 0; j < 8; ++j) { const float d = v[j] - k[j]; s[j] += d; q[j] += d * d; }
                 }
             }
 #pragma unroll
@@ -59,21 +65,37 @@ __global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(const bf16_t* x, l
 }
 
 // one block per sample, a thread per channel: the channel sums are folded into their groups through LDS (r03: the first version gave a
-// group to a thread, 2 x C/G dependent global reads each -- 13 .. 39 us per call at C = 1280, 27 ms of the UNet's step with its backward twin)
-__global__ __launch_bounds__(256) void gn_finalize_kernel(float* ws, const bf16_t* gamma, const bf16_t* beta, long long P, int C, int G, float eps) {
-    extern __shared__ float gsh[];                  // [4][G]: sum | sum of squares | mean | rstd
+// group to a thread, 2 x C/G dependent global reads each -- 13 .. 39 us per call at C = 1280, 27 ms of the UNet's step with its backward twin).
+// Channel c holds s = sum (x - k_c), q = sum (x - k_c)^2 over its P positions:  mean_c = k_c + s / P,  M2_c = q - s^2 / P.  Groups by the
+// parallel-variance formula, the channel means taken relative to the pivot of the group's first channel (differences of bf16 values: exact):
+//   d_c = mean_c - k_g,  mean_g = k_g + avg_c d_c,  M2_g = sum_c M2_c + P sum_c (d_c - avg d)^2,  var_g = M2_g / (P C/G)
+__global__ __launch_bounds__(256) void gn_finalize_kernel(float* ws, const bf16_t* x, long long ldx, const bf16_t* gamma, const bf16_t* beta,
+                                                          long long P, int C, int G, float eps) {
+    extern __shared__ float gsh[];                  // [4][G]: sum of d_c, then of (d_c - avg d)^2 | sum of M2_c | mean | rstd
     const int n = blockIdx.x, tid = threadIdx.x;
     float* w = ws + (size_t)n * 4 * C;
+    const bf16_t* x0 = x + ((long long)n * P) * ldx;
     const int cpg = C / G;
+    const float invp = 1.0f / (float)P;
     for (int g = tid; g < 2 * G; g += 256) gsh[g] = 0.f;
     __syncthreads();
-    for (int c = tid; c < C; c += 256) { atomicAdd(gsh + c / cpg, w[c]); atomicAdd(gsh + G + c / cpg, w[C + c]); }
+    for (int c = tid; c < C; c += 256) {
+        const float s = w[c], q = w[C + c];
+        const float d = (bf2f(x0[c]) - bf2f(x0[c / cpg * cpg])) + s * invp;
+        w[2 * C + c] = d;                           // the a | b planes are free until the last loop
+        atomicAdd(gsh + c / cpg, d);
+        atomicAdd(gsh + G + c / cpg, fmaxf(q - s * s * invp, 0.f));
+    }
+    __syncthreads();
+    for (int g = tid; g < G; g += 256) { gsh[2 * G + g] = gsh[g] / (float)cpg; gsh[g] = 0.f; }      // avg d; the slot now sums (d_c - avg d)^2
+    __syncthreads();
+    for (int c = tid; c < C; c += 256) { const float e = w[2 * C + c] - gsh[2 * G + c / cpg]; atomicAdd(gsh + c / cpg, e * e); }
     __syncthreads();
     const float cnt = (float)cpg * (float)P;
     for (int g = tid; g < G; g += 256) {
-        const float mean = gsh[g] / cnt;
-        const float var = fmaxf(gsh[G + g] / cnt - mean * mean, 0.f);
-        gsh[2 * G + g] = mean; gsh[3 * G + g] = rsqrtf(var + eps);
+        const float var = (gsh[G + g] + (float)P * gsh[g]) / cnt;
+        gsh[2 * G + g] += bf2f(x0[g * cpg]);
+        gsh[3 * G + g] = rsqrtf(var + eps);
     }
     __syncthreads();
     for (int c = tid; c < C; c += 256) {
@@ -136,7 +158,7 @@ extern "C" int vt_groupnorm_silu_cl(const void* x, long long ldx, const void* ga
     if (hipMemsetAsync(ws, 0, (size_t)N * 4 * C * 4, st) != hipSuccess) return VT_ERR_LAUNCH;
     const int slabs = gn_slabs(N, P, C);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(slabs, N), dim3(GN_THREADS), 2 * C * sizeof(float), st, (const bf16_t*)x, ldx, P, C, ws, slabs);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 4 * G * sizeof(float), st, ws, (const bf16_t*)gamma, (const bf16_t*)beta, P, C, G, eps);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 4 * G * sizeof(float), st, ws, (const bf16_t*)x, ldx, (const bf16_t*)gamma, (const bf16_t*)beta, P, C, G, eps);
     const long long total = P * (C >> 3);
     long long blocks = (total + GN_THREADS - 1) / GN_THREADS;
     if (blocks > 8192) blocks = 8192;
