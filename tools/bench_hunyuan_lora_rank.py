@@ -9,6 +9,13 @@ has its own adapter set (same seed), optimizer and packed K-extension operands, 
 HBM of its blocks (the other ranks' packed operands are resident and counted) and the delta against rank 4 of the same mode.
 
     python tools/bench_hunyuan_lora_rank.py [--ranks 4,16,32,64,128] [--rounds 3] [--steps 2] [--warmup 1] > profiles/hunyuan_lora_rank_step.json
+
+``--targets attn,attn+ff`` adds the target set as a second axis: ``attn`` = the attention projections (the default, lora_target_modules=None),
+``attn+ff`` = all eight targets (ff.net.0.proj, ff.net.2, proj_mlp, proj_out as well); ``ff`` = the four feed-forward targets alone.  Every
+(target set, rank) pair is a variant of its own in the alternation; the result then carries the trainable parameters of each and is keyed
+"<targets>/<rank>", deltas against the first variant.
+
+    python tools/bench_hunyuan_lora_rank.py --targets attn,attn+ff --ranks 4,64 --modes bf16,mfma,mfma+dgrad > profiles/hunyuan_lora_ff_step.json
 """
 import argparse
 import json
@@ -19,13 +26,17 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = {"bf16": (False, False), "mfma+dgrad": ("mfma", True)}
+MODES = {"bf16": (False, False), "mfma": ("mfma", False), "mfma+dgrad": ("mfma", True)}
+_ATTN = ["to_q", "to_k", "to_v", "to_out.0"]
+_FF = ["ff.net.0.proj", "ff.net.2", "proj_mlp", "proj_out"]
+TARGETS = {"attn": None, "attn+ff": _ATTN + _FF, "ff": _FF}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ranks", default="4,16,32,64,128")
     ap.add_argument("--modes", default="bf16,mfma+dgrad")
+    ap.add_argument("--targets", default="attn", help="comma-separated target sets: " + ", ".join(TARGETS))
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
@@ -39,19 +50,27 @@ def main():
         raise SystemExit("bench_hunyuan_lora_rank needs the GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(0)
-    ranks = [int(v) for v in args.ranks.split(",")]
+    tsets = args.targets.split(",")
+    keyed = tsets != ["attn"]                    # the default keeps the result's rank keys
+    # The variants share ONE pack of the frozen weights, built on the first step for the first variant's sites: it holds a bf16 transpose of
+    # every Linear that variant does not adapt.  "attn" first serves "attn+ff" too (which needs fewer); "ff" adapts other Linears than it keeps.
+    if len(tsets) > 1 and ("ff" in tsets or tsets[0] != "attn"):
+        raise SystemExit("--targets: several sets share one weight pack -- put attn first, and run ff in a process of its own")
+    ranks = [(tg, int(v)) for tg in tsets for v in args.ranks.split(",")]
+    name = lambda k: f"{k[0]}/{k[1]}" if keyed else str(k[1])
     nd, ns = (20, 40) if args.layers == 30 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
     lT, lH, lW, Lt, B = 5, 68, 120, 256, 1
-    model = HYVideoDiffusionTransformer(mm_double_blocks_depth=nd, mm_single_blocks_depth=ns, lora_rank=ranks[0]).to(dev).init_weights(11)
+    model = HYVideoDiffusionTransformer(mm_double_blocks_depth=nd, mm_single_blocks_depth=ns, lora_rank=ranks[0][1]).to(dev).init_weights(11)
     flow = HunyuanVideoFlow(model=model, learning_rate=1e-5).to(dev)
     runs = {}
-    for r in ranks:
-        L = _HYLora(model.hidden_size, nd, ns, r, 1.0).to(dev)
+    for key in ranks:
+        tg, r = key
+        L = _HYLora(model.hidden_size, nd, ns, r, 1.0, model.ratio, TARGETS[tg]).to(dev)
         L.init_weights(12, zero_b=False)
         model.lora = L
         ts = model.enable_lora_training()
-        runs[r] = dict(lora=L, opt=FusedAdamW(ts.params, lr=1e-5, fullft_state=ts), layout="wide" if L.wide else "narrow",
-                       ext=(L.ext_qkv, L.ext_proj))
+        runs[key] = dict(lora=L, opt=FusedAdamW(ts.params, lr=1e-5, fullft_state=ts), layout="wide" if L.wide else "narrow",
+                         ext=(L.ext_qkv, L.ext_proj), params=sum(int(torch.tensor(sh).prod()) for sh in L.shapes.values()))
     g = torch.Generator(device=dev).manual_seed(20230211)
     tv = torch.tensor([Lt], device=dev)
     mask = (torch.arange(Lt, device=dev)[None, :] < tv[:, None]).long()
@@ -96,16 +115,17 @@ def main():
         for r in ranks:
             run = runs[r]
             assert bool(torch.isfinite(run["loss"])), (mode, r)
-            res[str(r)] = {"layout": run["layout"], "ext_qkv_proj": run["ext"], "ms_per_step_median": statistics.median(run["ms"]),
+            res[name(r)] = {"layout": run["layout"], "ext_qkv_proj": run["ext"], "trainable_params": run["params"], "ms_per_step_median": statistics.median(run["ms"]),
                            "ms_per_step_rounds": run["ms"], "spread_ms": max(run["ms"]) - min(run["ms"]), "peak_hbm_gb": round(run["peak"], 1),
                            "loss_last": float(run["loss"])}
-        ref = res[str(ranks[0])]["ms_per_step_median"]
+        ref = res[name(ranks[0])]["ms_per_step_median"]
+        first = f"rank_{ranks[0][1]}" if not keyed else name(ranks[0])
         for r in ranks:
-            res[str(r)][f"delta_vs_rank_{ranks[0]}_ms"] = res[str(r)]["ms_per_step_median"] - ref
-            res[str(r)][f"delta_vs_rank_{ranks[0]}_pct"] = 100.0 * (res[str(r)]["ms_per_step_median"] - ref) / ref
+            res[name(r)][f"delta_vs_{first}_ms"] = res[name(r)]["ms_per_step_median"] - ref
+            res[name(r)][f"delta_vs_{first}_pct"] = 100.0 * (res[name(r)]["ms_per_step_median"] - ref) / ref
         out[mode] = res
     print(json.dumps({"workload": f"HunyuanVideo-T2V denoiser ({nd} + {ns} blocks), latents 16x{lT}x{lH}x{lW}, {lT * (lH // 2) * (lW // 2)} image + "
-                                  f"{Lt} text tokens, micro-batch {B}, LoRA on img q / k / v / out, HunyuanVideoFlow.training_step + AdamW",
+                                  f"{Lt} text tokens, micro-batch {B}, LoRA target sets {tsets}, HunyuanVideoFlow.training_step + AdamW",
                       "rounds": args.rounds, "steps_per_block": args.steps, "warmup": args.warmup, "modes": out}), flush=True)
 
 

@@ -27,6 +27,9 @@ gated d(proj out), gated d(fc2 out), d(u); per single block gated d(linear2 out)
 start of each backward.  The gated gradients are quantised by the gate multiply (vt_gate_mul_fp8), d(u) by the dGELU epilogue of the
 product that makes it, d(qkv) by one cast pass.  Parameter gradients keep reading the bf16 gradients; the forward is untouched (beyond the
 reference, which never quantises gradients).
+LoRA (``lora_rank``, ``lora_target_modules``): rank-r adapters on the image stream's attention projections (the shipped recipe's targets,
+the default) and, by name, on its feed-forward Linears -- fc1, fc2, the MLP rows of linear1, linear2 (_HYLora); every adapted Linear stays
+ONE GEMM over K-extended operands, forward and input gradient (DESIGN 3 "LoRA as a K-extension").
 
 NOT built (recorded in DESIGN.md): the embedders / token refiner / final layer of HYVideoDiffusionTransformer, the diffusers
 ``HunyuanVideoTransformer3DModel`` key map and LoRA wrappers of the shipped recipe, (the head_dim-128 attention backward is atomics-only: no dQ hand-off chains yet).  Padding text rows attend to the valid keys here
@@ -93,33 +96,89 @@ def lora_layout(r: int):
     return extension_layout(r, wide=True)
 
 
+ATTN_TARGETS = ("to_q", "to_k", "to_v", "to_out.0")                       # one group: today's sites
+FF_TARGETS = ("ff.net.0.proj", "ff.net.2", "proj_mlp", "proj_out")        # chosen one by one
+
+
+def resolve_lora_targets(target_modules):
+    """(attn, ff) for ``lora_target_modules``: attn -- whether the attention group ATTN_TARGETS is adapted, ff -- the members of FF_TARGETS
+    that are, in FF_TARGETS order.  None: the attention group alone (the shipped recipe).  The names are the diffusers / peft names of
+    configs/007_hunyuanvideo/hunyuanvideo_t2v_diffuser_lora.yaml; they reach the image stream's Linears of the double blocks and the
+    single blocks only -- the token refiner's feed-forward and the model-level proj_out, which peft's suffix rule would also match on
+    diffusers' class, stay frozen."""
+    if target_modules is None:
+        return True, ()
+    if isinstance(target_modules, str):
+        target_modules = [target_modules]
+    names = list(target_modules)
+    unknown = [t for t in names if t not in ATTN_TARGETS + FF_TARGETS]
+    if unknown:
+        raise ValueError(f"unsupported HunyuanVideo LoRA target(s) {unknown}: {ATTN_TARGETS + FF_TARGETS} are supported")
+    if not names:
+        raise ValueError("lora_target_modules is empty: name targets or pass None for the attention projections")
+    got = [t for t in ATTN_TARGETS if t in names]
+    if got and len(got) != len(ATTN_TARGETS):
+        raise ValueError(f"the attention targets {ATTN_TARGETS} are adapted together (the fused q | k | v projections share one K-extension): "
+                         f"{got} alone is not supported")
+    return bool(got), tuple(t for t in FF_TARGETS if t in names)
+
+
 class _HYLora(FlatParamModule):
-    """rank-r adapters on the image stream's attention projections, the modules the shipped recipe targets (configs/007_hunyuanvideo/
-    hunyuanvideo_t2v_diffuser_lora.yaml:59-64: r 4, alpha 1, target_modules to_q / to_k / to_v / to_out.0 of diffusers' attention): here the
+    """rank-r adapters on the image stream's Linears.  The attention group (the modules the shipped recipe targets, configs/007_hunyuanvideo/
+    hunyuanvideo_t2v_diffuser_lora.yaml:59-64: r 4, alpha 1, target_modules to_q / to_k / to_v / to_out.0 of diffusers' attention): the
     q / k / v row blocks of ``double_blocks.N.img_attn_qkv`` and of ``single_blocks.N.linear1`` and ``double_blocks.N.img_attn_proj``.
     Parameter names: ``<module>.lora_A.{q,k,v}.weight [r, D]``, ``<module>.lora_B.{q,k,v}.weight [D, r]`` (proj: no q/k/v level).
+    The feed-forward targets (``target_modules``, resolve_lora_targets), one adapter each, behind the attention group's parameters:
+    ff.net.0.proj -> ``double_blocks.N.img_mlp.fc1`` (A [r, D], B [4D, r]), ff.net.2 -> ``double_blocks.N.img_mlp.fc2`` (A [r, 4D],
+    B [D, r]), proj_mlp -> the MLP rows of ``single_blocks.N.linear1`` (tag ``mlp``: A [r, D], B [4D, r]), proj_out ->
+    ``single_blocks.N.linear2`` (A [r, 5D], B [D, r]).
     Ranks 1..128; the K-extension layout (narrow up to 3 r = 64, wide above) is lora_layout's and does not show in names or shapes."""
 
-    def __init__(self, D: int, n_double: int, n_single: int, r: int, alpha: float):
+    def __init__(self, D: int, n_double: int, n_single: int, r: int, alpha: float, ratio: float = 4.0, target_modules=None):
         super().__init__()
         self.rp, self.ext_qkv, self.ext_proj, self.wide = lora_layout(r)      # fixed at construction (VT355_LORA_WIDE is read here)
         self.r, self.scaling, self.D = r, alpha / r, D
+        self.attn, self.ff_targets = resolve_lora_targets(target_modules)
         sh: Dict[str, tuple] = {}
-        self.sites: Dict[str, list] = {}            # module name -> adapter tags
-        for i in range(n_double):
-            self.sites[f"double_blocks.{i}.img_attn_qkv"] = ["q", "k", "v"]
-            self.sites[f"double_blocks.{i}.img_attn_proj"] = [""]
-        for i in range(n_single):
-            self.sites[f"single_blocks.{i}.linear1"] = ["q", "k", "v"]
+        self.sites: Dict[str, list] = {}            # module name -> adapter tags (the attention group)
+        if self.attn:
+            for i in range(n_double):
+                self.sites[f"double_blocks.{i}.img_attn_qkv"] = ["q", "k", "v"]
+                self.sites[f"double_blocks.{i}.img_attn_proj"] = [""]
+            for i in range(n_single):
+                self.sites[f"single_blocks.{i}.linear1"] = ["q", "k", "v"]
         for mod, tags in self.sites.items():
             for t in tags:
                 dot = "." + t if t else ""
                 sh[f"{mod}.lora_A{dot}.weight"] = (r, D)
                 sh[f"{mod}.lora_B{dot}.weight"] = (D, r)
+        # The feed-forward sites: ONE adapter per site, in the extension columns [0, r) -- the narrow and the wide layout differ in the
+        # extension's width only (64 / rp rounded up to 64); t = x A^T and dt = g (scaling B) are bf16 GEMMs with N = ext, the rank
+        # gradients run on vt_lora_tn_wide, the pack kernels are the wide layout's with the rank padded to rpf.  ff: site key -> (module, tag, in width, out width, first weight row); the key is the module name, for
+        # linear1's MLP rows "<module>#mlp" (the module name is the attention group's q | k | v site).
+        M4 = int(D * ratio)
+        self.rpf, self.ext_ff = (r + 15) // 16 * 16, self.ext_proj
+        self.ff: Dict[str, SimpleNamespace] = {}
+        want = set(self.ff_targets)
+        for i in range(n_double):
+            if "ff.net.0.proj" in want:
+                self.ff[f"double_blocks.{i}.img_mlp.fc1"] = SimpleNamespace(mod=f"double_blocks.{i}.img_mlp.fc1", tag="", din=D, dout=M4, row0=0)
+            if "ff.net.2" in want:
+                self.ff[f"double_blocks.{i}.img_mlp.fc2"] = SimpleNamespace(mod=f"double_blocks.{i}.img_mlp.fc2", tag="", din=M4, dout=D, row0=0)
+        for i in range(n_single):
+            if "proj_mlp" in want:
+                self.ff[f"single_blocks.{i}.linear1#mlp"] = SimpleNamespace(mod=f"single_blocks.{i}.linear1", tag="mlp", din=D, dout=M4, row0=3 * D)
+            if "proj_out" in want:
+                self.ff[f"single_blocks.{i}.linear2"] = SimpleNamespace(mod=f"single_blocks.{i}.linear2", tag="", din=D + M4, dout=D, row0=0)
+        for s in self.ff.values():
+            dot = "." + s.tag if s.tag else ""
+            s.a_name, s.b_name = f"{s.mod}.lora_A{dot}.weight", f"{s.mod}.lora_B{dot}.weight"
+            sh[s.a_name] = (r, s.din)
+            sh[s.b_name] = (s.dout, r)
         self._setup_flat(sh)
 
     def ext_of(self, mod: str) -> int:
-        """K-extension columns of the adapted Linear `mod`"""
+        """K-extension columns of the adapted Linear `mod` of the attention group"""
         return self.ext_qkv if len(self.sites[mod]) == 3 else self.ext_proj
 
     def init_weights(self, seed: int = 0, zero_b: bool = True):
@@ -128,7 +187,7 @@ class _HYLora(FlatParamModule):
         with torch.no_grad():
             for n, p in self._plist.items():
                 if ".lora_A" in n:
-                    p.copy_((torch.randn(self.shapes[n], generator=g) * self.D ** -0.5).to(p.device, BF16))
+                    p.copy_((torch.randn(self.shapes[n], generator=g) * self.shapes[n][1] ** -0.5).to(p.device, BF16))
                 else:
                     p.copy_((torch.zeros(self.shapes[n]) if zero_b else torch.randn(self.shapes[n], generator=g) * 0.05).to(p.device, BF16))
         self._packed = None
@@ -142,7 +201,7 @@ class HunyuanBlocks(FlatParamModule):
     def __init__(self, hidden_size: int = 3072, heads_num: int = 24, mlp_width_ratio: float = 4.0, mm_double_blocks_depth: int = 20,
                  mm_single_blocks_depth: int = 40, fp8: bool = False, lora_rank: int = 0, lora_alpha: float = 1.0,
                  shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None, fp8_amax_history: int = 16,
-                 fp8_dgrad=False):
+                 fp8_dgrad=False, lora_target_modules=None):
         super().__init__()
         if hidden_size // heads_num != 128 or hidden_size % 128:
             raise ValueError("HunyuanVideo heads are 128 wide")
@@ -160,7 +219,11 @@ class HunyuanBlocks(FlatParamModule):
         self._setup_flat({**(shapes_before or {}), **sh, **(shapes_after or {})})
         # LoRA mode: the block weights stay frozen (no fp32 master, no gradients, no dW GEMMs); only the adapters train
         # lora_rank 0: no adapters; 1..MAX_R: _HYLora (which refuses anything else)
-        self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha) if lora_rank != 0 else None
+        # lora_target_modules: None = the attention projections (resolve_lora_targets); names without a rank are still checked
+        if lora_rank == 0:
+            resolve_lora_targets(lora_target_modules)
+        self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha, mlp_width_ratio,
+                            lora_target_modules) if lora_rank != 0 else None
         self.sp_group = None
         self.fp8_dgrad = fp8_dgrad
 
@@ -321,7 +384,8 @@ def _packed_hy(model: HunyuanBlocks) -> SimpleNamespace:
         for n, shp in model.shapes.items():
             if n.endswith(".weight") and len(shp) == 2:
                 w = model.flat(fb, n)
-                lora_site = model.lora is not None and n[:-7] in model.lora.sites       # its transposed operand is the extended one (_packed_lora)
+                # an adapted Linear's transposed operand is the extended one (_packed_lora / _pack_ff)
+                lora_site = model.lora is not None and (n[:-7] in model.lora.sites or n[:-7] in model.lora.ff)
                 if model.fp8:                                       # E4M3 copy + per-tensor scale (fp8_optimization.py:55-64) ...
                     wq, sw = ops.quantize_fp8(w)
                     w = (wq.to(torch.float32) * sw).to(BF16)        # ... and what the reference multiplies with: dequant(W) (:50-53, 72-78)
@@ -373,7 +437,7 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
                 regular &= L.offsets[f"{mod}.lora_A{dot}.weight"] == 2 * sidx * r * D and L.offsets[f"{mod}.lora_B{dot}.weight"] == (2 * sidx + 1) * r * D
                 site_of[(mod, t)] = sidx
                 sidx += 1
-        P.nsites, P.regular = sidx, bool(regular and L.numel == 2 * sidx * r * D)
+        P.nsites, P.regular = sidx, bool(regular)        # the feed-forward sites' parameters lie behind these 2 sidx r D elements
         P.idx3 = [torch.tensor([site_of[(m_, t)] for m_ in mods3], dtype=torch.long, device=dev) for t in ("q", "k", "v")]
         P.idx1 = torch.tensor([site_of[(m_, "")] for m_ in mods1], dtype=torch.long, device=dev)
         n3, n1 = len(mods3), len(mods1)
@@ -400,7 +464,7 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
     n3 = len(P.mods3)
     with torch.no_grad():
         if P.regular:
-            S2 = L.flat_bf16.view(P.nsites, 2, r * D)
+            S2 = L.flat_bf16[:2 * P.nsites * r * D].view(P.nsites, 2, r * D)
             A_all = S2[:, 0].reshape(P.nsites, r, D)
             sB_all = (S2[:, 1].float() * L.scaling).to(BF16).view(P.nsites, D, r)                  # scaling B, [D, r] per adapter
             for j in range(3):
@@ -426,6 +490,7 @@ def _packed_lora(model: HunyuanBlocks) -> SimpleNamespace:
                     a = L._plist[f"{mod}.lora_A{dot}.weight"]                                           # [r, D]
                     a3[j * r:(j + 1) * r] = a
                     a3t[:, j * r:(j + 1) * r] = a.t()
+    _pack_ff(model, P, prev is None)
     L._packed_base = base_key
     L._packed, L._packed_version = P, ver
     return P
@@ -477,9 +542,67 @@ def _packed_lora_wide(model: HunyuanBlocks, ver: int) -> SimpleNamespace:
             if dg:
                 for j, a in enumerate(A):
                     P.a3t[mod][:, j * rp:j * rp + r] = a.t()
+    _pack_ff(model, P, prev is None)
     L._packed_base = base_key
     L._packed, L._packed_version = P, ver
     return P
+
+
+def _pack_ff(model: HunyuanBlocks, P: SimpleNamespace, fresh: bool):
+    """the operands of the feed-forward sites (_HYLora.ff), either layout, into P.ff[key].  Per site of in / out widths K / N and ext
+    extension columns, the one adapter in extension columns [0, r):
+      wext [N, K + ext]   the forward operand [W | scaling B | 0]; linear1's MLP rows: [scaling B | 0 | W], its input buffer carries this
+                          site's extension in FRONT of x (the columns behind x belong to the q | k | v product).  fp8="mfma": the extension
+                          columns alone (wb, the bf16 tail of vt_gemm_mxfp8)
+      sbt  [ext, N]       (scaling B)^T, the operand of dt = g (scaling B)
+      wtx  [K, N + ext]   [W^T | A^T | 0], the operand of the input-gradient product over the extended gradient [g | dt] -- the adapter's
+                          dX term sits inside the product, in front of its dGELU / residual epilogue.  fp8_dgrad: the A^T columns alone
+                          (a3t, the bf16 tail of vt_gemm_mxfp8_dx)
+      a    [ext, K]       A over zero rows, the operand of t = x A^T: a bf16 GEMM with N = ext, which writes the extension's zeros too
+                          (at K = 12288 / 15360 it runs at twice the rate of vt_lora_down_wide, whose one block per 64 rows walks all of K)
+    The frozen base columns are kept when only the adapters changed (fresh = False)."""
+    L = model.lora
+    if not L.ff:
+        return
+    r, rpf, ext = L.r, L.rpf, L.ext_ff
+    dev = L.flat_bf16.device
+    mfma = model.fp8 == "mfma"
+    dg = mfma and bool(model.fp8_dgrad)
+    with torch.no_grad():
+        if fresh:
+            P.ff = {}
+            for key, s in L.ff.items():
+                K, N = s.din, s.dout
+                F = SimpleNamespace(wext=None, wtx=None)
+                w = _packed_hy(model).w.get(s.mod + ".weight")             # fp8 mode: the de-quantised E4M3 weight
+                if w is None:
+                    w = model.flat(model.flat_bf16, s.mod + ".weight")
+                w = w[s.row0:s.row0 + N]
+                front = s.tag == "mlp"
+                F.xoff, F.eoff = (ext, 0) if front else (0, K)
+                if mfma:
+                    F.wb = torch.empty(N, ext, dtype=BF16, device=dev)
+                else:
+                    F.wext = torch.empty(N, K + ext, dtype=BF16, device=dev)
+                    F.wext[:, F.xoff:F.xoff + K] = w
+                    F.wb = F.wext[:, F.eoff:F.eoff + ext]
+                F.sbt = torch.empty(ext, N, dtype=BF16, device=dev)
+                if dg:
+                    F.a3t = torch.zeros(K, ext, dtype=BF16, device=dev)
+                else:
+                    F.wtx = torch.zeros(K, N + ext, dtype=BF16, device=dev)
+                    F.wtx[:, :N] = ops.transpose(w)
+                    F.a3t = F.wtx[:, N:]
+                F.a = torch.zeros(ext, K, dtype=BF16, device=dev)
+                P.ff[key] = F
+        for key, s in L.ff.items():
+            F = P.ff[key]
+            a = L._plist[s.a_name]
+            F.a[:r].copy_(a)
+            F.a3t[:, :r] = a.t()
+            b32 = L._plist[s.b_name].float()                               # as _packed_lora_wide: the bf16 compute copy widened (exact)
+            ops.lora_pack_b_wide(b32, F.wb, F.wb.stride(0), 1, s.dout, r, rpf, ext, L.scaling)        # the whole extension, zeros included
+            ops.lora_pack_bt_wide(b32, F.sbt, s.dout, 1, s.dout, r, rpf, ext, L.scaling)
 
 
 class _HYRun(_STRun):
@@ -555,18 +678,26 @@ class _HYRun(_STRun):
         ops.cast_fp8_fmt(g, y, scale, amax)
         return y
 
-    def gate_mul_q(self, g, gate, bs, N, rps, site):
+    def gate_mul_q(self, g, gate, bs, N, rps, site, ext: int = 0):
         """(gg, ggq) = g * gate and its quantised copy for gradient site `site`, in one pass once the site has a history (ggq = None
-        without fp8_dgrad)"""
+        without fp8_dgrad).  ext > 0 (the gradient of an adapted feed-forward Linear): gg is the first N columns of an [M, N + ext]
+        buffer, returned third -- the extended gradient [gg | dt] of ff_rank / ff_dx"""
         M = g.shape[0]
-        gg = self.E(M, N)
+        gge = self.E(M, N + ext) if ext else None
+        gg = gge[:, :N] if ext else self.E(M, N)
+        if ext:
+            return (gg,) + self._gate_mul_q(g, gg, gate, bs, N, rps, site) + (gge,)
+        return (gg,) + self._gate_mul_q(g, gg, gate, bs, N, rps, site)
+
+    def _gate_mul_q(self, g, gg, gate, bs, N, rps, site):
+        M = g.shape[0]
         q = self.gsteady(site) if self.dg else None
         if q is None:
             ops.gate_mul(g, gg, gate, gate, bs, N, rps, 0)
-            return gg, (self.grad_in(site, gg) if self.dg else None)
+            return ((self.grad_in(site, gg) if self.dg else None),)
         ggq = torch.empty(M, N, dtype=self.gdt, device=self.dev)
         ops.gate_mul_fp8(g, gg, gate, gate, bs, N, rps, 0, ggq, q[0], q[1])
-        return gg, ggq
+        return (ggq,)
 
     def dx_gemm(self, gq, site, wname, dx, rows=None, cols=None, **kw):
         """dx = epilogue((gq WqT^T) s_g s_w) on vt_gemm_mxfp8_dx; rows / cols = (lo, hi): that slice of the transposed weight [K_in, N_out]
@@ -579,9 +710,17 @@ class _HYRun(_STRun):
         ops.gemm_mxfp8_dx(gq, wqt, dx, self.gsite(site)[0], sw, **kw)
         return dx
 
-    def dx_dgelu(self, gg, ggq, gsite, usite, wname, du, u, rows=None):
+    def dx_dgelu(self, gg, ggq, gsite, usite, wname, du, u, rows=None, ff=None, gge=None):
         """du = (gg W) * gelu'(u) (rows: that row range of the transposed weight).  fp8_dgrad: from the quantised ggq of site `gsite` on the
-        fp8 matrix cores, returning the quantised du of site `usite` (written by the epilogue once the site has a history); else bf16, None"""
+        fp8 matrix cores, returning the quantised du of site `usite` (written by the epilogue once the site has a history); else bf16, None.
+        ff = the key of an adapted feed-forward Linear whose extended gradient is gge = [gg | dt]: du = (gg W + dt A) * gelu'(u), the
+        adapter's term inside the product (ff_dx)"""
+        if ff is not None:
+            q = self.gsteady(usite) if self.dg else None
+            duq = None if q is None else torch.empty(du.shape[0], du.shape[1], dtype=self.gdt, device=self.dev)
+            kw = {} if q is None else dict(out_fp8=(duq, q[0], q[1]))
+            self.ff_dx(ff, gge, du, ggq, gsite, wname, rows=rows, epilogue=EPI_DGELU, pre_act_in=u, **kw)
+            return self.grad_in(usite, du, duq) if self.dg else None
         if not self.dg:
             wt = self.P.wt[wname]
             ops.gemm(gg, wt if rows is None else wt[rows[0]:rows[1]], du, None, epilogue=EPI_DGELU, pre_act_in=u)
@@ -724,6 +863,53 @@ class _HYRun(_STRun):
             return dxe[:, :D]                                           # a row-strided view
         return y, backward
 
+    # ---- the feed-forward sites (_HYLora.ff, _pack_ff): one adapter each, either layout ----
+    def ff_key(self, key: str):
+        """key when `key` names an adapted feed-forward site, else None"""
+        return key if (self.lora is not None and key in self.lora.ff) else None
+
+    def ff_forward(self, key: str, buf, y, bias, q8=None, **epi):
+        """y = epilogue([x | x A^T] [W | scaling B]^T + bias) for the feed-forward site `key`; buf: the site's input buffer, x in the
+        columns [xoff, xoff + K) and the extension, written here (t = x A^T, zeros past the rank), in [eoff, eoff + ext)
+        (_pack_ff).  q8 = (xq, site, wname, rows): the base product on vt_gemm_mxfp8, the extension as its bf16 tail.  Returns (x, t)."""
+        L, F = self.lora, self.LP.ff[key]
+        s = L.ff[key]
+        K, ext = s.din, L.ext_ff
+        x, t = buf[:, F.xoff:F.xoff + K], buf[:, F.eoff:F.eoff + ext]
+        ops.gemm(x, F.a, t, None)
+        if q8 is not None:
+            xq, site, wname, rows = q8
+            self.mx_gemm(xq, site, wname, y, bias, rows=rows, tail=(t, F.wb), **epi)
+        else:
+            ops.gemm(buf[:, :K + ext], F.wext, y, bias, **epi)
+        return x, t
+
+    def ff_rank(self, key: str, ge, x, t):
+        """the rank side of site `key`'s backward: ge = [g | .] the extended output gradient, x / t the site's input and t = x A^T.
+        dt = g (scaling B) into ge's extension columns, then the adapter's gradients straight into its slices of the flat fp32 gradient
+        (vt_lora_tn_wide: fp32 atomics, nothing staged -- a partial backward touches what it reaches)."""
+        L, F = self.lora, self.LP.ff[key]
+        s = L.ff[key]
+        N = s.dout
+        g, dt = ge[:, :N], ge[:, N:N + L.ext_ff]
+        ops.gemm(g, F.sbt, dt, None)
+        if self.lts is not None:
+            ops.lora_tn_wide(g, t, L.r, L.flat(self.lts.grad, s.b_name), L.r, 1, L.scaling, N)           # dB += scaling g^T t
+            ops.lora_tn_wide(x, dt, L.r, L.flat(self.lts.grad, s.a_name), 1, s.din, 1.0, s.din)          # dA += dt^T x
+
+    def ff_dx(self, key: str, ge, out, gq, gsite, wname, rows=None, cols=None, **epi):
+        """out = epilogue(g W + dt A) of site `key` from the extended gradient ge = [g | dt] (after ff_rank): ONE product over
+        [W^T | A^T], so the adapter's term is in front of a dGELU / residual epilogue; rows = (lo, hi): those input columns (linear2's
+        attention and MLP halves).  fp8_dgrad: g W on vt_gemm_mxfp8_dx from the quantised gq of gradient site `gsite` (cols: linear1's
+        row range of the fp8 weight), dt A as its bf16 tail."""
+        F, N = self.LP.ff[key], self.lora.ff[key].dout
+        lo, hi = rows if rows is not None else (0, F.a3t.shape[0])
+        if self.dg:
+            self.dx_gemm(gq, gsite, wname, out, rows=rows, cols=cols, tail=(ge[:, N:N + self.lora.ext_ff], F.a3t[lo:hi]), **epi)
+        else:
+            ops.gemm(ge[:, :N + self.lora.ext_ff], F.wtx[lo:hi], out, None, **epi)
+        return out
+
     def _lora_scatter_one(self, mod):
         """staging slots of one module -> its adapters' gradients"""
         L, r, D = self.lora, self.lora.r, self.m.hidden_size
@@ -745,7 +931,7 @@ class _HYRun(_STRun):
             self._lora_ran.clear()
             return
         r, D, n3 = L.r, self.m.hidden_size, len(P.mods3)
-        G2 = self.lts.grad.view(P.nsites, 2, r * D)
+        G2 = self.lts.grad[:2 * P.nsites * r * D].view(P.nsites, 2, r * D)
         GA, GB = G2[:, 0].view(P.nsites, r, D), G2[:, 1].view(P.nsites, D, r)
         for j in range(3):
             GB.index_add_(0, P.idx3[j], P.DB3[:, j * D:(j + 1) * D, j * r:(j + 1) * r], alpha=L.scaling)
@@ -810,8 +996,10 @@ class _HYRun(_STRun):
             yv = super().ln_mod(x, shift, scale, bstride, rows_per_sample, dshift, dscale, dbstride)
             return yv if site is None else (yv, None)
         M, D = x.d.shape
-        buf = self.ext(M) if ext else None
-        y = buf[:, :D] if ext else self.E(M, D)
+        # ext = (front, back): extension columns in front of / behind the D columns of y (feed-forward sites; True: the q | k | v extension)
+        front, back = ext if isinstance(ext, tuple) else (0, self.lora.ext_qkv if ext else 0)
+        buf = self.E(M, front + D + back) if ext else None
+        y = buf[:, front:front + D] if ext else self.E(M, D)
         mean, rstd = self.E(M, dt=F32), self.E(M, dt=F32)
         yq = None
         if q is not None:
@@ -839,7 +1027,12 @@ class _HYRun(_STRun):
         M = x.d.shape[0]
         w1, w2 = self.W(pre + "fc1.weight"), self.W(pre + "fc2.weight")
         H4, Dout = w1.shape[0], w2.shape[0]
-        u = self.E(M, H4); ga = self.E(M, H4)
+        # adapted feed-forward sites (LoRA targets ff.net.0.proj / ff.net.2): x lives in an extended buffer (ln_mod ext), ga gets one
+        k1, k2 = self.ff_key(pre + "fc1"), self.ff_key(pre + "fc2")
+        fext = self.lora.ext_ff if (k1 or k2) else 0
+        u = self.E(M, H4)
+        gae = self.E(M, H4 + fext) if k2 else None
+        ga = gae[:, :H4] if k2 else self.E(M, H4)
         y = self.E(M, Dout)
         branch = self.E(M, Dout) if (self.save and dgate is not None) else None          # the pre-gate branch: only d(gate) reads it
         epi2 = dict(epilogue=EPI_GATED_RES, residual=residual.d, gate_txt=gate[0], gate_vid=gate[0], gate_bstride=gate[1], S=gate[2], St=0,
@@ -848,13 +1041,25 @@ class _HYRun(_STRun):
             s1, s2 = sites
             q2 = self.steady(s2)
             gq = None if q2 is None else torch.empty(M, H4, dtype=ops.FP8, device=self.dev)
-            self.mx_gemm(self.fp8_in(s1, x.d, xq), s1, pre + "fc1.weight", ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u,
-                         out_fp8=None if q2 is None else (gq, q2[0], q2[1]))
-            self.mx_gemm(self.fp8_in(s2, ga, gq), s2, pre + "fc2.weight", y, self.W(pre + "fc2.bias"), **epi2)
+            epi1 = dict(epilogue=EPI_BIAS_GELU, pre_act_out=u, out_fp8=None if q2 is None else (gq, q2[0], q2[1]))
+            if k1:
+                self.ff_forward(k1, x.ext, ga, self.W(pre + "fc1.bias"), q8=(self.fp8_in(s1, x.d, xq), s1, pre + "fc1.weight", None), **epi1)
+            else:
+                self.mx_gemm(self.fp8_in(s1, x.d, xq), s1, pre + "fc1.weight", ga, self.W(pre + "fc1.bias"), **epi1)
+            if k2:
+                self.ff_forward(k2, gae, y, self.W(pre + "fc2.bias"), q8=(self.fp8_in(s2, ga, gq), s2, pre + "fc2.weight", None), **epi2)
+            else:
+                self.mx_gemm(self.fp8_in(s2, ga, gq), s2, pre + "fc2.weight", y, self.W(pre + "fc2.bias"), **epi2)
             del gq
         else:
-            ops.gemm(x.d, w1, ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u)
-            ops.gemm(ga, w2, y, self.W(pre + "fc2.bias"), **epi2)
+            if k1:
+                self.ff_forward(k1, x.ext, ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u)
+            else:
+                ops.gemm(x.d, w1, ga, self.W(pre + "fc1.bias"), epilogue=EPI_BIAS_GELU, pre_act_out=u)
+            if k2:
+                self.ff_forward(k2, gae, y, self.W(pre + "fc2.bias"), **epi2)
+            else:
+                ops.gemm(ga, w2, y, self.W(pre + "fc2.bias"), **epi2)
         yv = _Var(y)
         if self.save:
             def bwd_mlp():
@@ -864,16 +1069,25 @@ class _HYRun(_STRun):
                     ops.group_colsum(g_, None, y=branch, out2=dgate, D=Dout, S=gate[2], St=0, grouped=True, o_bstride=gate[1], o_segstride=0)
                 # fp8_dgrad: gated d(fc2 out) and d(u) are quantised by their producers, both dX products run in fp8
                 g2, g1 = gsites if self.dg else (None, None)
-                gg, ggq = self.gate_mul_q(g_, gate[0], gate[1], Dout, gate[2], g2)
+                gge = None
+                if k2:                  # ff.net.2: the extended gradient [gg | dt], the adapter's dX term inside the dGELU product
+                    gg, ggq, gge = self.gate_mul_q(g_, gate[0], gate[1], Dout, gate[2], g2, ext=fext)
+                    self.ff_rank(k2, gge, ga, gae[:, H4:])
+                else:
+                    gg, ggq = self.gate_mul_q(g_, gate[0], gate[1], Dout, gate[2], g2)
                 self.colsum(gg, pre + "fc2.bias", Dout)
                 self.dW(gg, ga, self.G(pre + "fc2.weight"))
-                du = self.E(M, H4)
-                duq = self.dx_dgelu(gg, ggq, g2, g1, pre + "fc2.weight", du, u)
+                due = self.E(M, H4 + fext) if k1 else None
+                du = due[:, :H4] if k1 else self.E(M, H4)
+                duq = self.dx_dgelu(gg, ggq, g2, g1, pre + "fc2.weight", du, u, ff=k2, gge=gge)
                 del ggq
                 self.colsum(du, pre + "fc1.bias", H4)
                 self.dW(du, x.d, self.G(pre + "fc1.weight"))
                 dx = self.E(M, w1.shape[1])
-                if self.dg:
+                if k1:                  # ff.net.0.proj: dx = du W1 + dt A in one product over [du | dt]
+                    self.ff_rank(k1, due, x.d, x.ext[:, w1.shape[1]:])
+                    self.ff_dx(k1, due, dx, duq, g1, pre + "fc1.weight")
+                elif self.dg:
                     self.dx_gemm(duq, g1, pre + "fc1.weight", dx)
                 else:
                     ops.gemm(du, self.P.wt[pre + "fc1.weight"], dx, None)
@@ -1007,7 +1221,7 @@ class _HYRun(_STRun):
             mod, dmod = self.modulation(sv, pre + s + "_mod", 6)
             sl = lambda k, buf=mod: buf[:, k * D:(k + 1) * D]
             dsl = (lambda k, buf=dmod: buf[:, k * D:(k + 1) * D]) if dmod is not None else (lambda k: None)
-            adapted = self.lora is not None and s == "img"
+            adapted = self.lora is not None and self.lora.attn and s == "img"
             qs = site0 + 4 * si                                                     # this stream's qkv / proj / fc1 / fc2 input sites
             if q8:
                 xm, xq = self.ln_mod(x, sl(0), sl(1), bs, L, dsl(0), dsl(1), bs, ext=adapted, site=qs)
@@ -1028,11 +1242,11 @@ class _HYRun(_STRun):
             x, L, off, sl, dsl, qkv, rp, qs = streams[s]
             aq = None
             if q8:                          # this stream's rows of the joint output: the bf16 copy and the e4m3 proj input in one pass
-                ae = self.ext(B * L, proj=True) if (self.lora is not None and s == "img") else None
+                ae = self.ext(B * L, proj=True) if (self.lora is not None and self.lora.attn and s == "img") else None
                 ad = ae[:, :C] if ae is not None else self.E(B * L, C)
                 aq = self.fp8_in(qs + 1, o, copy=ad, rows=(L, Lj, off), M=B * L)
                 av = _XVar(ad, ae) if ae is not None else _Var(ad)
-            elif self.lora is not None and s == "img":                               # input of the adapted projection: extended buffer
+            elif self.lora is not None and self.lora.attn and s == "img":            # input of the adapted projection: extended buffer
                 ae = self.ext(B * L, proj=True)
                 ae.view(B, L, ae.shape[1])[:, :, :C].copy_(o.view(B, Lj, C)[:, off:off + L])
                 av = _XVar(ae[:, :C], ae)
@@ -1048,13 +1262,14 @@ class _HYRun(_STRun):
             x1 = self.glinear(av, pre + s + "_attn_proj.weight", pre + s + "_attn_proj.bias", x, sl(2), dsl(2), L, bs, site=qs + 1, xq=aq,
                                gsite=qs + 1)
             del aq
+            fx = (0, self.lora.ext_ff) if self.ff_key(pre + s + "_mlp.fc1") else False      # ff.net.0.proj: fc1's input in an extended buffer
             if q8:
-                hm, hq = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs, site=qs + 2)
+                hm, hq = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs, ext=fx, site=qs + 2)
                 outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5), sites=(qs + 2, qs + 3), xq=hq,
                                    gsites=(qs + 2, qs + 3))
                 del hq
             else:
-                hm = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs)
+                hm = self.ln_mod(x1, sl(3), sl(4), bs, L, dsl(3), dsl(4), bs, ext=fx)
                 outs[s] = self.mlp(hm, pre + s + "_mlp.", residual=x1, gate=(sl(5), bs, L), dgate=dsl(5))
         return outs["img"], outs["txt"]
 
@@ -1071,30 +1286,42 @@ class _HYRun(_STRun):
         dsl = (lambda k: dmod[:, k * D:(k + 1) * D]) if dmod is not None else (lambda k: None)
         mod1 = pre + "linear1"
         adapted = self.lora is not None and mod1 in self.lora.sites
+        # adapted feed-forward sites (LoRA targets proj_mlp / proj_out).  linear1's input feeds two products: the buffer is
+        # [MLP adapter's extension | x | q, k, v extension], so that each product reads a contiguous [x | its own extension]
+        k1, k2 = self.ff_key(mod1 + "#mlp"), self.ff_key(pre + "linear2")
+        fext = self.lora.ext_ff if (k1 or k2) else 0
+        front = fext if k1 else 0
+        xext = (front, self.lora.ext_qkv if adapted else 0) if (k1 or adapted) else False
         q8 = self.q8
         xq = catq = None
         if q8:
-            xm, xq = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=adapted, site=site0)
+            xm, xq = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=xext, site=site0)
             xq = self.fp8_in(site0, xm.d, xq)
         else:
-            xm = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=adapted)
+            xm = self.ln_mod(x, sl(0), sl(1), bs, Lj, dsl(0), dsl(1), bs, ext=xext)
         w1, b1 = self.W(pre + "linear1.weight"), self.W(pre + "linear1.bias")
         qkv = self.E(M, 3 * D)
         bw1 = None
         if adapted:
-            qkv, bw1 = self.lora_linear(xm.ext, mod1, b1[:3 * D], y=qkv, q8=(xq, site0, pre + "linear1.weight", (0, 3 * D)) if q8 else None)
+            qkv, bw1 = self.lora_linear(xm.ext[:, front:], mod1, b1[:3 * D], y=qkv, q8=(xq, site0, pre + "linear1.weight", (0, 3 * D)) if q8 else None)
         elif q8:
             self.mx_gemm(xq, site0, pre + "linear1.weight", qkv, b1[:3 * D], rows=(0, 3 * D))
         else:
             ops.gemm(xm.d, w1[:3 * D], qkv, b1[:3 * D])
-        cat = self.E(M, D + M4)                                  # [attn | gelu(mlp)], read by linear2
+        cate = self.E(M, D + M4 + fext) if k2 else None          # proj_out: linear2's input with its extension columns
+        cat = cate[:, :D + M4] if k2 else self.E(M, D + M4)      # [attn | gelu(mlp)], read by linear2
         u = self.E(M, M4)
         if q8:                                                   # the GELU epilogue writes its columns of linear2's e4m3 input
             q2 = self.steady(site0 + 1)
             catq = None if q2 is None else torch.empty(M, D + M4, dtype=ops.FP8, device=self.dev)
-            self.mx_gemm(xq, site0, pre + "linear1.weight", cat[:, D:], b1[3 * D:], rows=(3 * D, 3 * D + M4), epilogue=EPI_BIAS_GELU,
-                         pre_act_out=u, out_fp8=None if q2 is None else (catq[:, D:], q2[0], q2[1]))
+            epi1 = dict(epilogue=EPI_BIAS_GELU, pre_act_out=u, out_fp8=None if q2 is None else (catq[:, D:], q2[0], q2[1]))
+            if k1:
+                self.ff_forward(k1, xm.ext, cat[:, D:], b1[3 * D:], q8=(xq, site0, pre + "linear1.weight", (3 * D, 3 * D + M4)), **epi1)
+            else:
+                self.mx_gemm(xq, site0, pre + "linear1.weight", cat[:, D:], b1[3 * D:], rows=(3 * D, 3 * D + M4), **epi1)
             del xq
+        elif k1:
+            self.ff_forward(k1, xm.ext, cat[:, D:], b1[3 * D:], epilogue=EPI_BIAS_GELU, pre_act_out=u)
         else:
             ops.gemm(xm.d, w1[3 * D:], cat[:, D:], b1[3 * D:], epilogue=EPI_BIAS_GELU, pre_act_out=u)
         qkvv = _Var(qkv)
@@ -1103,7 +1330,7 @@ class _HYRun(_STRun):
         catv = _Var(cat)
         if self.save:
             def bwd_linear1():
-                du = catv.g[:, D:]                               # bwd_linear2 left d u = (g W2[:, D:]) * gelu'(u) in the mlp columns
+                du = catv.g[:, D:D + M4]                         # bwd_linear2 left d u = (g W2[:, D:]) * gelu'(u) in the mlp columns
                 dqkv = qkvv.g
                 if self.ts is not None:
                     gw, gb = self.G(pre + "linear1.weight"), self.G(pre + "linear1.bias")
@@ -1120,7 +1347,11 @@ class _HYRun(_STRun):
                     else:
                         ops.gemm(dqkv, self._wt_rows(pre + "linear1.weight", 0, 3 * D), dx, None)
                 dx2 = self.E(M, D)
-                if self.dg:
+                if k1:                           # proj_mlp: dx2 = dx + du W1[3D:] + dt A over the extended gradient [du | dt]
+                    self.ff_rank(k1, catv.g[:, D:], xm.d, xm.ext[:, :front])
+                    self.ff_dx(k1, catv.g[:, D:], dx2, duq, gsite0 + 2, pre + "linear1.weight", cols=(3 * D, 3 * D + M4),
+                               epilogue=EPI_GATED_RES, residual=dx)
+                elif self.dg:
                     self.dx_gemm(duq, gsite0 + 2, pre + "linear1.weight", dx2, cols=(3 * D, 3 * D + M4), epilogue=EPI_GATED_RES, residual=dx)
                 else:
                     ops.gemm(du, self._wt_rows(pre + "linear1.weight", 3 * D, 3 * D + M4), dx2, None, epilogue=EPI_GATED_RES, residual=dx)
@@ -1136,8 +1367,14 @@ class _HYRun(_STRun):
         if q8:
             if catq is not None:                                 # the attention columns: one cast pass
                 ops.cast_fp8_scaled(cat[:, :D], catq[:, :D], *self.qsite(site0 + 1))
-            self.mx_gemm(self.fp8_in(site0 + 1, cat, catq), site0 + 1, pre + "linear2.weight", y, self.W(pre + "linear2.bias"), **epi2)
+            if k2:
+                self.ff_forward(k2, cate, y, self.W(pre + "linear2.bias"), q8=(self.fp8_in(site0 + 1, cat, catq), site0 + 1, pre + "linear2.weight", None),
+                                **epi2)
+            else:
+                self.mx_gemm(self.fp8_in(site0 + 1, cat, catq), site0 + 1, pre + "linear2.weight", y, self.W(pre + "linear2.bias"), **epi2)
             del catq
+        elif k2:
+            self.ff_forward(k2, cate, y, self.W(pre + "linear2.bias"), **epi2)
         else:
             ops.gemm(cat, w2, y, self.W(pre + "linear2.bias"), **epi2)
         yv = _Var(y)
@@ -1147,16 +1384,23 @@ class _HYRun(_STRun):
                 self.acc(x, g_)
                 if dmod is not None:
                     ops.group_colsum(g_, None, y=branch, out2=dsl(2), D=D, S=Lj, St=0, grouped=True, o_bstride=bs, o_segstride=0)
-                gg, ggq = self.gate_mul_q(g_, sl(2), bs, D, Lj, gsite0)
+                gge = None
+                if k2:                           # proj_out: the extended gradient [gg | dt]; both halves of d(cat) carry dt A
+                    gg, ggq, gge = self.gate_mul_q(g_, sl(2), bs, D, Lj, gsite0, ext=fext)
+                    self.ff_rank(k2, gge, cat, cate[:, D + M4:])
+                else:
+                    gg, ggq = self.gate_mul_q(g_, sl(2), bs, D, Lj, gsite0)
                 self.colsum(gg, pre + "linear2.bias", D)
                 self.dW(gg, cat, self.G(pre + "linear2.weight"))
-                dcat = self.E(M, D + M4)
-                if self.dg:                      # linear2's two column ranges are row slices of its transposed fp8 weight
+                dcat = self.E(M, D + M4 + (fext if k1 else 0))       # proj_mlp: d u with its extension columns (bwd_linear1)
+                if k2:
+                    self.ff_dx(k2, gge, dcat[:, :D], ggq, gsite0, pre + "linear2.weight", rows=(0, D))              # d attn
+                elif self.dg:                    # linear2's two column ranges are row slices of its transposed fp8 weight
                     self.dx_gemm(ggq, gsite0, pre + "linear2.weight", dcat[:, :D], rows=(0, D))                     # d attn
                 else:
                     ops.gemm(gg, self.P.wt[pre + "linear2.weight"][:D], dcat[:, :D], None)
                 # d u = (g W2[:, D:]) * gelu'(u) into the mlp columns (fp8_dgrad: with its quantised copy for linear1's product)
-                catv.gq = self.dx_dgelu(gg, ggq, gsite0, gsite0 + 2, pre + "linear2.weight", dcat[:, D:], u, rows=(D, D + M4))
+                catv.gq = self.dx_dgelu(gg, ggq, gsite0, gsite0 + 2, pre + "linear2.weight", dcat[:, D:D + M4], u, rows=(D, D + M4), ff=k2, gge=gge)
                 catv.g = dcat
                 ov.g = dcat[:, :D]
             self.tape.append(bwd_linear2)
@@ -1239,7 +1483,8 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  mm_single_blocks_depth: int = 40, rope_dim_list=(16, 56, 56), qkv_bias: bool = True, qk_norm: bool = True, qk_norm_type: str = "rms",
                  guidance_embed: bool = False, text_projection: str = "single_refiner", use_attention_mask: bool = True,
                  text_states_dim: Optional[int] = None, text_states_dim_2: Optional[int] = None, fp8: bool = False, lora_rank: int = 0,
-                 lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, fp8_dgrad=False, **unused):
+                 lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, fp8_dgrad=False, lora_target_modules=None,
+                 **unused):
         if text_projection != "single_refiner" or mlp_act_type != "gelu_tanh" or not qkv_bias or not qk_norm or qk_norm_type != "rms":
             raise NotImplementedError("only the shipped HunyuanVideo-T2V configuration (single_refiner, gelu_tanh, rms qk-norm) is built")
         if sum(rope_dim_list) != hidden_size // heads_num:
@@ -1271,7 +1516,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  "final_layer.adaLN_modulation.1.weight": (2 * D, D), "final_layer.adaLN_modulation.1.bias": (2 * D,)}
         super().__init__(hidden_size, heads_num, mlp_width_ratio, mm_double_blocks_depth, mm_single_blocks_depth, fp8, lora_rank, lora_alpha,
                          shapes_before=before, shapes_after=after, fp8_amax_history=fp8_amax_history,
-                         fp8_dgrad=fp8_dgrad)
+                         fp8_dgrad=fp8_dgrad, lora_target_modules=lora_target_modules)
         self.patch_size, self.in_channels, self.out_channels, self.guidance_embed = tuple(patch_size), in_channels, oc, guidance_embed
         self.text_states_dim, self.text_states_dim_2 = td, td2
 
