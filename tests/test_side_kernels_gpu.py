@@ -357,11 +357,12 @@ def test_silu(dev, n):
     close(got[:n], x.double() * torch.sigmoid(x.double()), 1e-2, 1e-3, "silu")
 
 
-@pytest.mark.parametrize("n", [1, 70001])
+@pytest.mark.parametrize("n", [1, 70001, 2 * 2097152 + 77])
 def test_cast_f32_bf16_is_round_to_nearest_even(dev, n):
     """bit for bit x.to(bfloat16): randn * 3 and the edge values; 4000 exact ties (low half 0x8000 under random even and odd
     upper halves over the whole normal range, both signs); their neighbours 0x7FFF / 0x8001; and values that round up into the
-    next binade (upper half 0x..7F / 0x..FF with the low half >= 0x8000, e.g. 0x3FFFFFFF -> 2.0)."""
+    next binade (upper half 0x..7F / 0x..FF with the low half >= 0x8000, e.g. 0x3FFFFFFF -> 2.0).
+    n = 2 * 2097152 + 77 is two sweeps of the capped grid (8192 workgroups x 256 threads) and 77 elements of a third."""
     from vt355 import ops
     x = _act_input(n, 8)
     g = torch.Generator().manual_seed(80)

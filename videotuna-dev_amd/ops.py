@@ -102,6 +102,35 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.dim() == 2 else t.stride(-2)
 
 
+# The glue kernels take their extents from ONE operand and trust the others to be at least as large; the checks below refuse, before
+# any launch, an operand smaller than what the launch will touch (a short output is written past its end otherwise).
+def _rows_cols(t: torch.Tensor, rows: int, cols: int, name: str, fn: str):
+    if t.shape[0] < rows or t.shape[1] < cols:
+        raise ValueError(f"{fn}: {name} {tuple(t.shape)} is smaller than the [{rows}, {cols}] the launch touches")
+
+
+def _numel(t: Optional[torch.Tensor], n: int, name: str, fn: str):
+    if t is not None and t.numel() < n:
+        raise ValueError(f"{fn}: {name} holds {t.numel()} elements, the launch touches {n}")
+
+
+def _span(t: torch.Tensor) -> int:
+    """elements from t's first to its last, in memory"""
+    return 0 if t.numel() == 0 else 1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+
+
+def _loss_operands(fn, vpred, noisy, x0, sa, sb, w, dvpred):
+    n, B = x0.numel(), x0.shape[0]
+    _numel(vpred, n, "vpred", fn); _numel(noisy, n, "noisy", fn); _numel(dvpred, n, "dvpred", fn)
+    _numel(sa, B, "sa", fn); _numel(sb, B, "sb", fn); _numel(w, B, "w", fn)
+
+
+def _patch_rows(img, tok, P: int, fn: str):
+    B, F, C, H, W = img.shape
+    if P > 0 and H % P == 0 and W % P == 0 and tok.shape[0] != B * F * (H // P) * (W // P):      # the library refuses any other P
+        raise ValueError(f"{fn}: tok has {tok.shape[0]} rows, img {tuple(img.shape)} at P={P} has {B * F * (H // P) * (W // P)} tokens")
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
          epilogue: int = EPI_BIAS, residual: Optional[torch.Tensor] = None, r_mod: int = 0,
          gate_txt: Optional[torch.Tensor] = None, gate_vid: Optional[torch.Tensor] = None, gate_bstride: int = 0,
@@ -540,6 +569,13 @@ def qk_layernorm_bwd(dq_hat_f32, dk_hat, qkv, mean, rstd, gq, gk, dqkv, H: int, 
 
 def gate_mul(x, y, g_txt, g_vid, bstride: int, D: int, S: int, St: int):
     _req(x, BF16, "x", 2); _req(y, BF16, "y", 2)
+    M = x.shape[0]
+    _rows_cols(x, M, D, "x", "gate_mul"); _rows_cols(y, M, D, "y", "gate_mul")
+    if S > 0 and D > 0 and M > 0:
+        need = ((M + S - 1) // S - 1) * bstride + D          # the last sample's gate row ends here
+        for nm, g in (("g_txt", g_txt), ("g_vid", g_vid)):
+            if g.dtype != torch.float32 or _span(g) < need or (g.dim() > 1 and g.shape[-1] < D):
+                raise ValueError(f"gate_mul: {nm} {tuple(g.shape)} ({g.dtype}) does not hold {need} fp32 gate elements at bstride {bstride}")
     lib = load_library()
     check(lib.vt_gate_mul(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), g_txt.data_ptr(), g_vid.data_ptr(), bstride,
                           x.shape[0], D, S, St, _stream()), "vt_gate_mul")
@@ -564,12 +600,14 @@ def timestep_embedding(t, out, flip: bool = True, freq_shift: float = 0.0):
 def patchify(img, tok, P: int):
     _req(img, BF16, "img", 5); _req(tok, BF16, "tok", 2)
     B, F, C, H, W = img.shape
+    _patch_rows(img, tok, P, "patchify")
     check(load_library().vt_patchify(img.data_ptr(), tok.data_ptr(), B, F, C, H, W, P, tok.stride(0), _stream()), "vt_patchify")
 
 
 def unpatchify(tok, img, P: int):
     _req(img, BF16, "img", 5); _req(tok, BF16, "tok", 2)
     B, F, C, H, W = img.shape
+    _patch_rows(img, tok, P, "unpatchify")
     check(load_library().vt_unpatchify(tok.data_ptr(), img.data_ptr(), B, F, C, H, W, P, tok.stride(0), _stream()),
           "vt_unpatchify")
 
@@ -577,6 +615,8 @@ def unpatchify(tok, img, P: int):
 def add_noise(x0, noise, sa, sb, noisy):
     _req(x0, torch.float32, "x0"); _req(noise, torch.float32, "noise"); _req(noisy, BF16, "noisy")
     B = x0.shape[0]
+    _numel(noise, x0.numel(), "noise", "add_noise"); _numel(noisy, x0.numel(), "noisy", "add_noise")
+    _numel(sa, B, "sa", "add_noise"); _numel(sb, B, "sb", "add_noise")
     check(load_library().vt_add_noise(x0.data_ptr(), noise.data_ptr(), sa.data_ptr(), sb.data_ptr(), noisy.data_ptr(),
                                       x0.numel() // B, B, _stream()), "vt_add_noise")
 
@@ -584,6 +624,8 @@ def add_noise(x0, noise, sa, sb, noisy):
 def diffusion_loss(vpred, noisy, x0, sa, sb, w, loss, partials, dvpred, grad_scale: float = 1.0):
     _req(vpred, BF16, "vpred"); _req(noisy, BF16, "noisy"); _req(x0, torch.float32, "x0")
     B = x0.shape[0]
+    _loss_operands("diffusion_loss", vpred, noisy, x0, sa, sb, w, dvpred)
+    _numel(loss, 1, "loss", "diffusion_loss"); _numel(partials, 512, "partials", "diffusion_loss")
     check(load_library().vt_diffusion_loss(vpred.data_ptr(), noisy.data_ptr(), x0.data_ptr(), sa.data_ptr(), sb.data_ptr(),
                                            w.data_ptr(), loss.data_ptr(), partials.data_ptr(), _p(dvpred),
                                            x0.numel() // B, B, grad_scale, _stream()), "vt_diffusion_loss")
@@ -592,6 +634,8 @@ def diffusion_loss(vpred, noisy, x0, sa, sb, w, loss, partials, dvpred, grad_sca
 def diffusion_loss_bwd(vpred, noisy, x0, sa, sb, w, grad_out, dvpred):
     _req(grad_out, torch.float32, "grad_out")
     B = x0.shape[0]
+    _loss_operands("diffusion_loss_bwd", vpred, noisy, x0, sa, sb, w, dvpred)
+    _numel(grad_out, 1, "grad_out", "diffusion_loss_bwd")
     check(load_library().vt_diffusion_loss_bwd(vpred.data_ptr(), noisy.data_ptr(), x0.data_ptr(), sa.data_ptr(), sb.data_ptr(),
                                                w.data_ptr(), grad_out.data_ptr(), dvpred.data_ptr(), x0.numel() // B, B,
                                                _stream()), "vt_diffusion_loss_bwd")
@@ -1072,6 +1116,7 @@ def dropout(x, y, p: float, seed: int, offset: int = 0, mask_out=None):
     """y = keep ? x / (1 - p) : 0 on bf16 rows [M, C] (y may alias x); keep is a pure function of (seed, offset, element index): the
     backward pass is the same call on the gradient.  mask_out: uint8 [M, C] keep flags (tests)."""
     _req(x, BF16, "x", 2); _req(y, BF16, "y", 2)
+    _rows_cols(y, x.shape[0], x.shape[1], "y", "dropout")
     if mask_out is not None and (mask_out.dtype != torch.uint8 or not mask_out.is_contiguous() or tuple(mask_out.shape) != tuple(x.shape)):
         raise ValueError("mask_out must be a contiguous uint8 tensor of x's shape")
     check(load_library().vt_dropout_bf16(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), x.shape[0], x.shape[1], float(p),
@@ -1080,11 +1125,17 @@ def dropout(x, y, p: float, seed: int, offset: int = 0, mask_out=None):
 
 def geglu_fwd(h, y):
     _req(h, BF16, "h", 2); _req(y, BF16, "y", 2)
+    if h.shape[1] != 2 * y.shape[1]:
+        raise ValueError(f"geglu_fwd: h {tuple(h.shape)} is not (a | gate) of twice y's width {y.shape[1]}")
+    _rows_cols(y, h.shape[0], y.shape[1], "y", "geglu_fwd")
     check(load_library().vt_geglu_fwd(h.data_ptr(), h.stride(0), y.data_ptr(), y.stride(0), h.shape[0], y.shape[1], _stream()), "vt_geglu_fwd")
 
 
 def geglu_bwd(dy, h, dh):
     _req(h, BF16, "h", 2); _req(dy, BF16, "dy", 2); _req(dh, BF16, "dh", 2)
+    if h.shape[1] != 2 * dy.shape[1]:
+        raise ValueError(f"geglu_bwd: h {tuple(h.shape)} is not (a | gate) of twice dy's width {dy.shape[1]}")
+    _rows_cols(dy, h.shape[0], dy.shape[1], "dy", "geglu_bwd"); _rows_cols(dh, h.shape[0], h.shape[1], "dh", "geglu_bwd")
     check(load_library().vt_geglu_bwd(dy.data_ptr(), dy.stride(0), h.data_ptr(), h.stride(0), dh.data_ptr(), dh.stride(0), h.shape[0],
                                       dy.shape[1], _stream()), "vt_geglu_bwd")
 
@@ -1092,6 +1143,7 @@ def geglu_bwd(dy, h, dh):
 def add_rows(a, b, out):
     """out = a + b on 2-d bf16 row views (out may be a or b)"""
     _req(a, BF16, "a", 2); _req(b, BF16, "b", 2); _req(out, BF16, "out", 2)
+    _rows_cols(b, a.shape[0], a.shape[1], "b", "add_rows"); _rows_cols(out, a.shape[0], a.shape[1], "out", "add_rows")
     check(load_library().vt_add_rows_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), a.shape[0],
                                           a.shape[1], _stream()), "vt_add_rows_bf16")
 
@@ -1110,12 +1162,15 @@ def row_map(src, out, mode: int, nb: int, d1: int, d2: int, accumulate: bool = F
 def q_sample(x0, noise, sa, sb, scale, xt):
     _req(x0, torch.float32, "x0"); _req(noise, torch.float32, "noise"); _req(xt, BF16, "xt")
     B = x0.shape[0]
+    _numel(noise, x0.numel(), "noise", "q_sample"); _numel(xt, x0.numel(), "xt", "q_sample")
+    _numel(sa, B, "sa", "q_sample"); _numel(sb, B, "sb", "q_sample"); _numel(scale, B, "scale", "q_sample")
     check(load_library().vt_q_sample(x0.data_ptr(), noise.data_ptr(), sa.data_ptr(), sb.data_ptr(), _p(scale), xt.data_ptr(),
                                      x0.numel() // B, B, _stream()), "vt_q_sample")
 
 
 def mse_loss(pred, target, loss, dpred=None, grad_scale: float = 1.0):
     _req(pred, BF16, "pred"); _req(target, torch.float32, "target"); _req(loss, torch.float32, "loss")
+    _numel(target, pred.numel(), "target", "mse_loss"); _numel(dpred, pred.numel(), "dpred", "mse_loss"); _numel(loss, 1, "loss", "mse_loss")
     check(load_library().vt_mse_loss(pred.data_ptr(), target.data_ptr(), loss.data_ptr(), _p(dpred), pred.numel(), grad_scale, _stream()),
           "vt_mse_loss")
 
