@@ -331,6 +331,44 @@ int vt_lora_up_add_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const 
 int vt_lora_up_add_wide_dgelu_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
                                    const void* U, int ldu, long long M, int K, float p, unsigned long long seed, int site0, void* stream);
 
+/* The wide _drop products with an ORIGIN MAP (_at): the call's operand is a piece -- some rows, a column range -- of the adapter's
+ * logical input [M_g, K_log], and the mask is keyed by the element's place in THAT array, e = m_g * K_log + k_g:
+ *   rows     b = m / seg_local, l = m % seg_local,  m_g = b * seg_global + l + (l < n_first ? off_first : off_rest)
+ *   columns  k_g = k0 + k
+ * (seg_local = seg_global >= M, n_first = off_first = off_rest = k0 = 0, K_log = K is the identity: the plain _drop entry point, which is
+ * the same kernel and returns the same bits.)  VT_ERR_BAD_SHAPE before any launch when k0 % 8 != 0, k0 + K > K_log, K_log % 4 != 0,
+ * seg_local <= 0, n_first > seg_local, an offset (or seg_global, n_first) is negative, or the largest e / 4 reaches 2^36 (the next
+ * site's counters).  Everything else is the sibling's.
+ *
+ * HunyuanVideo mask convention (vt355.hunyuan, lora_dropout > 0; a statement of record):
+ *   site     adapter site s = the 0-based position of the adapter among the lora_A entries of model.lora.shapes (the q, k, v adapters of
+ *            a fused projection are consecutive sites, as the multi-adapter kernels number them: site0 + j)
+ *   keep     element (m_g, k) of an adapter's logical input [M_g, K] (K = D, 4 D or 5 D), e = m_g * K + k, is kept iff word e % 4 of
+ *            Philox4x32-10(key = seed, counter = (s << 36) + e / 4) >= floor(p * 2^32): vt_dropout_bf16's rule;
+ *            oracle/philox.py: dropout_keep_mask(M_g, K, p, seed, offset = s << 36) is the same mask
+ *   rows     m_g is the row in the UNSHARDED run's row space of that Linear's input: double-block sites b * Li + l over the image
+ *            rows; single-block sites b * (Li + Lt) + l, image rows first, then text rows.  Under Ulysses sequence parallelism a
+ *            rank's rows are its contiguous 1/P of the image rows followed by the replicated text rows; the origin map puts them
+ *            back (seg_local = Li / P [+ Lt], seg_global = Li [+ Lt], n_first = Li / P, off_first = rank * Li / P, off_rest =
+ *            Li - Li / P), so a P-rank run draws the unsharded run's masks.  All ranks of a group use one seed.
+ *   columns  linear2's input gradient is produced in two column ranges of its [M, 5 D] input: k0 = 0 (attention half, K = D) and
+ *            k0 = D (MLP half, K = 4 D, the dgelu form), both with K_log = 5 D. */
+int vt_lora_down_wide_drop_at(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T, int ldt,
+                              long long M, int K, float p, unsigned long long seed, int site0, long long seg_local, long long seg_global,
+                              long long n_first, long long off_first, long long off_rest, int k0, int K_log, void* stream);
+int vt_lora_tn_wide_drop_at(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
+                            float alpha, long long M, int P, float p, unsigned long long seed, int site, long long seg_local,
+                            long long seg_global, long long n_first, long long off_first, long long off_rest, int k0, int K_log,
+                            void* stream);                       /* Big = columns k0 .. k0 + P of the logical input; one adapter */
+int vt_lora_up_add_wide_drop_at(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                long long M, int K, float p, unsigned long long seed, int site0, long long seg_local,
+                                long long seg_global, long long n_first, long long off_first, long long off_rest, int k0, int K_log,
+                                void* stream);                   /* dX, A = columns k0 .. k0 + K of the logical input / of the adapters */
+int vt_lora_up_add_wide_dgelu_drop_at(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
+                                      const void* U, int ldu, long long M, int K, float p, unsigned long long seed, int site0,
+                                      long long seg_local, long long seg_global, long long n_first, long long off_first,
+                                      long long off_rest, int k0, int K_log, void* stream);   /* U = the same columns of the pre-activation */
+
 /* DoRA (peft 0.12 LoraConfig(use_dora=True), DoraLinearLayer without dropout): y = b + c (x) (W x + s B A x), c_j = m_j / norm_j,
  * norm_j = ||W_j + s (B A)_j||_2 detached.  c is folded into the packed operands once per adapter version (csrc/dora.hip).
  * vt_dora_norm: out[j] = norm_j (mag == NULL) or mag[j] / norm_j, j < n_adapters * d_out; W bf16 [n_adapters d_out, K] (row stride ldw),

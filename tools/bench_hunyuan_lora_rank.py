@@ -16,6 +16,13 @@ HBM of its blocks (the other ranks' packed operands are resident and counted) an
 "<targets>/<rank>", deltas against the first variant.
 
     python tools/bench_hunyuan_lora_rank.py --targets attn,attn+ff --ranks 4,64 --modes bf16,mfma,mfma+dgrad > profiles/hunyuan_lora_ff_step.json
+
+``--lora-dropout P`` adds dropout as an axis: per (target set, rank) the variants ``p0`` (lora_dropout 0 in the layout the rank takes by
+itself), ``p0-wide`` (lora_dropout 0 in the wide layout, as VT355_LORA_WIDE=1 gives it; the same variant where the rank is wide anyway)
+and ``pP`` (lora_dropout P, which takes the wide layout at every rank), alternating like the ranks.  The result then carries, per
+rank, the layout switch (p0-wide against p0) and the dropout delta against p0-wide -- two separate costs.  Not with fp8_dgrad.
+
+    python tools/bench_hunyuan_lora_rank.py --ranks 4,64 --modes bf16,mfma --lora-dropout 0.1 > profiles/hunyuan_lora_dropout_step.json
 """
 import argparse
 import json
@@ -40,6 +47,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--lora-dropout", type=float, default=0.0, help="p > 0: the variants p0 / p0-wide / pP per rank")
     ap.add_argument("--layers", type=int, default=30, help="debug only; anything but 30 is not the benchmark's model")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
@@ -57,15 +65,22 @@ def main():
     if len(tsets) > 1 and ("ff" in tsets or tsets[0] != "attn"):
         raise SystemExit("--targets: several sets share one weight pack -- put attn first, and run ff in a process of its own")
     ranks = [(tg, int(v)) for tg in tsets for v in args.ranks.split(",")]
-    name = lambda k: f"{k[0]}/{k[1]}" if keyed else str(k[1])
+    name = lambda k: (f"{k[0]}/{k[1]}" if keyed else str(k[1])) + (f"/{k[2]}" if len(k) > 2 else "")
+    pd = args.lora_dropout
+    if pd > 0:                                   # (target set, rank, dropout variant)
+        ranks = [k + (v,) for k in ranks for v in ("p0", "p0-wide", f"p{pd:g}")]
     nd, ns = (20, 40) if args.layers == 30 else (max(1, args.layers // 3), max(1, args.layers - args.layers // 3))
     lT, lH, lW, Lt, B = 5, 68, 120, 256, 1
     model = HYVideoDiffusionTransformer(mm_double_blocks_depth=nd, mm_single_blocks_depth=ns, lora_rank=ranks[0][1]).to(dev).init_weights(11)
     flow = HunyuanVideoFlow(model=model, learning_rate=1e-5).to(dev)
     runs = {}
     for key in ranks:
-        tg, r = key
-        L = _HYLora(model.hidden_size, nd, ns, r, 1.0, model.ratio, TARGETS[tg]).to(dev)
+        tg, r = key[:2]
+        var = key[2] if len(key) > 2 else "p0"
+        if var == "p0-wide":
+            os.environ["VT355_LORA_WIDE"] = "1"          # read at construction
+        L = _HYLora(model.hidden_size, nd, ns, r, 1.0, model.ratio, TARGETS[tg], dropout=pd if var not in ("p0", "p0-wide") else 0.0).to(dev)
+        os.environ.pop("VT355_LORA_WIDE", None)
         L.init_weights(12, zero_b=False)
         model.lora = L
         ts = model.enable_lora_training()
@@ -123,10 +138,19 @@ def main():
         for r in ranks:
             res[name(r)][f"delta_vs_{first}_ms"] = res[name(r)]["ms_per_step_median"] - ref
             res[name(r)][f"delta_vs_{first}_pct"] = 100.0 * (res[name(r)]["ms_per_step_median"] - ref) / ref
+        if pd > 0:                                  # the layout switch and dropout, each against its own baseline
+            for k in ranks:
+                if k[2] == "p0":
+                    n0, nw, nd_ = res[name(k)], res[name(k[:2] + ("p0-wide",))], res[name(k[:2] + (f"p{pd:g}",))]
+                    m0, mw, md = (x["ms_per_step_median"] for x in (n0, nw, nd_))
+                    nw["layout_switch_vs_p0_ms"], nw["layout_switch_vs_p0_pct"] = mw - m0, 100.0 * (mw - m0) / m0
+                    nd_["dropout_delta_vs_p0_wide_ms"], nd_["dropout_delta_vs_p0_wide_pct"] = md - mw, 100.0 * (md - mw) / mw
+                    nd_["dropout_delta_beyond_spread"] = abs(md - mw) > max(nw["spread_ms"], nd_["spread_ms"])
         out[mode] = res
     print(json.dumps({"workload": f"HunyuanVideo-T2V denoiser ({nd} + {ns} blocks), latents 16x{lT}x{lH}x{lW}, {lT * (lH // 2) * (lW // 2)} image + "
                                   f"{Lt} text tokens, micro-batch {B}, LoRA target sets {tsets}, HunyuanVideoFlow.training_step + AdamW",
-                      "rounds": args.rounds, "steps_per_block": args.steps, "warmup": args.warmup, "modes": out}), flush=True)
+                      "rounds": args.rounds, "steps_per_block": args.steps, "warmup": args.warmup,
+                      **({"lora_dropout": pd} if pd > 0 else {}), "modes": out}), flush=True)
 
 
 if __name__ == "__main__":

@@ -21,6 +21,13 @@ launched once per round for --rounds rounds in one process (alternating, HIP-eve
     (the bf16 tail), against the same product with Kt = 0 plus the MFMA work the tail adds: Kt / K in bf16, 2 Kt / K in fp8.
 
     python tools/kbench_hunyuan_lora_wide.py --ff [--rounds 20] > profiles/hunyuan_lora_ff_kbench.txt
+
+``--drop P``: instead, the origin-map (_at) dropped rank-side kernels of lora_dropout = P at M = 10 456 (a single block's rows of one
+rank of a two-rank sequence-parallel run: 5 100 image + 256 text rows ... the map is not the identity) and K in {3072, 12288, 15360},
+ranks 4 and 64, one adapter (the feed-forward sites) and, at K = 3072, three (the fused q | k | v projection): each _at kernel is
+launched right after its undropped sibling -- down, tn (dA), up_add, and the dgelu form of up_add against the undropped up_add.
+
+    python tools/kbench_hunyuan_lora_wide.py --drop 0.1 [--rounds 20] > profiles/hunyuan_lora_dropout_kbench.txt
 """
 import argparse
 import os
@@ -36,6 +43,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--M", type=int, default=10456)
     ap.add_argument("--ff", action="store_true", help="the feed-forward targets' kernels instead of the attention sites' tails")
+    ap.add_argument("--drop", type=float, default=0.0, help="p > 0: the dropped _at rank-side kernels next to their undropped siblings")
     args = ap.parse_args()
     sys.path.insert(0, ROOT)
     import torch
@@ -50,6 +58,8 @@ def main():
     print(f"# M {M}, K {K}; median / spread (max - min) over {args.rounds} alternating launches, microseconds")
     if args.ff:
         return ff_kernels(args, torch, ops, dev)
+    if args.drop > 0:
+        return drop_kernels(args, torch, ops, dev)
     for N in (9216, 3072):
         aq, sa = ops.quantize_fp8(rnd(M, K).to(BF))
         wq, sw = ops.quantize_fp8(rnd(N, K, sc=K ** -0.5).to(BF))
@@ -182,6 +192,61 @@ def ff_kernels(args, torch, ops, dev):
             print(f"{Kt:>4} | {bm:8.1f} / {bs:5.1f} | {ob:7.1f} {100 * ob / res[('bf16', 0)][0]:5.1f}% | {100.0 * Kt / K:9.1f}% | "
                   f"{qm:8.1f} / {qs:5.1f} | {oq:7.1f} {100 * oq / res[('fp8', 0)][0]:5.1f}% | {200.0 * Kt / K:9.1f}%")
         del xe, we, aq, wq, gq, y, u, variants
+
+
+def drop_kernels(args, torch, ops, dev):
+    BF, M, p, seed = torch.bfloat16, args.M, args.drop, 20230211
+    gen = torch.Generator(device=dev).manual_seed(5)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, device=dev, generator=gen) * sc)
+    KS = (3072, 12288, 15360)
+    Lt = 256
+    Lil = M - Lt                                            # rank 1 of 2: its image rows start at Lil, the text rows sit behind 2 Lil
+    og = lambda K: (M, 2 * Lil + Lt, Lil, Lil, Lil, 0, K)
+    x, u = rnd(M, KS[-1]).to(BF), rnd(M, KS[-1]).to(BF)
+    dx = rnd(M, KS[-1]).to(BF)
+    variants, order = {}, []
+    for r in (4, 64):
+        rp = (r + 15) // 16 * 16
+        for n, K in [(1, K) for K in KS] + [(3, 3072)]:
+            ext = (n * rp + 63) // 64 * 64
+            a = rnd(n * r, K, sc=0.02).to(BF)
+            t = torch.empty(M, ext, dtype=BF, device=dev)
+            dt = rnd(M, ext, sc=0.1).to(BF)
+            gA = torch.zeros(r, K, device=dev)
+            key = lambda kern, kind, r=r, n=n, K=K: (kern, r, n, K, kind)
+            order.append((r, n, K))
+            variants[key("down", "plain")] = lambda a=a, n=n, r=r, rp=rp, ext=ext, t=t, K=K: ops.lora_down_wide(x[:, :K], a, n, r, rp, ext, t, K)
+            variants[key("down", "drop")] = lambda a=a, n=n, r=r, rp=rp, ext=ext, t=t, K=K: [
+                ops.lora_down_wide_drop_at(x[:, :K], a[j * r:], g, r, rp, ext - j * rp if j + g == n else g * rp, t[:, j * rp:], K, p, seed, j, og(K))
+                for j, g in _groups(ops, n, rp)]
+            variants[key("tn", "plain")] = lambda r=r, K=K, gA=gA, dt=dt: ops.lora_tn_wide(x[:, :K], dt, r, gA, 1, K, 1.0, K)
+            variants[key("tn", "drop")] = lambda r=r, K=K, gA=gA, dt=dt: ops.lora_tn_wide_drop_at(x[:, :K], dt, r, gA, 1, K, 1.0, K, p, seed, 0, og(K))
+            variants[key("up_add", "plain")] = lambda a=a, n=n, r=r, rp=rp, dt=dt, K=K: ops.lora_up_add_wide(dx[:, :K], dt, a, n, r, rp, K)
+            variants[key("up_add", "drop")] = lambda a=a, n=n, r=r, rp=rp, dt=dt, K=K: ops.lora_up_add_wide_drop_at(dx[:, :K], dt, a, n, r, rp, K, p, seed, 0, og(K))
+            variants[key("up_add", "dgelu")] = lambda a=a, n=n, r=r, rp=rp, dt=dt, K=K: ops.lora_up_add_wide_dgelu_drop_at(
+                dx[:, :K], dt, a, n, r, rp, u[:, :K], K, p, seed, 0, og(K))
+    res = _alternate(torch, variants, args.warmup, args.rounds)
+    print(f"\n## lora_dropout {p}: each _at kernel right after its undropped sibling; microseconds median / spread, ratio to the sibling")
+    print("## tn is one adapter per call at any n; down at n = 3, r = 64 is two calls (2 + 1 adapters: the masked x blocks of three do not fit the LDS)")
+    print(f"{'kernel':>8} | {'r':>3} | {'n':>1} | {'K':>5} | {'undropped':>16} | {'_drop_at':>16} | {'ratio':>5} | {'dgelu _drop_at':>16} | {'ratio':>5}")
+    for kern in ("down", "tn", "up_add"):
+        for r, n, K in order:
+            (pm, ps), (dm, ds) = res[(kern, r, n, K, "plain")], res[(kern, r, n, K, "drop")]
+            g = res.get((kern, r, n, K, "dgelu"))
+            gcell = f"{g[0]:8.1f} / {g[1]:5.1f} | {g[0] / pm:5.2f}" if g else f"{'-':>16} | {'-':>5}"
+            print(f"{kern:>8} | {r:>3} | {n:>1} | {K:>5} | {pm:8.1f} / {ps:5.1f} | {dm:8.1f} / {ds:5.1f} | {dm / pm:5.2f} | {gcell}")
+
+
+def _groups(ops, n, rp):
+    """(first adapter, adapters) of each vt_lora_down_wide_drop_at call for n adapters: the engine's grouping (_HYRun.drop_down)"""
+    out, j = [], 0
+    while j < n:
+        g = n - j
+        while g > 1 and not ops.lora_down_wide_drop_fits(g, rp):
+            g -= 1
+        out.append((j, g))
+        j += g
+    return out
 
 
 if __name__ == "__main__":

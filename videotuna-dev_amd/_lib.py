@@ -93,6 +93,12 @@ PROTOTYPES = {
     "vt_lora_up_add_wide_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_up_add_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
     "vt_lora_up_add_wide_dgelu_drop": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i, _vp],
+    # _at: the wide _drop products with an origin map (seg_local, seg_global, n_first, off_first, off_rest, k0, K_log) before the stream
+    "vt_lora_down_wide_drop_at": [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i] + [_ll] * 5 + [_i, _i, _vp],
+    "vt_lora_tn_wide_drop_at": [_vp, _i, _vp, _i, _i, _fp, _ll, _ll, _f, _ll, _i, _f, C.c_ulonglong, _i] + [_ll] * 5 + [_i, _i, _vp],
+    "vt_lora_up_add_wide_drop_at": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _ll, _i, _f, C.c_ulonglong, _i] + [_ll] * 5 + [_i, _i, _vp],
+    "vt_lora_up_add_wide_dgelu_drop_at": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _ll, _i, _f, C.c_ulonglong, _i] + [_ll] * 5
+                                         + [_i, _i, _vp],
     # DoRA (use_dora): row norms / c = m / norm, the scaled operand refresh, the dB and dm finishes (csrc/dora.hip)
     "vt_dora_norm": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _fp, _fp, _vp],
     "vt_dora_scale": [_vp, _ll, _vp, _ll, _fp, _i, _i, _i, _vp],

@@ -187,3 +187,50 @@ static inline LoraDrop vt_lora_drop(float p, unsigned long long seed, int site0,
     return LoraDrop{vt_keep_thresh(p), 1.0f / (1.0f - p), seed, site0, n, r, 0};
 }
 static inline int vt_lora_drop_bad(float p, int site0) { return !(p >= 0.f) || !(p < 1.f) || site0 < 0 || site0 > (1 << 20); }
+// The origin map of a dropped wide-layout kernel (lora_wide.hip; the pack is LoraDrop, LoraOrigin [, LoraDgelu]): where the call's
+// [M, K] operand sits inside the adapter's logical input [M_g, K_log], whose element index e = m_g * K_log + k_g keys the mask.  The call
+// may hold a subset of the logical rows (one rank's rows under sequence parallelism) and a column range of the logical width:
+//   rows     b = m / seg_local, l = m % seg_local,  m_g = b * seg_global + l + (l < n_first ? off_first : off_rest)
+//   columns  k_g = k0 + k
+// The identity map (seg_local = seg_global >= M, no offsets, k0 = 0, K_log = K) is what the plain _drop entry points pass.
+struct LoraOrigin {
+    long long seg_local, seg_global, n_first, off_first, off_rest;
+    int k0, K_log;
+};
+static inline LoraOrigin vt_lora_origin_identity(long long M, int K) { return LoraOrigin{M > 0 ? M : 1, M > 0 ? M : 1, 0, 0, 0, 0, K}; }
+__host__ __device__ __forceinline__ long long lora_origin_row(const LoraOrigin& o, long long m) {
+    const long long b = m / o.seg_local, l = m - b * o.seg_local;
+    return b * o.seg_global + l + (l < o.n_first ? o.off_first : o.off_rest);
+}
+// index of element (m, 0) of the call's operand within the logical input
+__device__ __forceinline__ unsigned long long lora_origin_elem(const LoraOrigin& o, long long m) {
+    return (unsigned long long)lora_origin_row(o, m) * (unsigned long long)o.K_log + (unsigned long long)o.k0;
+}
+// a map no kernel may be launched with: a column range off the 8-element chunks or outside the logical width, a logical width that
+// splits a Philox counter between two rows, a non-positive segment, negative offsets, or an element whose counter e / 4 would reach
+// the next site's 2^36
+static inline int vt_lora_origin_bad(const LoraOrigin& o, long long M, int K) {
+    if (o.k0 < 0 || (o.k0 % 8) || o.K_log <= 0 || (o.K_log % 4) || (long long)o.k0 + K > o.K_log) return 1;
+    if (o.seg_local <= 0 || o.seg_global < 0 || o.n_first < 0 || o.n_first > o.seg_local || o.off_first < 0 || o.off_rest < 0) return 1;
+    if (M <= 0) return 0;
+    // the largest logical row: m_g grows with l inside each of a segment's two pieces, so the last row of each piece of the last two segments
+    const long long lim = (1LL << 38) / o.K_log;        // rows whose elements all lie below 2^38 (off by < 1 row: checked exactly below)
+    const long long bl = (M - 1) / o.seg_local, ll = (M - 1) - bl * o.seg_local;
+    if (bl > lim || o.seg_global > lim || o.off_first > lim || o.off_rest > lim || o.seg_local > (1LL << 40)) return 1;
+    if (o.seg_global && bl > lim / o.seg_global) return 1;
+    long long mg = 0;
+    for (int back = 0; back < 2 && bl - back >= 0; ++back) {
+        const long long last = back ? o.seg_local - 1 : ll;
+        const long long c0 = last < o.n_first ? last : o.n_first - 1;                  // last row of the first piece, if any
+        if (c0 >= 0) { const long long v = (bl - back) * o.seg_global + c0 + o.off_first; if (v > mg) mg = v; }
+        if (last >= o.n_first) { const long long v = (bl - back) * o.seg_global + last + o.off_rest; if (v > mg) mg = v; }
+    }
+    return (unsigned __int128)mg * (unsigned)o.K_log + (unsigned)(o.k0 + K - 1) >= ((unsigned __int128)1 << 38);
+}
+__device__ __forceinline__ LoraDrop lora_drop_arg(const LoraDrop& d, const LoraOrigin&) { return d; }
+__device__ __forceinline__ LoraDrop lora_drop_arg(const LoraDrop& d, const LoraOrigin&, const LoraDgelu&) { return d; }
+__device__ __forceinline__ LoraDgelu lora_dgelu_arg(const LoraDrop&, const LoraOrigin&) { return LoraDgelu{nullptr, 0}; }
+__device__ __forceinline__ LoraDgelu lora_dgelu_arg(const LoraDrop&, const LoraOrigin&, const LoraDgelu& g) { return g; }
+__device__ __forceinline__ LoraOrigin lora_origin_arg() { return LoraOrigin{1, 1, 0, 0, 0, 0, 4}; }
+__device__ __forceinline__ LoraOrigin lora_origin_arg(const LoraDrop&, const LoraOrigin& o) { return o; }
+__device__ __forceinline__ LoraOrigin lora_origin_arg(const LoraDrop&, const LoraOrigin& o, const LoraDgelu&) { return o; }

@@ -8,8 +8,10 @@
 // correction) are transposed on their way into LDS.  LDS rows are padded by 8 elements: the 16-byte fragment reads of 16 rows
 // then start 4 banks apart.
 // lora_dropout > 0: each product's dropped form is the same kernel with the trailing LoraDrop argument (mask convention and
-// semantics: see lora.hip and common.h).  Adapter j of a call is site site0 + j; element (m, k) of the logical [M, K] adapter input
-// has index e = m * K + k.
+// semantics: see lora.hip and common.h).  Adapter j of a call is site site0 + j; element (m_g, k_g) of the logical [M_g, K_log] adapter
+// input has index e = m_g * K_log + k_g.  Every dropped instantiation takes a LoraOrigin behind the LoraDrop: the map from the call's
+// (m, k) to (m_g, k_g).  The _drop entry points pass the identity (the call IS the logical input); the _drop_at entry points take the
+// map from the caller: one rank's rows of a sequence-parallel run, one column range of a wider input (HunyuanVideo).
 #include "common.h"
 
 #define LW_PAD 8
@@ -38,6 +40,7 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
                                                             int ext, bf16_t* T, int ldt, long long M, int K, D... drop) {
     constexpr bool DROP = sizeof...(D) > 0;
     const LoraDrop dr = lora_drop_arg(drop...);
+    const LoraOrigin og = lora_origin_arg(drop...);
     const int nx = DROP ? n : 1;                // X blocks in LDS
     extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
     bf16_t* sX = lw_smem;                       // [nx][64][LW_KS]; DROP: block j = X masked for adapter j
@@ -51,6 +54,11 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
     for (int i = 0; i < LWD_TPW; ++i)
 #pragma unroll
         for (int rt = 0; rt < 4; ++rt) acc[i][rt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    unsigned long long eb[2] = {0ull, 0ull};    // DROP: logical index of element (m, 0) of the two rows this thread stages
+    if constexpr (DROP) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) eb[it] = lora_origin_elem(og, row0 + ((tid + 256 * it) >> 3));
+    }
     for (int k0 = 0; k0 < K; k0 += 64) {
         __syncthreads();
 #pragma unroll
@@ -60,7 +68,7 @@ __global__ __launch_bounds__(256) void lora_wide_down_kernel(const bf16_t* X, in
             u32x4 v = zero4;
             if (m < M) v = *(const u32x4*)(X + (size_t)m * ldx + k0 + 8 * ch);
             if constexpr (DROP) {
-                const unsigned long long e4 = ((unsigned long long)m * K + k0 + 8 * ch) >> 2;
+                const unsigned long long e4 = (eb[it] + k0 + 8 * ch) >> 2;
                 for (int j = 0; j < n; ++j)
                     *(u32x4*)(sX + (j * 64 + row) * LW_KS + 8 * ch) = keep_mask8(v, lora_site_offset(dr.site0 + j) + e4, dr.seed, dr.thresh);
             } else {
@@ -134,7 +142,7 @@ extern "C" int vt_lora_down_wide_drop_fits(int n_adapters, int rp) {
 }
 // dr == nullptr: no dropout
 static int lora_down_wide_launch(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T, int ldt,
-                                 long long M, int K, const LoraDrop* dr, void* stream) {
+                                 long long M, int K, const LoraDrop* dr, const LoraOrigin* og, void* stream) {
     if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
         n_adapters * rp > 16 * 4 * LWD_TPW || ext < n_adapters * rp || (ext % 4) || (ldx % 8) || (lda % 8) || (ldt % 4) || ldt < ext)
         return VT_ERR_BAD_SHAPE;
@@ -147,19 +155,31 @@ static int lora_down_wide_launch(const void* X, int ldx, const void* A, int lda,
         hipLaunchKernelGGL(lora_wide_down_kernel<>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X, ldx,
                            (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K);
     else
-        hipLaunchKernelGGL(lora_wide_down_kernel<LoraDrop>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)X,
-                           ldx, (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K, *dr);
+        hipLaunchKernelGGL((lora_wide_down_kernel<LoraDrop, LoraOrigin>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream,
+                           (const bf16_t*)X, ldx, (const bf16_t*)A, lda, n_adapters, r, rp, ext, (bf16_t*)T, ldt, M, K, *dr, *og);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 extern "C" int vt_lora_down_wide(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
                                  int ldt, long long M, int K, void* stream) {
-    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, nullptr, stream);
+    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, nullptr, nullptr, stream);
 }
 extern "C" int vt_lora_down_wide_drop(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
                                       int ldt, long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
     if (n_adapters <= 0 || !vt_lora_down_wide_drop_fits(n_adapters, rp) || vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site0);
-    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, &dr, stream);
+    const LoraOrigin og = vt_lora_origin_identity(M, K);
+    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, &dr, &og, stream);
+}
+// _at: X holds the rows / columns of the adapters' logical input that the origin map names (common.h, LoraOrigin)
+extern "C" int vt_lora_down_wide_drop_at(const void* X, int ldx, const void* A, int lda, int n_adapters, int r, int rp, int ext, void* T,
+                                         int ldt, long long M, int K, float p, unsigned long long seed, int site0, long long seg_local,
+                                         long long seg_global, long long n_first, long long off_first, long long off_rest, int k0,
+                                         int K_log, void* stream) {
+    const LoraOrigin og = {seg_local, seg_global, n_first, off_first, off_rest, k0, K_log};
+    if (n_adapters <= 0 || !vt_lora_down_wide_drop_fits(n_adapters, rp) || vt_lora_drop_bad(p, site0) || vt_lora_origin_bad(og, M, K))
+        return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    return lora_down_wide_launch(X, ldx, A, lda, n_adapters, r, rp, ext, T, ldt, M, K, &dr, &og, stream);
 }
 
 // ---------------- out[p*osp + i*osr] += alpha * sum_m Big[m,p] * Small[m,i]   (i < R <= 128) ----------------
@@ -178,6 +198,7 @@ __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, in
                                                           int tiles_per_slice, D... drop) {
     constexpr bool DROP = sizeof...(D) > 0;
     const LoraDrop dr = lora_drop_arg(drop...);
+    const LoraOrigin og = lora_origin_arg(drop...);
     const unsigned long long off = lora_site_offset(dr.site0);
     __shared__ __attribute__((aligned(16))) bf16_t sB[128 * LW_KS];
     __shared__ __attribute__((aligned(16))) bf16_t sS[128 * LW_KS];
@@ -205,9 +226,9 @@ __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, in
                 if (m < M) r0 = *(const u32x4*)(Big + (size_t)m * ldb + p);
                 if (m + 1 < M) r1 = *(const u32x4*)(Big + (size_t)(m + 1) * ldb + p);
                 if constexpr (DROP) {
-                    const unsigned long long e4 = ((unsigned long long)m * P + p) >> 2;
-                    if (m < M) r0 = keep_mask8(r0, off + e4, dr.seed, dr.thresh);
-                    if (m + 1 < M) r1 = keep_mask8(r1, off + e4 + (P >> 2), dr.seed, dr.thresh);
+                    // the two rows' logical indices separately: a segment boundary of the origin map may lie between them
+                    if (m < M) r0 = keep_mask8(r0, off + ((lora_origin_elem(og, m) + p) >> 2), dr.seed, dr.thresh);
+                    if (m + 1 < M) r1 = keep_mask8(r1, off + ((lora_origin_elem(og, m + 1) + p) >> 2), dr.seed, dr.thresh);
                 }
             }
             lw_store_pair_t(sB, LW_KS, 8 * pc, q, r0, r1);
@@ -257,7 +278,7 @@ __global__ __launch_bounds__(256) void lora_wide_tn_kernel(const bf16_t* Big, in
 }
 // dr == nullptr: no dropout, else alpha carries the 1 / (1 - p)
 static int lora_tn_wide_launch(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
-                               float alpha, long long M, int P, const LoraDrop* dr, void* stream) {
+                               float alpha, long long M, int P, const LoraDrop* dr, const LoraOrigin* og, void* stream) {
     if (M <= 0 || P <= 0 || (P % 8) || R <= 0 || R > 128 || (ldb % 8) || lds_ < R || osp <= 0 || osr <= 0) return VT_ERR_BAD_SHAPE;
     if (((uintptr_t)Big) & 15) return VT_ERR_BAD_ALIGN;
     if ((((uintptr_t)Small) & 1) || (((uintptr_t)out) & 3)) return VT_ERR_BAD_ALIGN;
@@ -276,21 +297,32 @@ static int lora_tn_wide_launch(const void* Big, int ldb, const void* Small, int 
         if (osr == 1) hipLaunchKernelGGL(lora_wide_tn_kernel<true>, grid, dim3(256), 0, st, LWT_ARGS);
         else hipLaunchKernelGGL(lora_wide_tn_kernel<false>, grid, dim3(256), 0, st, LWT_ARGS);
     } else {
-        if (osr == 1) hipLaunchKernelGGL((lora_wide_tn_kernel<true, LoraDrop>), grid, dim3(256), 0, st, LWT_ARGS, *dr);
-        else hipLaunchKernelGGL((lora_wide_tn_kernel<false, LoraDrop>), grid, dim3(256), 0, st, LWT_ARGS, *dr);
+        if (osr == 1) hipLaunchKernelGGL((lora_wide_tn_kernel<true, LoraDrop, LoraOrigin>), grid, dim3(256), 0, st, LWT_ARGS, *dr, *og);
+        else hipLaunchKernelGGL((lora_wide_tn_kernel<false, LoraDrop, LoraOrigin>), grid, dim3(256), 0, st, LWT_ARGS, *dr, *og);
     }
 #undef LWT_ARGS
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 extern "C" int vt_lora_tn_wide(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
                                float alpha, long long M, int P, void* stream) {
-    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha, M, P, nullptr, stream);
+    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha, M, P, nullptr, nullptr, stream);
 }
 extern "C" int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp, long long osr,
                                     float alpha, long long M, int P, float p, unsigned long long seed, int site, void* stream) {
     if (vt_lora_drop_bad(p, site)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site);
-    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha * dr.inv_keep, M, P, &dr, stream);
+    const LoraOrigin og = vt_lora_origin_identity(M, P);
+    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha * dr.inv_keep, M, P, &dr, &og, stream);
+}
+// _at: Big holds the rows / columns of the adapter's logical input that the origin map names (the P columns are k0 .. k0 + P of K_log)
+extern "C" int vt_lora_tn_wide_drop_at(const void* Big, int ldb, const void* Small, int lds_, int R, float* out, long long osp,
+                                       long long osr, float alpha, long long M, int P, float p, unsigned long long seed, int site,
+                                       long long seg_local, long long seg_global, long long n_first, long long off_first,
+                                       long long off_rest, int k0, int K_log, void* stream) {
+    const LoraOrigin og = {seg_local, seg_global, n_first, off_first, off_rest, k0, K_log};
+    if (vt_lora_drop_bad(p, site) || vt_lora_origin_bad(og, M, P)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site);
+    return lora_tn_wide_launch(Big, ldb, Small, lds_, R, out, osp, osr, alpha * dr.inv_keep, M, P, &dr, &og, stream);
 }
 
 // ---------------- dX[m,k] += sum_j sum_i dT[m, j*rp + i] * A[j*r + i, k]   (in place, bf16; all adapters in one pass) ----------------
@@ -307,8 +339,9 @@ extern "C" int vt_lora_tn_wide_drop(const void* Big, int ldb, const void* Small,
 template <typename... D>
 __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int ldx, const bf16_t* dT, int ldt, const bf16_t* A, int lda,
                                                               int n, int r, int rp, long long M, int K, D... drop) {
-    constexpr bool DROP = sizeof...(D) > 0, DGELU = sizeof...(D) > 1;
+    constexpr bool DROP = sizeof...(D) > 0, DGELU = sizeof...(D) > 2;       // the pack: LoraDrop, LoraOrigin [, LoraDgelu]
     const LoraDrop dr = lora_drop_arg(drop...);
+    const LoraOrigin og = lora_origin_arg(drop...);
     const LoraDgelu dg = lora_dgelu_arg(drop...);
     extern __shared__ __attribute__((aligned(16))) bf16_t lw_smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
@@ -317,6 +350,11 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
     const long long row0 = (long long)blockIdx.x * 128 + 32 * wave;
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
     bf16x8 dtf[2][LWU_MAXKS];
+    unsigned long long eb[2] = {0ull, 0ull};    // DROP: logical index of element (m, 0) of this lane's two rows
+    if constexpr (DROP) {
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) eb[rt] = lora_origin_elem(og, row0 + rt * 16 + fr);
+    }
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
         const long long m = row0 + rt * 16 + fr;
@@ -386,7 +424,7 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
                 const unsigned long long off = lora_site_offset(dr.site0 + j);
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt) {
-                    const unsigned long long e4 = ((unsigned long long)(row0 + rt * 16 + fr) * K + k0 + 4 * fq) >> 2;
+                    const unsigned long long e4 = (eb[rt] + k0 + 4 * fq) >> 2;
 #pragma unroll
                     for (int ct = 0; ct < 4; ++ct) {
                         unsigned rnd[4];
@@ -445,7 +483,8 @@ __global__ __launch_bounds__(256) void lora_wide_up_add_kernel(bf16_t* dX, int l
 }
 // dr == nullptr: no dropout
 static int lora_up_add_wide_launch(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
-                                   long long M, int K, const LoraDrop* dr, void* stream, const LoraDgelu* dg = nullptr) {
+                                   long long M, int K, const LoraDrop* dr, const LoraOrigin* og, void* stream,
+                                   const LoraDgelu* dg = nullptr) {
     if (M <= 0 || K <= 0 || (K % 64) || n_adapters <= 0 || r <= 0 || r > 128 || rp < r || (rp % 16) ||
         n_adapters * rp > 32 * LWU_MAXKS || (ldx % 4) || ldx < K || (ldt % 8) || ldt < n_adapters * rp || (lda % 8))
         return VT_ERR_BAD_SHAPE;
@@ -463,22 +502,34 @@ static int lora_up_add_wide_launch(void* dX, int ldx, const void* dT, int ldt, c
         hipLaunchKernelGGL(lora_wide_up_add_kernel<>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
                            (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K);
     else if (dg != nullptr)
-        hipLaunchKernelGGL((lora_wide_up_add_kernel<LoraDrop, LoraDgelu>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream,
-                           (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr, *dg);
+        hipLaunchKernelGGL((lora_wide_up_add_kernel<LoraDrop, LoraOrigin, LoraDgelu>), dim3((unsigned)blocks), dim3(256), lds,
+                           (hipStream_t)stream, (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr,
+                           *og, *dg);
     else
-        hipLaunchKernelGGL(lora_wide_up_add_kernel<LoraDrop>, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, (bf16_t*)dX, ldx,
-                           (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr);
+        hipLaunchKernelGGL((lora_wide_up_add_kernel<LoraDrop, LoraOrigin>), dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream,
+                           (bf16_t*)dX, ldx, (const bf16_t*)dT, ldt, (const bf16_t*)A, lda, n_adapters, r, rp, M, K, *dr, *og);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 extern "C" int vt_lora_up_add_wide(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
                                    long long M, int K, void* stream) {
-    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, nullptr, stream);
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, nullptr, nullptr, stream);
 }
 extern "C" int vt_lora_up_add_wide_drop(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r, int rp,
                                         long long M, int K, float p, unsigned long long seed, int site0, void* stream) {
     if (vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site0);
-    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, stream);
+    const LoraOrigin og = vt_lora_origin_identity(M, K);
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, &og, stream);
+}
+// _at: dX holds the rows / columns of the adapters' logical input gradient that the origin map names
+extern "C" int vt_lora_up_add_wide_drop_at(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r,
+                                           int rp, long long M, int K, float p, unsigned long long seed, int site0, long long seg_local,
+                                           long long seg_global, long long n_first, long long off_first, long long off_rest, int k0,
+                                           int K_log, void* stream) {
+    const LoraOrigin og = {seg_local, seg_global, n_first, off_first, off_rest, k0, K_log};
+    if (vt_lora_drop_bad(p, site0) || vt_lora_origin_bad(og, M, K)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, &og, stream);
 }
 // the dgelu form (lora.hip, lora_up_add_kernel): the masked sum times gelu'(U[m,k]), U the saved pre-activation of the GELU whose
 // output the adapters read
@@ -488,7 +539,18 @@ extern "C" int vt_lora_up_add_wide_dgelu_drop(void* dX, int ldx, const void* dT,
     if (vt_lora_drop_bad(p, site0)) return VT_ERR_BAD_SHAPE;
     const LoraDrop dr = vt_lora_drop(p, seed, site0);
     const LoraDgelu dg = {(const bf16_t*)U, ldu};
-    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, stream, &dg);
+    const LoraOrigin og = vt_lora_origin_identity(M, K);
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, &og, stream, &dg);
+}
+extern "C" int vt_lora_up_add_wide_dgelu_drop_at(void* dX, int ldx, const void* dT, int ldt, const void* A, int lda, int n_adapters, int r,
+                                                 int rp, const void* U, int ldu, long long M, int K, float p, unsigned long long seed,
+                                                 int site0, long long seg_local, long long seg_global, long long n_first,
+                                                 long long off_first, long long off_rest, int k0, int K_log, void* stream) {
+    const LoraOrigin og = {seg_local, seg_global, n_first, off_first, off_rest, k0, K_log};
+    if (vt_lora_drop_bad(p, site0) || vt_lora_origin_bad(og, M, K)) return VT_ERR_BAD_SHAPE;
+    const LoraDrop dr = vt_lora_drop(p, seed, site0);
+    const LoraDgelu dg = {(const bf16_t*)U, ldu};
+    return lora_up_add_wide_launch(dX, ldx, dT, ldt, A, lda, n_adapters, r, rp, M, K, &dr, &og, stream, &dg);
 }
 
 // ---------------- write (alpha/r) * B into the ext-column K-extension of the packed weight and of its transpose ----------------

@@ -30,6 +30,9 @@ reference, which never quantises gradients).
 LoRA (``lora_rank``, ``lora_target_modules``): rank-r adapters on the image stream's attention projections (the shipped recipe's targets,
 the default) and, by name, on its feed-forward Linears -- fc1, fc2, the MLP rows of linear1, linear2 (_HYLora); every adapted Linear stays
 ONE GEMM over K-extended operands, forward and input gradient (DESIGN 3 "LoRA as a K-extension").
+``lora_dropout`` = p > 0: in training mode every adapter reads its Linear's input under its own Philox keep mask (peft's nn.Dropout in front of
+lora_A), recomputed inside the wide rank-side kernels and keyed by the row of the unsharded run (DESIGN 4 "mask convention"); the input
+gradient is then the base product plus an in-place masked correction.
 
 NOT built (recorded in DESIGN.md): the embedders / token refiner / final layer of HYVideoDiffusionTransformer, the diffusers
 ``HunyuanVideoTransformer3DModel`` key map and LoRA wrappers of the shipped recipe, (the head_dim-128 attention backward is atomics-only: no dQ hand-off chains yet).  Padding text rows attend to the valid keys here
@@ -45,6 +48,7 @@ import torch
 import torch.distributed
 
 from . import ops
+from .engine import lora_dropout_seed
 from .lora import extension_layout
 from .ops import BF16, EPI_BIAS_GELU, EPI_DGELU, EPI_GATED_RES
 from .stdit import _STRun
@@ -84,14 +88,15 @@ EXT = 64          # K-extension columns of a LoRA'd Linear: x_ext = [x | x A^T (
 MAX_R = 128       # ranks with 3 r > EXT: the wide layout of vt355.lora.extension_layout on the MFMA rank-side kernels (csrc/lora_wide.hip)
 
 
-def lora_layout(r: int):
+def lora_layout(r: int, wide: bool = False):
     """(rp, ext_qkv, ext_proj, wide) of the K-extension of a HunyuanVideo adapter of rank r.  3 r <= 64: the three adapters of a fused
     projection sit side by side (column stride rp = r) in a fixed 64-column extension.  Above that -- or at any rank when VT355_LORA_WIDE=1
-    is set, a test / A-B knob -- the wide layout: rp = r rounded up to a multiple of 16, adapter j in columns [j rp, j rp + r), the
+    is set, a test / A-B knob, or with wide=True (lora_dropout > 0: the narrow layout's rank-side work is stock GEMMs with nowhere to
+    mask) -- the wide layout: rp = r rounded up to a multiple of 16, adapter j in columns [j rp, j rp + r), the
     extension 3 rp (q | k | v projections) / rp (img_attn_proj) columns rounded up to a multiple of 64, every other column zero."""
     if r <= 0 or r > MAX_R:
         raise ValueError(f"rank {r}: HunyuanVideo LoRA ranks are 1..{MAX_R} (three adapters of {MAX_R} rank columns fill the widest K-extension)")
-    if 3 * r <= EXT and os.environ.get("VT355_LORA_WIDE", "0") in ("", "0"):
+    if not wide and 3 * r <= EXT and os.environ.get("VT355_LORA_WIDE", "0") in ("", "0"):
         return r, EXT, EXT, False
     return extension_layout(r, wide=True)
 
@@ -132,11 +137,16 @@ class _HYLora(FlatParamModule):
     ff.net.0.proj -> ``double_blocks.N.img_mlp.fc1`` (A [r, D], B [4D, r]), ff.net.2 -> ``double_blocks.N.img_mlp.fc2`` (A [r, 4D],
     B [D, r]), proj_mlp -> the MLP rows of ``single_blocks.N.linear1`` (tag ``mlp``: A [r, D], B [4D, r]), proj_out ->
     ``single_blocks.N.linear2`` (A [r, 5D], B [D, r]).
-    Ranks 1..128; the K-extension layout (narrow up to 3 r = 64, wide above) is lora_layout's and does not show in names or shapes."""
+    Ranks 1..128; the K-extension layout (narrow up to 3 r = 64, wide above) is lora_layout's and does not show in names or shapes.
+    ``dropout`` = p > 0 (peft's lora_dropout): every adapter reads its Linear's input under its own Philox keep mask in training mode
+    (DESIGN 4 "mask convention"); the layout is then the wide one at every rank.  ``site_of``: lora_A name -> adapter site, the adapter's
+    position among the lora_A entries of ``shapes`` (q, k, v of a fused projection are consecutive sites)."""
 
-    def __init__(self, D: int, n_double: int, n_single: int, r: int, alpha: float, ratio: float = 4.0, target_modules=None):
+    def __init__(self, D: int, n_double: int, n_single: int, r: int, alpha: float, ratio: float = 4.0, target_modules=None,
+                 dropout: float = 0.0):
         super().__init__()
-        self.rp, self.ext_qkv, self.ext_proj, self.wide = lora_layout(r)      # fixed at construction (VT355_LORA_WIDE is read here)
+        self.p = float(dropout)
+        self.rp, self.ext_qkv, self.ext_proj, self.wide = lora_layout(r, wide=self.p > 0)      # fixed at construction (VT355_LORA_WIDE is read here)
         self.r, self.scaling, self.D = r, alpha / r, D
         self.attn, self.ff_targets = resolve_lora_targets(target_modules)
         sh: Dict[str, tuple] = {}
@@ -176,6 +186,7 @@ class _HYLora(FlatParamModule):
             sh[s.a_name] = (r, s.din)
             sh[s.b_name] = (s.dout, r)
         self._setup_flat(sh)
+        self.site_of = {n: i for i, n in enumerate(n for n in self.shapes if ".lora_A" in n)}
 
     def ext_of(self, mod: str) -> int:
         """K-extension columns of the adapted Linear `mod` of the attention group"""
@@ -201,10 +212,21 @@ class HunyuanBlocks(FlatParamModule):
     def __init__(self, hidden_size: int = 3072, heads_num: int = 24, mlp_width_ratio: float = 4.0, mm_double_blocks_depth: int = 20,
                  mm_single_blocks_depth: int = 40, fp8: bool = False, lora_rank: int = 0, lora_alpha: float = 1.0,
                  shapes_before: Optional[Dict[str, tuple]] = None, shapes_after: Optional[Dict[str, tuple]] = None, fp8_amax_history: int = 16,
-                 fp8_dgrad=False, lora_target_modules=None):
+                 fp8_dgrad=False, lora_target_modules=None, lora_dropout: float = 0.0):
         super().__init__()
         if hidden_size // heads_num != 128 or hidden_size % 128:
             raise ValueError("HunyuanVideo heads are 128 wide")
+        if not (0.0 <= lora_dropout < 1.0):
+            raise ValueError(f"lora_dropout={lora_dropout!r}: a probability 0 <= p < 1")
+        if lora_dropout > 0 and lora_rank == 0:
+            raise ValueError(f"lora_dropout={lora_dropout!r} without adapters: set lora_rank")
+        if lora_dropout > 0 and fp8_dgrad:
+            raise NotImplementedError(f"lora_dropout={lora_dropout!r} with fp8_dgrad={fp8_dgrad!r}: the dGELU epilogue's fp8 copy of d(u) would lack "
+                                      "the masked adapter term, which is added after the product (DESIGN 8: a vt_cast_fp8_fmt pass after the "
+                                      "masked add at the two dGELU gradient sites)")
+        self.lora_dropout = float(lora_dropout)
+        self.lora_dropout_seed = None        # lora_dropout > 0: None = a fresh mask seed per training forward, an int pins it
+        self.last_lora_dropout_seed = None   # the seed the latest training forward used
         if fp8_amax_history < 1:
             raise ValueError("fp8_amax_history: at least one recorded amax")
         self.hidden_size, self.heads_num, self.ratio = hidden_size, heads_num, mlp_width_ratio
@@ -223,7 +245,7 @@ class HunyuanBlocks(FlatParamModule):
         if lora_rank == 0:
             resolve_lora_targets(lora_target_modules)
         self.lora = _HYLora(hidden_size, mm_double_blocks_depth, mm_single_blocks_depth, lora_rank, lora_alpha, mlp_width_ratio,
-                            lora_target_modules) if lora_rank != 0 else None
+                            lora_target_modules, dropout=lora_dropout) if lora_rank != 0 else None
         self.sp_group = None
         self.fp8_dgrad = fp8_dgrad
 
@@ -254,6 +276,9 @@ class HunyuanBlocks(FlatParamModule):
             raise ValueError(f"fp8_dgrad={mode!r}: one of False, True / 'e5m2', 'e4m3'")
         if mode and self._fp8 != "mfma":
             raise ValueError(f"fp8_dgrad={mode!r}: the fp8 input-gradient products belong to fp8='mfma' (fp8={self._fp8!r})")
+        if mode and getattr(self, "lora_dropout", 0.0) > 0:
+            raise NotImplementedError(f"fp8_dgrad={mode!r} with lora_dropout={self.lora_dropout!r}: the dGELU epilogue's fp8 copy of d(u) would "
+                                      "lack the masked adapter term (DESIGN 8)")
         self._fp8_dgrad = mode
         self._packed = None                 # the transposed operands change: fp8 bytes instead of bf16 copies
         self.fp8_reset()
@@ -317,6 +342,16 @@ class HunyuanBlocks(FlatParamModule):
                 raise ValueError(f"{self.heads_num} heads do not split over {dist.get_world_size(group)} ranks")
         self.sp_group = group
         return self
+
+    def _sp_rows(self, N: int):
+        """(first row, row count) of this rank's image tokens: everything without sequence parallelism"""
+        if self.sp_group is None:
+            return 0, N
+        import torch.distributed as dist
+        P, r = dist.get_world_size(self.sp_group), dist.get_rank(self.sp_group)
+        if N % P:
+            raise ValueError(f"{N} image tokens do not split over {P} ranks")
+        return r * (N // P), N // P
 
     def init_weights(self, seed: int = 0):
         g = torch.Generator().manual_seed(seed)
@@ -630,6 +665,37 @@ class _HYRun(_STRun):
         self.gdt, self.gfmax = (ops.FP8, 448.0) if model.fp8_grad_format == "e4m3" else (ops.FP8_E5M2, 57344.0)
         self.g8s = None                 # (amax, history, scale) of the gradient sites, set by backward()
         self.gjit = False
+        # lora_dropout > 0 and model.training: (p, seed) of this forward's keep masks, else None -- and then nothing below is dropout's
+        self.drop = lora_dropout_seed(model) if (model.lora is not None and model.lora.p > 0) else None
+        if self.drop is not None and self.sp is not None and model.lora_dropout_seed is None:
+            raise RuntimeError("lora_dropout under sequence parallelism: every rank of the group must use one mask seed -- set "
+                               "model.lora_dropout_seed (HunyuanVideoFlow.training_step broadcasts one per step)")
+
+    # ---- lora_dropout: adapter sites and origin maps (DESIGN 4 "mask convention") ----
+    def origin(self, joint: bool, K_log: int, k0: int = 0):
+        """the origin map (ops.lora_*_drop_at) of an operand whose rows are this run's image rows (double blocks) or its [image; text]
+        rows (joint: single blocks) and whose columns are k0 .. of the adapter's K_log wide input: the mask is keyed by the row of the
+        UNSHARDED run, b Li + l resp. b (Li + Lt) + l with the image rows first -- under sequence parallelism this rank's image rows
+        start at _sp_rows' first row, the replicated text rows sit behind all of the image rows"""
+        Lil, Lt = self._Lil, self._Lt
+        Li = Lil * self.spP
+        lo = self.m._sp_rows(Li)[0]
+        if joint:
+            return (Lil + Lt, Li + Lt, Lil, lo, Li - Lil, k0, K_log)
+        return (Lil, Li, 0, 0, lo, k0, K_log)
+
+    def drop_down(self, x, a, n: int, r: int, rp: int, ext: int, t, K: int, site0: int, og):
+        """t = the adapters' masked down-projections of x (the whole extension, zeros included): one vt_lora_down_wide_drop_at call where
+        the n masked copies of an x block fit the LDS, else the largest groups that do (rank 128: one adapter per call)"""
+        p, seed = self.drop
+        j = 0
+        while j < n:
+            g = n - j
+            while g > 1 and not ops.lora_down_wide_drop_fits(g, rp):
+                g -= 1
+            last = j + g == n
+            ops.lora_down_wide_drop_at(x, a[j * r:], g, r, rp, ext - j * rp if last else g * rp, t[:, j * rp:], K, p, seed, site0 + j, og)
+            j += g
 
     # ---- fp8="mfma": activation sites and their delayed scales ----
     def qsite(self, site):
@@ -829,7 +895,13 @@ class _HYRun(_STRun):
         n = len(tags)
         wext, wtext, a = self.LP.wext[mod], self.LP.wtext[mod], self.LP.a[mod]
         assert ext == L.ext_of(mod) and wext.shape[1] == D + ext
-        ops.lora_down_wide(xe, a, n, r, rp, ext, xe[:, D:], D)
+        drop = self.drop
+        if drop is not None:            # adapter j reads x under the mask of site s0 + j; the rows: image rows, or linear1's [image; text]
+            s0 = L.site_of[f"{mod}.lora_A{'.' + tags[0] if tags[0] else ''}.weight"]
+            og = self.origin(mod.startswith("single_blocks."), D)
+            self.drop_down(xe, a, n, r, rp, ext, xe[:, D:], D, s0, og)
+        else:
+            ops.lora_down_wide(xe, a, n, r, rp, ext, xe[:, D:], D)
         if y is None:
             y = self.E(M, wext.shape[0])
         if q8 is not None:
@@ -854,12 +926,18 @@ class _HYRun(_STRun):
                     gB = L.flat(self.lts.grad, f"{mod}.lora_B{dot}.weight")         # [D, r]
                     gA = L.flat(self.lts.grad, f"{mod}.lora_A{dot}.weight")         # [r, D]
                     ops.lora_tn_wide(g[:, j * D:(j + 1) * D], xe[:, D + j * rp:], r, gB, r, 1, L.scaling, D)    # dB_j += scaling g_j^T t_j
-                    ops.lora_tn_wide(xe[:, :D], dt[:, j * rp:], r, gA, 1, D, 1.0, D)                            # dA_j += dt_j^T x
+                    if drop is not None:                                                                        # dA_j += dt_j^T (keep_j * x) / (1 - p)
+                        ops.lora_tn_wide_drop_at(xe[:, :D], dt[:, j * rp:], r, gA, 1, D, 1.0, D, drop[0], drop[1], s0 + j, og)
+                    else:
+                        ops.lora_tn_wide(xe[:, :D], dt[:, j * rp:], r, gA, 1, D, 1.0, D)                        # dA_j += dt_j^T x
             if fp8dx:
                 dx = self.E(M, D)
                 self.dx_gemm(self.grad_in(gsite, g, gq), gsite, q8[2], dx, cols=q8[3], tail=(dt, self.LP.a3t[mod]))
                 return dx
-            ops.lora_up_add_wide(dxe, dt, a, n, r, rp, D)               # dx += sum_j dt_j A_j, in place
+            if drop is not None:                                        # dx += sum_j keep_j * (dt_j A_j) / (1 - p), in place
+                ops.lora_up_add_wide_drop_at(dxe, dt, a, n, r, rp, D, drop[0], drop[1], s0, og)
+            else:
+                ops.lora_up_add_wide(dxe, dt, a, n, r, rp, D)           # dx += sum_j dt_j A_j, in place
             return dxe[:, :D]                                           # a row-strided view
         return y, backward
 
@@ -876,13 +954,20 @@ class _HYRun(_STRun):
         s = L.ff[key]
         K, ext = s.din, L.ext_ff
         x, t = buf[:, F.xoff:F.xoff + K], buf[:, F.eoff:F.eoff + ext]
-        ops.gemm(x, F.a, t, None)
+        if self.drop is not None:       # t = (keep * x) A^T / (1 - p): the site's own mask over its whole input
+            self.drop_down(x, F.a, 1, L.r, L.rpf, ext, t, K, L.site_of[s.a_name], self.ff_origin(key))
+        else:
+            ops.gemm(x, F.a, t, None)
         if q8 is not None:
             xq, site, wname, rows = q8
             self.mx_gemm(xq, site, wname, y, bias, rows=rows, tail=(t, F.wb), **epi)
         else:
             ops.gemm(buf[:, :K + ext], F.wext, y, bias, **epi)
         return x, t
+
+    def ff_origin(self, key: str, k0: int = 0):
+        """origin map of the feed-forward site `key` (columns k0 .. of its input): the single blocks' sites see [image; text] rows"""
+        return self.origin(key.startswith("single_blocks."), self.lora.ff[key].din, k0)
 
     def ff_rank(self, key: str, ge, x, t):
         """the rank side of site `key`'s backward: ge = [g | .] the extended output gradient, x / t the site's input and t = x A^T.
@@ -895,7 +980,11 @@ class _HYRun(_STRun):
         ops.gemm(g, F.sbt, dt, None)
         if self.lts is not None:
             ops.lora_tn_wide(g, t, L.r, L.flat(self.lts.grad, s.b_name), L.r, 1, L.scaling, N)           # dB += scaling g^T t
-            ops.lora_tn_wide(x, dt, L.r, L.flat(self.lts.grad, s.a_name), 1, s.din, 1.0, s.din)          # dA += dt^T x
+            if self.drop is not None:                                                                    # dA += dt^T (keep * x) / (1 - p)
+                ops.lora_tn_wide_drop_at(x, dt, L.r, L.flat(self.lts.grad, s.a_name), 1, s.din, 1.0, s.din, self.drop[0], self.drop[1],
+                                         L.site_of[s.a_name], self.ff_origin(key))
+            else:
+                ops.lora_tn_wide(x, dt, L.r, L.flat(self.lts.grad, s.a_name), 1, s.din, 1.0, s.din)      # dA += dt^T x
 
     def ff_dx(self, key: str, ge, out, gq, gsite, wname, rows=None, cols=None, **epi):
         """out = epilogue(g W + dt A) of site `key` from the extended gradient ge = [g | dt] (after ff_rank): ONE product over
@@ -904,6 +993,19 @@ class _HYRun(_STRun):
         row range of the fp8 weight), dt A as its bf16 tail."""
         F, N = self.LP.ff[key], self.lora.ff[key].dout
         lo, hi = rows if rows is not None else (0, F.a3t.shape[0])
+        if self.drop is not None:
+            # lora_dropout: the adapter's term keep * (dt A) / (1 - p) is masked per element of `out` and the base product is not, so it
+            # cannot ride in the product: the base product alone with the epilogue, then the masked correction in place -- times
+            # gelu'(u) where the epilogue was the dGELU one (the site's input is gelu(u): out = (g W + keep * (dt A) / (1 - p)) gelu'(u))
+            L = self.lora
+            ops.gemm(ge[:, :N], F.wtx[lo:hi, :N], out, None, **epi)
+            og = self.ff_origin(key, k0=lo)
+            args = (out, ge[:, N:N + L.ext_ff], F.a[:, lo:hi], 1, L.r, L.rpf)
+            if epi.get("epilogue") == EPI_DGELU:
+                ops.lora_up_add_wide_dgelu_drop_at(*args, epi["pre_act_in"], hi - lo, self.drop[0], self.drop[1], L.site_of[L.ff[key].a_name], og)
+            else:
+                ops.lora_up_add_wide_drop_at(*args, hi - lo, self.drop[0], self.drop[1], L.site_of[L.ff[key].a_name], og)
+            return out
         if self.dg:
             self.dx_gemm(gq, gsite, wname, out, rows=rows, cols=cols, tail=(ge[:, N:N + self.lora.ext_ff], F.a3t[lo:hi]), **epi)
         else:
@@ -1416,6 +1518,7 @@ class _HYRun(_STRun):
         m = self.m
         B, Li, D = img.shape
         Lt = txt.shape[1]
+        self._Lt = Lt
         self._Lil = Li                                                               # local image rows; the attention's keys: all P shards + valid text
         kv_len = (txt_valid.to(self.dev).to(torch.int32) + Li * self.spP).contiguous()
         rope = None if freqs is None else (freqs[0].to(self.dev, F32).contiguous(), freqs[1].to(self.dev, F32).contiguous())
@@ -1484,7 +1587,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  guidance_embed: bool = False, text_projection: str = "single_refiner", use_attention_mask: bool = True,
                  text_states_dim: Optional[int] = None, text_states_dim_2: Optional[int] = None, fp8: bool = False, lora_rank: int = 0,
                  lora_alpha: float = 1.0, dtype=None, device=None, fp8_amax_history: int = 16, fp8_dgrad=False, lora_target_modules=None,
-                 **unused):
+                 lora_dropout: float = 0.0, **unused):
         if text_projection != "single_refiner" or mlp_act_type != "gelu_tanh" or not qkv_bias or not qk_norm or qk_norm_type != "rms":
             raise NotImplementedError("only the shipped HunyuanVideo-T2V configuration (single_refiner, gelu_tanh, rms qk-norm) is built")
         if sum(rope_dim_list) != hidden_size // heads_num:
@@ -1516,7 +1619,7 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
                  "final_layer.adaLN_modulation.1.weight": (2 * D, D), "final_layer.adaLN_modulation.1.bias": (2 * D,)}
         super().__init__(hidden_size, heads_num, mlp_width_ratio, mm_double_blocks_depth, mm_single_blocks_depth, fp8, lora_rank, lora_alpha,
                          shapes_before=before, shapes_after=after, fp8_amax_history=fp8_amax_history,
-                         fp8_dgrad=fp8_dgrad, lora_target_modules=lora_target_modules)
+                         fp8_dgrad=fp8_dgrad, lora_target_modules=lora_target_modules, lora_dropout=lora_dropout)
         self.patch_size, self.in_channels, self.out_channels, self.guidance_embed = tuple(patch_size), in_channels, oc, guidance_embed
         self.text_states_dim, self.text_states_dim_2 = td, td2
 
@@ -1617,16 +1720,6 @@ class HYVideoDiffusionTransformer(HunyuanBlocks):
         dims = (B, tt, th, tw)
         out = _HYFinal.apply(xx, self, vec, Nl, dims, tokens) if xx.requires_grad else _final_forward(self, xx, vec, Nl, dims, tokens)[0]
         return {"x": out} if return_dict else out
-
-    def _sp_rows(self, N: int):
-        """(first row, row count) of this rank's image tokens: everything without sequence parallelism"""
-        if self.sp_group is None:
-            return 0, N
-        import torch.distributed as dist
-        P, r = dist.get_world_size(self.sp_group), dist.get_rank(self.sp_group)
-        if N % P:
-            raise ValueError(f"{N} image tokens do not split over {P} ranks")
-        return r * (N // P), N // P
 
     def patchify(self, x):
         """[B, C_out, T, H, W] -> [B, N, C_out pt ph pw]: the token layout of the final layer's output (the inverse of unpatchify, models.py:702-720);
@@ -1760,7 +1853,17 @@ class HunyuanVideoFlow(torch.nn.Module):
             torch.distributed.broadcast(idx, src, group=group); torch.distributed.broadcast(noise, src, group=group)
         sigma = self.sigmas.to(x0.device)[idx]
         guidance = torch.full((B,), 1000.0, device=x0.device) if self.model.guidance_embed else None
-        return self.loss_from(x0, batch["prompt_embeds"], batch["prompt_attention_mask"], batch["pooled_prompt_embeds"], sigma, noise, guidance)
+        pinned = self.model.lora_dropout_seed
+        if group is not None and pinned is None and self.model.lora_dropout > 0 and self.model.training:
+            # lora_dropout: the ranks that share a sample's rows share its masks -- group rank 0 draws the step's seed (engine's rule)
+            drawn = lora_dropout_seed(self.model)[1] if torch.distributed.get_rank(group) == 0 else 0
+            seed = torch.tensor([drawn], dtype=torch.int64, device=x0.device)
+            torch.distributed.broadcast(seed, src, group=group)
+            self.model.lora_dropout_seed = int(seed.item())
+        try:
+            return self.loss_from(x0, batch["prompt_embeds"], batch["prompt_attention_mask"], batch["pooled_prompt_embeds"], sigma, noise, guidance)
+        finally:
+            self.model.lora_dropout_seed = pinned
 
 
 class _FlowLoss(torch.autograd.Function):

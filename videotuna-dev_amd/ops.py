@@ -847,6 +847,46 @@ def lora_up_add_wide_dgelu_drop(dx, dt, a, n_adapters: int, r: int, rp: int, u, 
           "vt_lora_up_add_wide_dgelu_drop")
 
 
+# ---- the wide _drop products with an origin map (HunyuanVideo): the call's operand is a piece of the adapter's logical input ----
+# origin = (seg_local, seg_global, n_first, off_first, off_rest, k0, K_log): row m of the call (b = m // seg_local, l = m % seg_local) is
+# row m_g = b * seg_global + l + (off_first if l < n_first else off_rest) and column k is column k0 + k of the logical [M_g, K_log] input;
+# the mask element is e = m_g * K_log + k0 + k.  (M, M, 0, 0, 0, 0, K) is the identity: the plain _drop call.  A bad map raises VtError
+# before any launch.
+def _origin(origin):
+    sl, sg, nf, of, orr, k0, klog = (int(v) for v in origin)
+    return sl, sg, nf, of, orr, k0, klog
+
+
+def lora_down_wide_drop_at(x, a, n_adapters: int, r: int, rp: int, ext: int, t_out, K: int, p: float, seed: int, site0: int, origin):
+    _req(x, BF16, "x", 2); _req(a, BF16, "a", 2); _req(t_out, BF16, "t", 2)
+    check(load_library().vt_lora_down_wide_drop_at(x.data_ptr(), x.stride(0), a.data_ptr(), a.stride(0), n_adapters, r, rp, ext,
+                                                   t_out.data_ptr(), t_out.stride(0), x.shape[0], K, float(p), int(seed) & _U64, site0,
+                                                   *_origin(origin), _stream()), "vt_lora_down_wide_drop_at")
+
+
+def lora_tn_wide_drop_at(big, small, R: int, out, osp: int, osr: int, alpha: float, P: int, p: float, seed: int, site: int, origin):
+    _req(big, BF16, "big", 2); _req(small, BF16, "small", 2); _req(out, torch.float32, "out")
+    check(load_library().vt_lora_tn_wide_drop_at(big.data_ptr(), big.stride(0), small.data_ptr(), small.stride(0), R, out.data_ptr(),
+                                                 osp, osr, alpha, big.shape[0], P, float(p), int(seed) & _U64, site, *_origin(origin),
+                                                 _stream()), "vt_lora_tn_wide_drop_at")
+
+
+def lora_up_add_wide_drop_at(dx, dt, a, n_adapters: int, r: int, rp: int, K: int, p: float, seed: int, site0: int, origin):
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    check(load_library().vt_lora_up_add_wide_drop_at(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(), a.stride(0),
+                                                     n_adapters, r, rp, dx.shape[0], K, float(p), int(seed) & _U64, site0,
+                                                     *_origin(origin), _stream()), "vt_lora_up_add_wide_drop_at")
+
+
+def lora_up_add_wide_dgelu_drop_at(dx, dt, a, n_adapters: int, r: int, rp: int, u, K: int, p: float, seed: int, site0: int, origin):
+    _req(dx, BF16, "dx", 2); _req(dt, BF16, "dt", 2); _req(a, BF16, "a", 2)
+    _req_preact(u, dx, K, dt, a, n_adapters * r, n_adapters * rp)
+    check(load_library().vt_lora_up_add_wide_dgelu_drop_at(dx.data_ptr(), dx.stride(0), dt.data_ptr(), dt.stride(0), a.data_ptr(),
+                                                           a.stride(0), n_adapters, r, rp, u.data_ptr(), u.stride(0), dx.shape[0], K,
+                                                           float(p), int(seed) & _U64, site0, *_origin(origin), _stream()),
+          "vt_lora_up_add_wide_dgelu_drop_at")
+
+
 # ---- DoRA (use_dora, csrc/dora.hip): c = m / ||W + s B A|| per output feature, folded into the packed operands ----
 def dora_norm(w, a, b, n_adapters: int, r: int, scale: float, out, mag=None):
     """out[j] = ||w[j] + scale * b[j] @ a||_2, or mag[j] / that norm when mag is given.  w bf16 [n d_out, K], a bf16 [n r, K], b bf16
