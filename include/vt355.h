@@ -14,8 +14,8 @@
  *     no allocation, no host reads of device data -> safe under hipGraph capture;
  *   - return 0 on success, a negative VT_ERR_* otherwise; no C++ exception crosses the ABI;
  *   - compute entry points keep no state between calls and are safe from autograd's backward thread (one process per
- *     GPU, as PL's DDPStrategy runs the reference).  Three process-global TUNING knobs exist for tests and A/B timing only --
- *     vt_gemm_set_tile, vt_conv_set_tile, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
+ *     GPU, as PL's DDPStrategy runs the reference).  Four process-global TUNING knobs exist for tests and A/B timing only --
+ *     vt_gemm_set_tile, vt_gemm_set_big_loop, vt_conv_set_tile, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
  *     they select between kernels that give the same results, the product path never calls them.
  *   - deviation from SURVEY 8(b)'s sketch of this ABI (vt_tensor descriptors, vt_<op>_params structs,
  *     vt_workspace_bytes_<op>, vt_last_error): arguments are flat pointers + leading dimensions (one ctypes call, no struct
@@ -62,6 +62,9 @@ int vt_gemm_set_tile(int mode);
 /* which kernel vt_gemm_bf16 runs for an (M, N, K) problem under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128
  * producer/consumer, 4 = the producer/consumer kernel's 128-row instantiation; < 0 on a bad shape */
 int vt_gemm_bf16_kernel(int M, int N, int K);
+/* K-loop of the 256x256 kernel: 0 = by shape (default), 1 = always the two-phase loop, 2 = always the eight-phase loop (operand
+ * loads in flight across barriers); bit-identical results, tests and A/B timing only */
+int vt_gemm_set_big_loop(int mode);
 /* convolution tile choice: 0 = per shape (default), 1 = always the 128 x 128 kernels, 2 = the 320-wide loader / multiplier kernels whenever
  * Cout % 320 == 0 (tests and A/B timing; csrc/convnd.hip) */
 int vt_conv_set_tile(int mode);

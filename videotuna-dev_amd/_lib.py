@@ -27,6 +27,7 @@ PROTOTYPES = {
     "vt_gemm_bf16": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _fp, _fp, _i, _i, _i,
                      _vp, _i, _vp, _i, _vp],
     "vt_gemm_set_tile": [_i],
+    "vt_gemm_set_big_loop": [_i],
     "vt_gemm_bf16_kernel": [_i, _i, _i],
     "vt_conv_set_tile": [_i],
     "vt_transpose_bf16": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp],

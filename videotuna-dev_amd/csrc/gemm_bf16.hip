@@ -175,6 +175,15 @@ static int pick_tile(int M, int N, int K) {
         const long long passes = (t256 + 255) / 256;
         const bool full = t256 <= 256 ? t256 >= 160 : 10 * t256 >= 9 * passes * 256;
         if (full && (N >= 2560 || ((N % 640) == 0 && N <= 1280) || ((N % 256) >= 192 && K >= 4096))) return 2;
+        // with the eight-phase K-loop (profiles/gemm_big8_kbench.txt: all three kernels interleaved per shape) the 256x256 kernel takes 8-26 %
+        // less time than the producer / consumer kernel at N = 1920 and 1984 for every K (CogVideoX out / ff2 projections and the input gradients
+        // of qkv, out and ff1: 93.75 % and 97 % of the last column tile used), also at 4.3 passes of the chip (M = 35552); it still loses
+        // at 1152 (90 %) and 320.  Only the products with K < 4096 move here (DESIGN.md 8, item 2 has the rest).  What was measured:
+        // the 15/16 rule at N = 1920 and 1984 only, the 85 % pass fill at M = 35552 with those two N only; no other N whose last column
+        // tile is at least 15/16 used was timed
+        const long long nbn = (N + 255) / 256;
+        const bool most = t256 > 256 && 100 * t256 >= 85 * passes * 256;
+        if ((full || most) && K < 4096 && 16LL * N >= 15 * 256 * nbn) return 2;
     }
     if (tpc >= 512 && K >= 512) return 3;
     // a few hundred rows against a large weight (the frozen T5 encoder: 452 x [4096 .. 20480] x [4096 .. 10240]): the weights

@@ -4,11 +4,12 @@
 // videotuna/models/cogvideo_hf/cogvideo_pl.py:865-871, SURVEY 8(a) a4,a5); used for the token-sized problems.
 //
 // Why a second tiling: a wave that owns a 64x64 output tile reads (64+64) x 64 bf16 = 16 KiB of LDS per 64-deep
-// K-tile for 512 Ki flop -- 32 flop per LDS byte, exactly the ratio of the CU's MFMA rate (4096 flop/clk) to its LDS
-// bandwidth (128 B/clk), so the 128x128 kernel can never run the matrix cores above ~50 %.  Here the workgroup tile is
+// K-tile for 512 Ki flop -- 32 flop per LDS byte, against 16 flop per byte that the CU can feed (MFMA rate 4096 flop/clk,
+// ds_read_b128 256 B/clk: MI355X_MICROARCH.md), so the 128x128 kernel keeps the LDS pipe half busy for fragments alone,
+// next to the staging writes and the epilogue.  Here the workgroup tile is
 // 256x256x64 with 8 waves (2 x 4), each wave owning 128x64 = 8x4 tiles of v_mfma_f32_16x16x32_bf16 (128 accumulator
-// registers, two waves per SIMD): 24 KiB of LDS reads per wave per K-tile for 1 Mi flop -> the LDS pipe is ~75 % busy
-// at full MFMA rate.  Operands are staged by LDS-DMA (buffer_load ... lds, XOR swizzle applied to the source chunk),
+// registers, two waves per SIMD): 24 KiB of LDS reads per wave per K-tile for 1 Mi flop -> 43 flop per byte, the LDS
+// pipe is under 40 % busy at full MFMA rate.  Operands are staged by LDS-DMA (buffer_load ... lds, XOR swizzle applied to the source chunk),
 // double-buffered (2 x 64 KiB); the accumulators leave through LDS in eight 32-row slabs so that the epilogue reads
 // residuals / writes C in row-contiguous 512-B segments.
 #include "gemm_epilogue.h"
@@ -24,6 +25,14 @@
 // Staggered staging: waves 0..3 issue their LDS-DMA pieces at the start of a K-tile, waves 4..7 in its middle, so the two waves of a SIMD
 // are never both busy issuing DMA (the issue cost of one hides under the MFMAs of the other): +2-5 %.  The variants that were measured
 // against this body (four waves, loader waves, one piece per k-step, the 32x32x16 body, the timing ablations) are in csrc/exp/README.md.
+//
+// Two K-loops, template PHASED (vt_gemm_set_big_loop; bit-identical results, the choice per shape is big_loop_phased below):
+//   two-phase   one __syncthreads() per K-tile, whose vmcnt(0) retires the next K-tile's LDS-DMA: one K-tile in flight, every K-tile
+//               pays an LDS round trip behind a full drain.
+//   eight-phase cdna_hip_programming.md, "The 256^2 8-phase template": four phases of 16 MFMAs per K-tile between raw s_barriers,
+//               one half-tile of LDS-DMA issued per phase, one counted s_waitcnt vmcnt(6) per K-tile (three half-tiles stay in
+//               flight across it), waves 4-7 one barrier behind waves 0-3 so that on every SIMD one wave multiplies while the
+//               other reads fragments and issues DMA.  The default from 8 K-tiles up, from 2 where N >= 2560 (profiles/gemm_big8_kbench.txt).
 
 typedef int gb_i32x4 __attribute__((ext_vector_type(4)));
 
@@ -36,7 +45,7 @@ __device__ __forceinline__ gb_i32x4 gb_words(const void* base, unsigned bytes) {
 // generation g of slot s computes tile g * G + s.  The first K-tile of the NEXT output tile is fetched while the last
 // K-tile of the current one is multiplied and its epilogue runs, so neither a workgroup launch nor the first HBM round
 // trip of a tile is exposed.
-template <int EPI, bool OUT_F32>
+template <int EPI, bool OUT_F32, bool PHASED>
 __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[2 * GB_STAGE];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -88,6 +97,20 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
         }
     };
 
+    // eight-phase loop: the staging unit is a half-tile = 2 of the wave's 8 pieces.  h = 0: A pieces 0, 2 (rows 0-63 of both wave rows,
+    // read in phase 1), 1: A pieces 1, 3 (rows 64-127 of both, phase 3), 2: W pieces 0, 1, 3: W pieces 2, 3 (phases 1 and 2).  Always
+    // through inline asm: the compiler must not know of these transfers, or it drains them (vmcnt(0)) at its next LDS access.
+    // (m0 is written without being named as a clobber, as in dma_hidden: it is a reserved register on this target -- the compiler
+    // rejects it in a clobber list, keeps no value live in it and sets it itself right before each of its own instructions that read it.)
+    auto half = [&](const gb_i32x4 ra, const gb_i32x4 rw, int kt, int b, int h) {
+        const unsigned dst = smem_lds + b * GB_STAGE + wave * 1024 + (h >= 2 ? 32768 : 0);
+        const int j0 = h == 0 ? 0 : h == 1 ? 1 : h == 2 ? 0 : 2, j1 = h == 0 ? 2 : h == 1 ? 3 : h == 2 ? 1 : 3;
+        const int soff = kt * GB_BK * 2, pstep = h >= 2 ? w_pstep : a_pstep, voff = h >= 2 ? w_voff0 : a_voff0;
+        const gb_i32x4 rs = h >= 2 ? rw : ra;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(dst + j0 * 8192), "v"(voff), "s"(rs), "s"(soff + j0 * pstep) : "memory");
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" :: "s"(dst + j1 * 8192), "v"(voff), "s"(rs), "s"(soff + j1 * pstep) : "memory");
+    };
+
     const int nk = p.K / GB_BK;
     const int fr16 = lane & 15, fq = lane >> 4, fx16 = (fr16 >> 1) & 7;   // 16-row fragments: row, k-chunk of a 32-deep k-step, swz(row)
     const int er = tid >> 6;              // epilogue: 0..7, row inside an 8-row pass
@@ -96,7 +119,12 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
     if (slot >= ntiles) return;
     GemmTile cur = gemm_tile<GB_BM, GB_BN>(p, slot, nbm, nbn);
     int buf = 0;
+    if constexpr (PHASED) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) half(gb_words(cur.a, cur.a_bytes), gb_words(cur.w, cur.w_bytes), 0, 0, h);
+    } else {
     dma(cur, 0, 0);
+    }
     for (int tile = slot; tile < ntiles; tile += gridDim.x) {
         const bool has_next = tile + (int)gridDim.x < ntiles;
         GemmTile nxt = cur;
@@ -109,6 +137,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc16[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+        if constexpr (!PHASED) {
         __syncthreads();                  // vmcnt(0): the first K-tile (fetched during the previous tile) has landed
         for (int kt = 0; kt < nk; ++kt) {
             const bool last = kt + 1 == nk;
@@ -140,6 +169,135 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
             if (!last) __syncthreads();   // its vmcnt(0) also retires the next K-tile's LDS-DMA (in the waves that issued it)
             else gemm_lds_barrier();        // the cross-tile prefetch keeps flying
             buf ^= 1;
+        }
+        } else {
+        // ---- eight-phase loop (cdna_hip_programming.md, "The 256^2 8-phase template"): a K-tile is four phases, one 64 x 32 quadrant of
+        // the wave's 128 x 64 output each (16 MFMAs), in the order (A rows 0-63, W cols 0-31), (0-63, 32-63), (64-127, 32-63),
+        // (64-127, 0-31); the fragment reads are 4 W + 8 A, 4 W, 8 A, none (the first W fragments stay in registers).  Each acc16 tile
+        // still receives K-tile 0 (k-step 0, 1), K-tile 1 (k-step 0, 1), ...: bit-identical to the two-phase loop.
+        // A phase is: fragment reads (W before A, order pinned), one half-tile of LDS-DMA, s_waitcnt lgkmcnt(0), s_barrier, s_setprio 1,
+        // 16 MFMAs, s_setprio 0, s_barrier.  Waves 4-7 take one extra barrier before the loop and waves 0-3 one after it: in the slot
+        // between two barriers one wave of every SIMD is in its MFMA half and the other in its read half.
+        // Staging runs along the stream of K-tiles q = 0 .. nk-1 of this output tile followed by q = nk, the first K-tile of the next
+        // one; K-tile q lives in stage buf ^ (q & 1) (so the next output tile starts in the stage its predecessor's epilogue does not
+        // use).  Every phase issues one half-tile, in the order the stage is vacated:
+        //   phase 1 of K-tile kt: half 1 of kt+1    (its region of the other stage was last read in phase 3 of kt-1)
+        //   phase 2:              half 0 of kt+2    (this stage; last read in phase 1 of kt)
+        //   phase 3:              half 2 of kt+2    (last read in phase 2)
+        //   phase 4:              half 3 of kt+2    (last read in phase 2), then s_waitcnt vmcnt(6): only the three half-tiles of kt+2 stay
+        //                         in flight, K-tile kt+1 has landed in this wave.
+        // Write after read, by the counts: a wave retires the reads of phase p (lgkmcnt(0)) before it enters the first barrier of p;
+        // the late waves enter it one slot after the early ones, and an early wave's DMA of phase p+1 is issued after it has left
+        // that same barrier (its second of phase p).  So restaging one phase after the last read is ordered for both wave groups.
+        // Read after write: the late waves' vmcnt(6) of phase 4 precedes their first barrier of that phase, which is the early waves'
+        // second; the early waves' first read of K-tile kt+1 follows it (phase 1 of kt+1), the late waves' comes a slot later.
+        // K-tile nk+1 does not exist: the last K-tile's stage is the epilogue's slab, so the halves 0, 2, 3 of K-tile 1 of the next
+        // output tile are issued at its start, after the epilogue, followed by the same counted wait (which also covers the epilogue's
+        // stores: they are older).  Without a next output tile nothing is in flight past K-tile nk-1 and the wait before it is vmcnt(0).
+        const bool late = wave >= 4;
+        const gb_i32x4 ra_c = gb_words(cur.a, cur.a_bytes), rw_c = gb_words(cur.w, cur.w_bytes);
+        const gb_i32x4 ra_n = gb_words(nxt.a, nxt.a_bytes), rw_n = gb_words(nxt.w, nxt.w_bytes);
+        {
+            const bool own = nk > 1;
+            if (own || has_next) {
+                half(own ? ra_c : ra_n, own ? rw_c : rw_n, own ? 1 : 0, buf ^ 1, 0);
+                half(own ? ra_c : ra_n, own ? rw_c : rw_n, own ? 1 : 0, buf ^ 1, 2);
+                half(own ? ra_c : ra_n, own ? rw_c : rw_n, own ? 1 : 0, buf ^ 1, 3);
+                asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            asm volatile("s_barrier" ::: "memory");
+            if (late) asm volatile("s_barrier" ::: "memory");       // waves 4-7 run one barrier behind waves 0-3 through the K-loop
+        }
+        bf16x8 fa[4][2], fw0[2][2], fw1[2][2];            // [16-row tile][k-step]
+        auto read_a = [&](const char* As, int qa) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) fa[t][ks] = *(const bf16x8*)(As + (qa * 4 + t) * 2048 + (((ks * 4 + fq) ^ fx16) << 4));
+        };
+        auto read_w = [&](const char* Ws, int qw, bf16x8 (&fw)[2][2]) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) fw[t][ks] = *(const bf16x8*)(Ws + (qw * 2 + t) * 2048 + (((ks * 4 + fq) ^ fx16) << 4));
+        };
+        auto mfma_head = [&]() {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this phase's reads are retired before the wave enters the barrier
+            asm volatile("s_barrier" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_setprio(1);
+        };
+        auto mfma_tail = [&]() {
+            __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_barrier" ::: "memory");
+        };
+#define GB_QUADRANT(QA, QW, FW)                                                                                                   \
+    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                               \
+    _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                                  \
+    _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                                  \
+        acc16[(QW) * 2 + u][(QA) * 4 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(FW[u][ks], fa[t][ks], acc16[(QW) * 2 + u][(QA) * 4 + t], 0, 0, 0);
+        // STEADY: kt + 2 < nk, so every half-tile is of this output tile and the wait is vmcnt(6); otherwise one of the last two K-tiles
+        auto ktile = [&](int kt, int b, auto steady) {
+            constexpr bool STEADY = decltype(steady)::value;
+            const bool own1 = STEADY || kt + 1 < nk, own2 = STEADY || kt + 2 < nk;
+            const bool i1 = own1 || has_next;                            // K-tile kt + 1 of the stream exists (kt + 1 <= nk)
+            const bool i2 = own2 || (kt + 2 == nk && has_next);          // K-tile kt + 2 of the stream exists
+            const gb_i32x4 ra1 = own1 ? ra_c : ra_n, ra2 = own2 ? ra_c : ra_n, rw2 = own2 ? rw_c : rw_n;
+            const int k1 = own1 ? kt + 1 : 0, k2 = own2 ? kt + 2 : 0;
+            const char* As = smem + b * GB_STAGE + (wm * 128 + fr16) * 128;
+            const char* Ws = smem + b * GB_STAGE + 32768 + (wn * 64 + fr16) * 128;
+            // phase 1
+            read_w(Ws, 0, fw0);
+            __builtin_amdgcn_sched_barrier(0);
+            read_a(As, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i1) half(ra1, ra1, k1, b ^ 1, 1);
+            mfma_head();
+            GB_QUADRANT(0, 0, fw0)
+            mfma_tail();
+            // phase 2
+            read_w(Ws, 1, fw1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i2) half(ra2, rw2, k2, b, 0);
+            mfma_head();
+            GB_QUADRANT(0, 1, fw1)
+            mfma_tail();
+            // phase 3
+            read_a(As, 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i2) half(ra2, rw2, k2, b, 2);
+            mfma_head();
+            GB_QUADRANT(1, 1, fw1)
+            mfma_tail();
+            // phase 4
+            if (i2) half(ra2, rw2, k2, b, 3);
+            if (STEADY || kt + 1 < nk) {                                 // K-tile kt + 1 is read from the next phase on
+                if (i2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // last output tile of this workgroup, K-tile nk - 2 only
+            }
+            mfma_head();
+            GB_QUADRANT(1, 0, fw0)
+            mfma_tail();
+        };
+        int kt = 0;
+        for (; kt + 4 <= nk; kt += 2) {                   // two K-tiles = eight phases per iteration
+            ktile(kt, buf, std::true_type());
+            ktile(kt + 1, buf ^ 1, std::true_type());
+        }
+        if (kt + 3 <= nk) {
+            ktile(kt, buf, std::true_type());
+            ++kt;
+            buf ^= 1;
+        }
+        for (; kt < nk; ++kt) {                           // the last two K-tiles (one if nk == 1)
+            ktile(kt, buf, std::false_type());
+            buf ^= 1;
+        }
+        if (!late) asm volatile("s_barrier" ::: "memory");         // back in step for the epilogue
+#undef GB_QUADRANT
         }
 
         // ---------------- epilogue: eight 32-row slabs through the stage that was just consumed ----------------
@@ -193,6 +351,23 @@ __global__ __launch_bounds__(512, 1) void gemm_tn_big_kernel(GemmParams p) {
     }
 }
 
+// K-loop of gemm_tn_big_kernel: 0 = choose by shape, 1 = two-phase, 2 = eight-phase (tests and A/B timing; same results either way)
+static int g_big_loop = 0;
+extern "C" int vt_gemm_set_big_loop(int mode) {
+    if (mode < 0 || mode > 2) return VT_ERR_BAD_SHAPE;
+    g_big_loop = mode;
+    return VT_OK;
+}
+static bool big_loop_phased(const GemmParams& p) {
+    if (g_big_loop) return g_big_loop == 2;
+    // profiles/gemm_big8_kbench.txt (both loops interleaved in one process): the eight-phase loop is ahead by more than the spread
+    // from 8 K-tiles up at N = 640 and 5120 (and at every larger K-tile count measured; on one shape a 9 % lead is inside the
+    // two-phase arm's own spread), and from 2 K-tiles up
+    // at N = 2560 and 5120; it ties at 6 K-tiles with N = 640 and is behind at one K-tile (all prologue) and at N = 320 with 5
+    const int nk = p.K / GB_BK;
+    return nk >= 8 || (nk >= 2 && p.N >= 2560);
+}
+
 template <int EPI, bool F32>
 static int launch_big(const GemmParams& p, hipStream_t st) {
     const int nbm = (p.M + GB_BM - 1) / GB_BM, nbn = (p.N + GB_BN - 1) / GB_BN;
@@ -204,7 +379,8 @@ static int launch_big(const GemmParams& p, hipStream_t st) {
     }
     const int ntiles = nbm * nbn;
     const int grid = ntiles < slots ? (ntiles + 7) / 8 * 8 : slots;
-    hipLaunchKernelGGL((gemm_tn_big_kernel<EPI, F32>), dim3(grid), dim3(512), 0, st, p);
+    if (big_loop_phased(p)) hipLaunchKernelGGL((gemm_tn_big_kernel<EPI, F32, true>), dim3(grid), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL((gemm_tn_big_kernel<EPI, F32, false>), dim3(grid), dim3(512), 0, st, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 

@@ -468,6 +468,11 @@ def gemm_set_tile(mode: int = 0):
     check(load_library().vt_gemm_set_tile(mode), "vt_gemm_set_tile")
 
 
+def gemm_set_big_loop(mode: int = 0):
+    """K-loop of the 256x256 kernel: 0 = by shape, 1 = always two-phase, 2 = always eight-phase (bit-identical; tuning / test knob)"""
+    check(load_library().vt_gemm_set_big_loop(mode), "vt_gemm_set_big_loop")
+
+
 def gemm_kernel(M: int, N: int, K: int) -> int:
     """the kernel vt_gemm_bf16 runs for this shape under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128 producer / consumer,
     4 = the producer / consumer kernel's 128-row instantiation"""
