@@ -192,6 +192,10 @@ long long vt_attn_bwd_chain_ws_bytes(int B, int H, int S);
 /* tuning / test knob: chain_len 1 = atomics only, 0 = default (3, or VT_BWD_CHAIN); slots 0 = one workgroup per CU,
  * else a smaller persistent grid (multiple of 8) so that small problems run several generations */
 int vt_attn_bwd_set_chain(int chain_len, int slots);
+/* host-only query, no launch: the plan vt_attn_bwd_hd64 follows for this problem under the current knobs.  have_ws != 0: the caller hands
+ * a chain workspace.  chain_len: 1 = every key block adds its dQ atomically, L > 1 = runs of up to L key blocks hand their dQ tiles on;
+ * grid: workgroups of the persistent launch; generations: key blocks a workgroup sweeps at most.  Each output pointer may be NULL. */
+int vt_attn_bwd_chain_plan(int B, int H, int S, int have_ws, int* chain_len, int* grid, int* generations);
 
 /* y = LayerNorm(x; gamma, beta, eps) * (1 + scale[b,seg]) + shift[b,seg]; gamma/beta may be NULL (no
  * affine), the four modulation pointers may be NULL (plain LayerNorm).  mean/rstd [M] fp32 optional.

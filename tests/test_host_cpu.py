@@ -24,6 +24,18 @@ def test_library_exports_every_declared_symbol():
     assert lib.vt_error_string(-1).decode().startswith("bad shape")
 
 
+def test_attn_bwd_chain_plan_is_a_host_query():
+    """it launches nothing and needs no device: without one the persistent grid falls back to its minimum of 8 slots, nothing can chain
+    (chain length <= grid / 8 = 1) and the key blocks are swept in generations of 8"""
+    from vt355 import ops
+    from vt355._lib import VtError
+    L, grid, gens = ops.attn_bwd_chain_plan(1, 6, 600)                         # 3 key blocks x 6 heads = 18 items
+    assert (L, grid, gens) == ((3, 24, 1) if torch.cuda.is_available() else (1, 8, 3))
+    assert ops.attn_bwd_chain_plan(1, 1, 64, have_ws=False) == (1, 8, 1)
+    with pytest.raises(VtError, match="vt_attn_bwd_chain_plan"):
+        ops.attn_bwd_chain_plan(1, 0, 600)
+
+
 def test_no_cpu_fallback():
     from vt355 import ops
     from vt355.dit import CogVideoXTransformer3DModel

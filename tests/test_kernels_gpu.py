@@ -133,10 +133,12 @@ def test_attn_fwd(dev, B, S, H, spike, pre):
 @pytest.mark.parametrize("B,S,H,spike", [(1, 64, 1, False), (2, 100, 2, False), (1, 333, 3, True), (1, 700, 2, False), (1, 256, 1, False),
                                          (1, 3000, 2, False), (2, 2700, 3, True)])
 def test_attn_bwd(dev, B, S, H, spike, pre, chain):
-    """chain 0: one workgroup per key block, pure atomics.  chain 1: persistent grid, runs of consecutive key blocks
-    hand their dQ tiles to each other (12 / 11 key blocks per head in the two long cases: chains of up to 8, cut at
-    head ends and XCD slot-range ends).  chain 2: the same on a 24-slot grid -> several generations per slot, chains
-    of 3, slots that change role between generations."""
+    """chain 0: no workspace, every key block adds its dQ atomically.  chain 1: with the workspace; in the two long cases (12 / 11 key blocks
+    per head) runs of consecutive key blocks hand their dQ tiles to each other: chains of 3 (the default length), cut at head ends and XCD
+    slot-range ends.  The cases with S <= 700 have at most 8 workgroups, the chain length is clamped to grid / 8 = 1 and they run the
+    atomics path although a workspace is given (vt_attn_bwd_chain_plan says so below; tests/test_attn64_gpu.py has the small shapes that
+    do chain).  chain 2: the long cases on a 24-slot grid -> several generations per slot, chains of 3, slots that change role between
+    generations."""
     if S > 1000 and not pre:
         pytest.skip("long cases run once (prescaled, the engine's configuration)")
     if chain == 2 and S < 1000:
@@ -163,6 +165,8 @@ def test_attn_bwd(dev, B, S, H, spike, pre, chain):
     ws = ops.attn_bwd_chain_workspace(B, H, S, dev) if chain else None
     assert (ws is not None) == bool(chain)
     try:
+        planned = ops.attn_bwd_chain_plan(B, H, S, have_ws=ws is not None)[0]
+        assert planned == (3 if chain and S > 1000 else 1), "the launch would not take the path this id names"
         ops.attn_bwd(qd, kd, vd, o, do.to(dev, BF).view(B, S, D), lse2, delta, dq, dk, dv, B, H, S, q_prescaled=pre, chain_ws=ws)
         if chain:
             assert ops.attn_bwd_chain_error(ws) == 0

@@ -719,6 +719,32 @@ extern "C" int VT_CAT(vt_attn_bwd_set_chain, VT_SUFFIX)(int chain_len, int slots
     return VT_OK;
 }
 
+// The launch plan of a problem: key blocks per head, workgroups, the persistent grid and the chain length the launch really uses.  The entry
+// point and vt_attn_bwd_chain_plan both read it from here.
+struct BwdPlan { int nkb; long long nwg, grid; int L; };
+static BwdPlan bwd_plan(int B, int H, int S) {
+    BwdPlan pl;
+    pl.L = bwd_chain_len();
+    pl.nkb = (S + 255) / 256;
+    pl.nwg = (long long)pl.nkb * H * B;
+    pl.grid = pl.nwg < g_bwd_slots ? (pl.nwg + 7) / 8 * 8 : g_bwd_slots;      // persistent grid, a multiple of 8
+    if (pl.L > pl.grid / 8) pl.L = (int)(pl.grid / 8);
+    if (pl.L > pl.nkb) pl.L = pl.nkb;
+    return pl;
+}
+// host-only query (no launch): what vt_attn_bwd_hd64 would do for this problem under the current vt_attn_bwd_set_chain / VT_BWD_CHAIN state.
+// have_ws: the caller hands a chain workspace of vt_attn_bwd_chain_ws_bytes.  chain_len 1 = every key block adds its dQ atomically;
+// generations = key blocks a slot of the persistent grid sweeps at most.  Any of the three outputs may be NULL.
+extern "C" int VT_CAT(vt_attn_bwd_chain_plan, VT_SUFFIX)(int B, int H, int S, int have_ws, int* chain_len, int* grid, int* generations) {
+    if (B <= 0 || H <= 0 || S <= 0) return VT_ERR_BAD_SHAPE;
+    const BwdPlan pl = bwd_plan(B, H, S);
+    if (pl.nwg > 0x3fffffLL) return VT_ERR_BAD_SHAPE;
+    if (chain_len) *chain_len = (have_ws && pl.L > 1) ? pl.L : 1;
+    if (grid) *grid = (int)pl.grid;
+    if (generations) *generations = (int)((pl.nwg + pl.grid - 1) / pl.grid);
+    return VT_OK;
+}
+
 extern "C" int BWD_ENTRY(const void* q, const void* k, const void* v, const void* o, const void* dout,
                                 const float* lse2, float* delta_ws, float* dq_f32, void* dk, void* dv,
                                 int B, int H, int S,
@@ -751,16 +777,12 @@ extern "C" int BWD_ENTRY(const void* q, const void* k, const void* v, const void
     p.q_rs = q_rs; p.k_rs = k_rs; p.v_rs = v_rs; p.do_rs = do_rs; p.dq_rs = dq_rs; p.dk_rs = dk_rs; p.dv_rs = dv_rs;
     p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = v_bs; p.do_bs = do_bs; p.dq_bs = dq_bs; p.dk_bs = dk_bs; p.dv_bs = dv_bs;
     p.scale = softmax_scale; p.scale_log2 = softmax_scale * 1.4426950408889634f;
-    const int nkb = (S + 255) / 256;
-    const long long nwg = (long long)nkb * H * B;
-    if (nwg > 0x3fffffLL) return VT_ERR_BAD_SHAPE;
+    const BwdPlan pl = bwd_plan(B, H, S);
+    if (pl.nwg > 0x3fffffLL) return VT_ERR_BAD_SHAPE;
     // dQ hand-off chains: need the caller's workspace and enough co-resident workgroups per XCD (see the header comment)
     p.chain_len = 1; p.chain_ctr = nullptr; p.chain_flags = nullptr; p.chain_xcc = nullptr; p.chain_tiles = nullptr;
-    int L = bwd_chain_len();
-    const long long pgrid = nwg < g_bwd_slots ? (nwg + 7) / 8 * 8 : g_bwd_slots;      // persistent grid, a multiple of 8
-    const long long grid = pgrid;
-    if (L > pgrid / 8) L = (int)(pgrid / 8);
-    if (L > nkb) L = nkb;
+    const int L = pl.L;
+    const long long grid = pl.grid;
     if (chain_ws != nullptr && chain_ws_bytes >= 64 && !(((uintptr_t)chain_ws) & 255)) {
         char* ws = (char*)chain_ws;
         const bool on = L > 1 && chain_ws_bytes >= bwd_chain_ws_bytes(g_bwd_slots);

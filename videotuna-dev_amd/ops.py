@@ -487,6 +487,15 @@ def attn_bwd_set_chain(chain_len: int = 0, slots: int = 0):
     check(load_library().vt_attn_bwd_set_chain(chain_len, slots), "vt_attn_bwd_set_chain")
 
 
+def attn_bwd_chain_plan(B: int, H: int, S: int, have_ws: bool = True):
+    """(chain_len, grid, generations) of the launch vt_attn_bwd_hd64 would make for this problem under the current knobs; no launch.
+    chain_len 1: every key block adds its dQ atomically (always so without a workspace)"""
+    import ctypes as C
+    L, grid, gens = C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load_library().vt_attn_bwd_chain_plan(B, H, S, int(have_ws), C.byref(L), C.byref(grid), C.byref(gens)), "vt_attn_bwd_chain_plan")
+    return L.value, grid.value, gens.value
+
+
 def attn_bwd_chain_error(chain_ws: torch.Tensor) -> int:
     """error word of the last launch that used this workspace (synchronises): non-zero = a hand-off wait timed out"""
     return int(chain_ws[32:36].view(torch.int32).item())
