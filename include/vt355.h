@@ -164,6 +164,24 @@ int vt_causal_conv3d_in8_cl(const void* x, const void* wk, const void* bias, voi
  * for an EVEN frame count): avg_pool1d(2, 2) over all frames, y bf16 [N, T/2, HW, C].  Channels-last. */
 int vt_temporal_pool_cl(const void* x, long long ldx, void* y, long long ldy, int N, int T, long long HW, int C, int keep_first,
                         void* stream);
+/* SpatialNorm3D (+ SiLU) of the VAE decoder: y = silu?( ((x - mean) * rstd * gamma + beta) * mod_y[n,tz,hz,wz,c] + mod_b[n,tz,hz,wz,c] ).
+ * x, y: bf16 [N,T,H,W,C] channels-last (position stride ldx / ldy); mod: bf16 [N,Tz,Hz,Wz,2C] contiguous = (conv_y(zq) | conv_b(zq)) at
+ * LATENT resolution (1x1x1 convolutions commute with nearest interpolation: one GEMM over the latent's positions, no upsampled zq is
+ * stored); hz = h / (H/Hz), wz = w / (W/Wz); T > 1: tz = 0 for t = 0, else 1 + (t-1) / ((T-1)/(Tz-1)); T == 1: tz = 0; the ratios must
+ * be powers of two.  Statistics and ws as vt_groupnorm_silu_cl; 64-bit offsets (x / y may exceed 4 GiB).
+ * Replaces: SpatialNorm3D.forward (cogvideo_sat/vae_modules/cp_enc_dec.py:462-539: two F.interpolate, two 1x1x1 convolutions over the
+ * upsampled latent, GroupNorm, multiply, add) + nonlinearity (:753, :766, :1064) of ContextParallelDecoder3D. */
+int vt_spatialnorm_silu_cl(const void* x, long long ldx, const void* gamma, const void* beta, const void* mod, void* y, long long ldy,
+                           int N, int T, int H, int W, int C, int Tz, int Hz, int Wz, int G, float eps, int silu, float* ws,
+                           long long ws_bytes, void* stream);
+/* Upsample3D.forward in one implicit-GEMM launch: nearest 2x in h / w (tup != 0 and T > 1: also in t with frame 0 kept single,
+ * To = 1 + 2 (T-1), output frame t reads input frame 0 for t = 0, else 1 + (t-1)/2; otherwise To = T), then the per-frame 3x3 Conv2d:
+ *   y[n,t,h,w,co] = bias[co] + sum_{dh,dw,ci} x[n, ts(t), (h+dh-1)>>1, (w+dw-1)>>1, ci] * wk[co,(dh,dw),ci]
+ * zero where h+dh-1 / w+dw-1 leaves [0,2H) / [0,2W).  x: bf16 [N,T,H,W,Cin], wk: bf16 [Cout, 9*Cin], y: bf16 [N,To,2H,2W,Cout].
+ * Cin % 64 == 0, Cout % 4 == 0; descriptors rebased per tile, 64-bit stores: any size of x and y.  The upsampled tensor is never stored.
+ * Replaces: Upsample3D.forward (cogvideo_sat/vae_modules/cp_enc_dec.py:560-622: F.interpolate per 32-channel split, torch.cat, Conv2d). */
+int vt_upsample_conv2d_cl(const void* x, long long ldx, const void* wk, const void* bias, void* y, long long ldy,
+                          int N, int T, int H, int W, int Cin, int Cout, int tup, void* stream);
 /* T5LayerNorm: y[m,:] = x[m,:] * rsqrt(mean(x[m,:]^2) + eps) * w  (bf16 rows of D, fp32 statistics; no mean, no bias) */
 int vt_rmsnorm_bf16(const void* x, long long ldx, const void* w, void* y, long long ldy, long long M, int D, float eps,
                     void* stream);

@@ -19,7 +19,11 @@ struct Conv3dParams {
     int Ho, Wo;            // output lines / pixels (H, W at stride 1; H/2, W/2 for the stride-2 downsample)
     long long ldx;         // position stride of x in elements (>= Cin)
     long long x_rows;      // N*T*H*W
+    int To, tup;           // UP only: output frames; tup != 0: nearest 2x in t with frame 0 kept single (To = 1 + 2 (T - 1))
 };
+
+// input frame of output frame t of the fused nearest upsample (Upsample3D, compress_time: the first frame is upsampled on its own)
+__device__ __forceinline__ int up_src_frame(int t, int tup) { return (tup && t > 0) ? 1 + ((t - 1) >> 1) : t; }
 
 #define CV_BM 128
 #define CV_BN 128
@@ -31,7 +35,10 @@ struct Conv3dParams {
 // downsample -- no padding on top / left, one zero line / column at the bottom / right), EPI = EPI_BIAS or EPI_GATED_RES (+ residual).
 // IN8: the first convolution of the encoder (RGB input): x has 8 channels per position (3 used) = ONE 16-byte chunk, and a K-tile
 // of 64 holds 8 TAPS x 8 channels instead of 64 channels of one tap -- 4 K-tiles (32 tap slots, 27 used) instead of 27.
-template <int KT, int STRIDE, int EPI, bool IN8 = false>
+// UP (KT = 1, STRIDE = 1): the convolution reads the nearest-2x upsampled input without it being stored -- the output has 2H x 2W
+// positions per frame and cp.To frames, tap (dh, dw) of output (t, h, w) is input (up_src_frame(t), (h+dh-1) >> 1, (w+dw-1) >> 1),
+// zero where h+dh-1 / w+dw-1 leaves the UPSAMPLED image.
+template <int KT, int STRIDE, int EPI, bool IN8 = false, bool UP = false>
 __global__ __launch_bounds__(256, 2) void conv3d_cl_kernel(Conv3dParams cp) {
     constexpr int PAD = STRIDE == 1 ? 1 : 0;
     __shared__ __attribute__((aligned(16))) char smem[65536];
@@ -51,9 +58,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_cl_kernel(Conv3dParams cp) {
     long long base_row;
     {
         const long long nt = (long long)row0 / HWo;
-        const int t0 = (int)(nt % cp.T);
+        const int To = UP ? cp.To : cp.T;
+        const int t0 = (int)(nt % To);
         int tt = t0 - (KT - 1); tt = tt < 0 ? 0 : tt;
-        base_row = ((nt / cp.T) * cp.T + tt) * (long long)HW;
+        if (UP) tt = up_src_frame(t0, cp.tup);
+        base_row = ((nt / To) * cp.T + tt) * (long long)HW;
     }
     const long long a_rem = (cp.x_rows - base_row) * cp.ldx * 2;
     __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A + base_row * cp.ldx, (unsigned)(a_rem > 0x7fffffffLL ? 0x7fffffffLL : a_rem));
@@ -75,10 +84,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_cl_kernel(Conv3dParams cp) {
         if (m < p.M) {
             const int sp = (int)(m % HWo);
             const long long nt = m / HWo;
-            rt[j] = (int)(nt % cp.T);
+            const int To = UP ? cp.To : cp.T;
+            rt[j] = (int)(nt % To);
+            if (UP) rt[j] = up_src_frame(rt[j], cp.tup);
             rh[j] = sp / cp.Wo;
             rw_[j] = sp - rh[j] * cp.Wo;
-            rfr[j] = (nt / cp.T) * cp.T * (long long)HW - base_row;
+            rfr[j] = (nt / To) * cp.T * (long long)HW - base_row;
         } else {
             rt[j] = -1; rh[j] = 0; rw_[j] = 0; rfr[j] = 0;
         }
@@ -92,8 +103,12 @@ __global__ __launch_bounds__(256, 2) void conv3d_cl_kernel(Conv3dParams cp) {
         for (int j = 0; j < 4; ++j) {
             int tt = rt[j] + dt - (KT - 1);
             tt = tt < 0 ? 0 : tt;                                   // causal: frames before the first one are the first one
-            const int hh = rh[j] * STRIDE + dh - PAD, ww = rw_[j] * STRIDE + dw - PAD;
-            const bool ok = rt[j] >= 0 && hh >= 0 && hh < cp.H && ww >= 0 && ww < cp.W && (!IN8 || tap < KT * 9);
+            int hh = rh[j] * STRIDE + dh - PAD, ww = rw_[j] * STRIDE + dw - PAD;
+            bool ok = rt[j] >= 0 && hh >= 0 && hh < cp.H && ww >= 0 && ww < cp.W && (!IN8 || tap < KT * 9);
+            if (UP) {                                               // (hh, ww) is a position of the upsampled image
+                ok = rt[j] >= 0 && hh >= 0 && hh < cp.Ho && ww >= 0 && ww < cp.Wo;
+                hh >>= 1; ww >>= 1;
+            }
             const long long r = rfr[j] + (long long)tt * HW + (long long)hh * cp.W + ww;
             a_voff[j] = ok ? (unsigned)(r * cp.ldx * 2 + (IN8 ? 0 : chunk_off)) : CV_OOB;
         }
@@ -394,7 +409,7 @@ static int conv_launch(const void* x, long long ldx, const void* wk, const void*
     p.R = (const bf16_t*)res; p.gate_txt = nullptr; p.gate_vid = nullptr; p.C2 = nullptr; p.U = nullptr;
     p.M = (int)rows_out; p.N = Cout; p.K = KT * 9 * Cin; p.lda = (int)ldx; p.ldw = KT * 9 * Cin; p.ldc = (int)ldy; p.ldr = (int)ldr;
     p.ldc2 = 0; p.ldu = 0; p.S = 1; p.St = 0; p.gate_bstride = 0; p.r_mod = 0; p.splits = 1;
-    cp.T = T; cp.H = H; cp.W = W; cp.Cin = Cin; cp.Ho = Ho; cp.Wo = Wo; cp.ldx = ldx; cp.x_rows = rows_in;
+    cp.T = T; cp.H = H; cp.W = W; cp.Cin = Cin; cp.Ho = Ho; cp.Wo = Wo; cp.ldx = ldx; cp.x_rows = rows_in; cp.To = T; cp.tup = 0;
     // kernel: the producer / consumer one (256-row tiles, persistent) where it was measured faster; VT_CONV_KERNEL=1|2 forces the
     // 128-row / the producer-consumer kernel
     static int kmode = -1, slots = 0;
@@ -456,8 +471,38 @@ extern "C" int vt_causal_conv3d_in8_cl(const void* x, const void* wk, const void
     p.R = nullptr; p.gate_txt = nullptr; p.gate_vid = nullptr; p.C2 = nullptr; p.U = nullptr;
     p.M = (int)rows; p.N = Cout; p.K = 256; p.lda = 8; p.ldw = 256; p.ldc = (int)ldy; p.ldr = 0; p.ldc2 = 0; p.ldu = 0;
     p.S = 1; p.St = 0; p.gate_bstride = 0; p.r_mod = 0; p.splits = 1;
-    cp.T = T; cp.H = H; cp.W = W; cp.Cin = 8; cp.Ho = H; cp.Wo = W; cp.ldx = 8; cp.x_rows = rows;
+    cp.T = T; cp.H = H; cp.W = W; cp.Cin = 8; cp.Ho = H; cp.Wo = W; cp.ldx = 8; cp.x_rows = rows; cp.To = T; cp.tup = 0;
     const int nbm = (p.M + CV_BM - 1) / CV_BM, nbn = (Cout + CV_BN - 1) / CV_BN;
     hipLaunchKernelGGL((conv3d_cl_kernel<3, 1, EPI_BIAS, true>), dim3(nbm * nbn), dim3(256), 0, (hipStream_t)stream, cp);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
+// Upsample3D.forward (cp_enc_dec.py:560-622) in one implicit-GEMM launch: nearest 2x in h and w -- with tup != 0 and T > 1 also in t,
+// frame 0 kept single: To = 1 + 2 (T - 1), output frame t reads input frame 0 (t = 0) or 1 + (t - 1) / 2 -- then the per-frame 3x3
+// convolution with zero padding 1, the upsampled tensor never stored.  x: bf16 [N,T,H,W,Cin] (position stride ldx); wk: bf16
+// [Cout, 9 * Cin] (pack_conv_weight of the Conv2d weight); y: bf16 [N,To,2H,2W,Cout] (position stride ldy).  Cin % 64 == 0,
+// Cout % 4 == 0.  The A descriptor is rebased per tile and the store is 64-bit: x and y may be of any size.
+extern "C" int vt_upsample_conv2d_cl(const void* x, long long ldx, const void* wk, const void* bias, void* y, long long ldy,
+                                     int N, int T, int H, int W, int Cin, int Cout, int tup, void* stream) {
+    if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % CV_BK) || (Cout % 4)) return VT_ERR_BAD_SHAPE;
+    if ((ldx % 8) || (ldy % 4) || ldx < Cin || ldy < Cout) return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)x) | ((uintptr_t)wk) | ((uintptr_t)y)) & 15) return VT_ERR_BAD_ALIGN;
+    if (H > 16384 || W > 16384) return VT_ERR_BAD_SHAPE;
+    tup = (tup && T > 1) ? 1 : 0;
+    const int To = tup ? 1 + 2 * (T - 1) : T, Ho = 2 * H, Wo = 2 * W;
+    const long long rows_in = (long long)N * T * H * W, rows_out = (long long)N * To * Ho * Wo;
+    // 31-bit byte offsets from the start of the first input frame a tile touches: the frames its 128 output rows can reach
+    const long long span = (((long long)CV_BM / ((long long)Ho * Wo) + 3) * H * W + 256) * ldx * 2;
+    if (rows_out >= 0x7fffffffLL || span >= 0x7fffffffLL || 9LL * Cin * 2 * CV_BN >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+    Conv3dParams cp;
+    GemmParams& p = cp.g;
+    p.A = (const bf16_t*)x; p.W = (const bf16_t*)wk; p.C = y; p.bias = (const bf16_t*)bias;
+    p.R = nullptr; p.gate_txt = nullptr; p.gate_vid = nullptr; p.C2 = nullptr; p.U = nullptr;
+    p.M = (int)rows_out; p.N = Cout; p.K = 9 * Cin; p.lda = (int)ldx; p.ldw = 9 * Cin; p.ldc = (int)ldy; p.ldr = 0;
+    p.ldc2 = 0; p.ldu = 0; p.S = 1; p.St = 0; p.gate_bstride = 0; p.r_mod = 0; p.splits = 1;
+    cp.T = T; cp.H = H; cp.W = W; cp.Cin = Cin; cp.Ho = Ho; cp.Wo = Wo; cp.ldx = ldx; cp.x_rows = rows_in; cp.To = To; cp.tup = tup;
+    const long long nbm = (rows_out + CV_BM - 1) / CV_BM, nbn = (Cout + CV_BN - 1) / CV_BN;
+    if (nbm * nbn >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+    hipLaunchKernelGGL((conv3d_cl_kernel<1, 1, EPI_BIAS, false, true>), dim3((unsigned)(nbm * nbn)), dim3(256), 0, (hipStream_t)stream, cp);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }

@@ -168,6 +168,92 @@ extern "C" int vt_groupnorm_silu_cl(const void* x, long long ldx, const void* ga
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// SpatialNorm3D (+ SiLU) of the CogVideoX VAE decoder (cp_enc_dec.py:462-539):  y = silu?( GroupNorm(x) * conv_y(zq^) + conv_b(zq^) ),
+// zq^ = the latent nearest-interpolated to x's size with the first frame handled apart.  conv_y / conv_b are 1x1x1, so they commute with
+// the interpolation: the host computes them ONCE at latent resolution (one GEMM) into mod [N, Tz, Hz, Wz, 2C] = (Y | B) and this apply
+// pass gathers from that table (L2-resident: 13x60x90 positions x 2C) -- no upsampled zq is ever stored.  Index rule (ratios are powers of
+// two, the host checks): hz = h >> sh, wz = w >> sw;  T > 1: tz = 0 for t = 0, else 1 + ((t-1) >> st);  T == 1: tz = 0.
+// Statistics: the two passes above, unchanged.  Positions of one sample are indexed in 32 bits (the host bounds P * C/8 < 2^31), every
+// element offset is 64-bit: x / y may lie past 2 / 4 GiB.
+template <bool SILU>
+__global__ __launch_bounds__(GN_THREADS) void spn_apply_kernel(const bf16_t* x, long long ldx, bf16_t* y, long long ldy, const bf16_t* mod,
+                                                               int T, int H, int W, int C, int Tz, int Hz, int Wz, int st, int sh, int sw,
+                                                               const float* ws) {
+    const int n = blockIdx.y;
+    const unsigned nch = C >> 3, HW = (unsigned)H * W;
+    const float* a = ws + (size_t)n * 4 * C + 2 * C;
+    const float* b = a + C;
+    const unsigned total = (unsigned)T * HW * nch;
+    const long long xbase = (long long)n * T * HW;
+    const long long zbase = (long long)n * Tz * Hz * Wz;
+    for (unsigned i = blockIdx.x * GN_THREADS + threadIdx.x; i < total; i += gridDim.x * GN_THREADS) {
+        const unsigned p = i / nch;
+        const int c = (int)(i - p * nch) * 8;
+        const unsigned t = p / HW, r = p - t * HW;
+        const unsigned h = r / (unsigned)W, w = r - h * (unsigned)W;
+        const int tz = (T > 1 && t > 0) ? 1 + (int)((t - 1) >> st) : 0;
+        const long long zrow = zbase + ((long long)tz * Hz + (h >> sh)) * Wz + (w >> sw);
+        float v[8], my[8], mb[8];
+        unpack8(*(const u32x4*)(x + (xbase + p) * ldx + c), v);
+        unpack8(*(const u32x4*)(mod + zrow * (2LL * C) + c), my);
+        unpack8(*(const u32x4*)(mod + zrow * (2LL * C) + C + c), mb);
+        const f32x4 a0 = *(const f32x4*)(a + c), a1 = *(const f32x4*)(a + c + 4), b0 = *(const f32x4*)(b + c), b1 = *(const f32x4*)(b + c + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = (v[j] * a0[j] + b0[j]) * my[j] + mb[j];
+            v[j + 4] = (v[j + 4] * a1[j] + b1[j]) * my[j + 4] + mb[j + 4];
+        }
+        if (SILU) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = v[j] * (1.0f - __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(v[j] * 1.4426950408889634f) + 1.0f));
+        }
+        *(u32x4*)(y + (xbase + p) * ldy + c) = pack8(v);
+    }
+}
+
+static int pow2_shift(int big, int small) {          // log2(big / small) when that ratio is a power of two, else -1
+    if (small <= 0 || big % small) return -1;
+    const int r = big / small;
+    if (r & (r - 1)) return -1;
+    int s = 0;
+    while ((1 << s) < r) ++s;
+    return s;
+}
+
+// x, y: bf16 [N, T, H, W, C] channels-last with position stride ldx / ldy; gamma / beta: bf16 [C] or null; mod: bf16 [N, Tz, Hz, Wz, 2C]
+// contiguous (conv_y(zq) | conv_b(zq) at latent resolution); ws as for vt_groupnorm_silu_cl.  H / Hz, W / Wz and (T-1) / (Tz-1) must be
+// powers of two (T > 1 needs Tz > 1; T == 1 reads latent frame 0).
+extern "C" int vt_spatialnorm_silu_cl(const void* x, long long ldx, const void* gamma, const void* beta, const void* mod, void* y,
+                                      long long ldy, int N, int T, int H, int W, int C, int Tz, int Hz, int Wz, int G, float eps, int silu,
+                                      float* ws, long long ws_bytes, void* stream) {
+    if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || G <= 0 || (C % G) || (C % 8) || C > 8192 || (ldx % 8) || (ldy % 8) || ldx < C || ldy < C)
+        return VT_ERR_BAD_SHAPE;
+    if (N > 65535 || mod == nullptr || ws == nullptr || ws_bytes < vt_groupnorm_ws_bytes(N, C)) return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)ws) | ((uintptr_t)mod)) & 15) return VT_ERR_BAD_ALIGN;
+    const int sh = pow2_shift(H, Hz), sw = pow2_shift(W, Wz);
+    int st = 0;
+    if (T > 1) {
+        if (Tz < 2) return VT_ERR_BAD_SHAPE;
+        st = pow2_shift(T - 1, Tz - 1);
+    } else if (Tz < 1) return VT_ERR_BAD_SHAPE;
+    if (sh < 0 || sw < 0 || st < 0) return VT_ERR_BAD_SHAPE;
+    const long long P = (long long)T * H * W;
+    if (P * (C >> 3) >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(ws, 0, (size_t)N * 4 * C * 4, s) != hipSuccess) return VT_ERR_LAUNCH;
+    const int slabs = gn_slabs(N, P, C);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(slabs, N), dim3(GN_THREADS), 2 * C * sizeof(float), s, (const bf16_t*)x, ldx, P, C, ws, slabs);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(N), dim3(256), 4 * G * sizeof(float), s, ws, (const bf16_t*)x, ldx, (const bf16_t*)gamma, (const bf16_t*)beta, P, C, G, eps);
+    long long blocks = (P * (C >> 3) + GN_THREADS - 1) / GN_THREADS;
+    if (blocks > 8192) blocks = 8192;
+    if (silu) hipLaunchKernelGGL(spn_apply_kernel<true>, dim3((unsigned)blocks, N), dim3(GN_THREADS), 0, s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy,
+                                 (const bf16_t*)mod, T, H, W, C, Tz, Hz, Wz, st, sh, sw, ws);
+    else hipLaunchKernelGGL(spn_apply_kernel<false>, dim3((unsigned)blocks, N), dim3(GN_THREADS), 0, s, (const bf16_t*)x, ldx, (bf16_t*)y, ldy,
+                            (const bf16_t*)mod, T, H, W, C, Tz, Hz, Wz, st, sh, sw, ws);
+    return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Temporal compression of the VAE's DownSample3D (compress_time, cp_enc_dec.py:640-657): the first frame is kept, the remaining
 // T - 1 frames are averaged in consecutive pairs (avg_pool1d(kernel 2, stride 2): a trailing odd frame is dropped).
 //   y[n, 0] = x[n, 0];   y[n, 1 + i] = (x[n, 1 + 2i] + x[n, 2 + 2i]) / 2,   To = 1 + (T - 1) / 2      (T == 1: copy)

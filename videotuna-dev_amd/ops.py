@@ -384,6 +384,71 @@ def temporal_pool(x, y, keep_first: bool = True):
     return y
 
 
+def _pow2_ratio(big: int, small: int, what: str) -> int:
+    if small < 1 or big % small or (big // small) & (big // small - 1):
+        raise ValueError(f"{what}: {big} / {small} is not a power-of-two ratio")
+    return big // small
+
+
+def spatialnorm_zq_index(T: int, Tz: int, H: int, Hz: int, W: int, Wz: int):
+    """the (tz[t], hz[h], wz[w]) index vectors vt_spatialnorm_silu_cl gathers with: nearest interpolation of the latent to [T, H, W]
+    with the first frame handled apart (SpatialNorm3D.forward, rank-0 / fake_cp branch).  ValueError unless every ratio is a power of two."""
+    rh, rw = _pow2_ratio(H, Hz, "H / Hz"), _pow2_ratio(W, Wz, "W / Wz")
+    if T > 1:
+        if Tz < 2:
+            raise ValueError(f"T = {T} frames need a latent of at least 2 frames, got Tz = {Tz}")
+        rt = _pow2_ratio(T - 1, Tz - 1, "(T-1) / (Tz-1)")
+        tz = [0] + [1 + (t - 1) // rt for t in range(1, T)]
+    else:
+        if Tz < 1:
+            raise ValueError("Tz must be at least 1")
+        tz = [0]
+    return tz, [h // rh for h in range(H)], [w // rw for w in range(W)]
+
+
+def upsample_src_frames(T: int, temporal: bool):
+    """input frame of every output frame of vt_upsample_conv2d_cl: ts(t) = t, or with temporal upsampling (and T > 1) ts(0) = 0,
+    ts(t) = 1 + (t-1)//2 over 1 + 2 (T-1) output frames (Upsample3D.forward with compress_time, first frame kept single)"""
+    if temporal and T > 1:
+        return [0] + [1 + (t - 1) // 2 for t in range(1, 1 + 2 * (T - 1))]
+    return list(range(T))
+
+
+def spatialnorm_silu(x, gamma, beta, mod, y, groups: int = 32, eps: float = 1e-6, silu: bool = True, ws: Optional[torch.Tensor] = None):
+    """SpatialNorm3D (+ SiLU): x, y bf16 [N,T,H,W,C] channels-last; mod bf16 [N,Tz,Hz,Wz,2C] contiguous = (conv_y(zq) | conv_b(zq)) at
+    latent resolution; y = silu?(GroupNorm(x) * mod_y[zq index] + mod_b[zq index])"""
+    _req(x, BF16, "x", 5); _req(y, BF16, "y", 5); _req(mod, BF16, "mod", 5)
+    N, T, H, W, C = x.shape
+    Nz, Tz, Hz, Wz, C2 = mod.shape
+    if tuple(y.shape) != tuple(x.shape) or Nz != N or C2 != 2 * C or not mod.is_contiguous():
+        raise ValueError(f"shape mismatch: x {tuple(x.shape)} mod {tuple(mod.shape)} y {tuple(y.shape)}")
+    spatialnorm_zq_index(T, Tz, H, Hz, W, Wz)              # raises ValueError on a ratio the kernel does not take
+    _cl_check(x, "x"); _cl_check(y, "y")
+    lib = load_library()
+    need = int(lib.vt_groupnorm_ws_bytes(N, C))
+    if ws is None:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    check(lib.vt_spatialnorm_silu_cl(x.data_ptr(), x.stride(3), _p(gamma), _p(beta), mod.data_ptr(), y.data_ptr(), y.stride(3),
+                                     N, T, H, W, C, Tz, Hz, Wz, groups, eps, int(silu), ws.data_ptr(), ws.numel() * 4, _stream()),
+          "vt_spatialnorm_silu_cl")
+    return y
+
+
+def upsample_conv2d(x, wk, bias, y, temporal: bool = False):
+    """Upsample3D.forward fused: nearest 2x in h / w (temporal: also in t, first frame kept single), then the per-frame 3x3 convolution.
+    x bf16 [N,T,H,W,Cin], wk = pack_conv_weight(Conv2d weight), y bf16 [N, len(upsample_src_frames(T, temporal)), 2H, 2W, Cout]"""
+    _req(x, BF16, "x", 5); _req(y, BF16, "y", 5); _req(wk, BF16, "wk", 2)
+    N, T, H, W, Cin = x.shape
+    Cout = y.shape[4]
+    To = len(upsample_src_frames(T, temporal))
+    if tuple(y.shape[:4]) != (N, To, 2 * H, 2 * W) or tuple(wk.shape) != (Cout, 9 * Cin) or not wk.is_contiguous():
+        raise ValueError(f"shape mismatch: x {tuple(x.shape)} wk {tuple(wk.shape)} y {tuple(y.shape)} (expected {To} output frames)")
+    _cl_check(x, "x"); _cl_check(y, "y")
+    check(load_library().vt_upsample_conv2d_cl(x.data_ptr(), x.stride(3), wk.data_ptr(), _p(bias), y.data_ptr(), y.stride(3),
+                                               N, T, H, W, Cin, Cout, int(temporal), _stream()), "vt_upsample_conv2d_cl")
+    return y
+
+
 def rmsnorm(x, w, y, eps: float = 1e-6):
     """T5LayerNorm: y = x * rsqrt(mean(x^2) + eps) * w (rows of a 2-d bf16 tensor)"""
     _req(x, BF16, "x", 2); _req(y, BF16, "y", 2); _req(w, BF16, "w", 1)

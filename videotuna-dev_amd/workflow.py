@@ -57,6 +57,7 @@ class CogVideoXWorkFlow(nn.Module):
         # (cogvideo_pl.py:104-121 builds them unconditionally; offline a model name such as "DeepFloyd/t5-v1_1-xxl" cannot
         # be fetched -> the stage stays None and batches must come pre-encoded, see get_batch_input)
         self.first_stage, self.cond_stage = first_stage, cond_stage
+        self._first_stage_config = first_stage_config        # the decoder is built from it lazily (decode_latents / decode_first_stage)
         if first_stage is None and first_stage_config is not None:
             vae = self._optional_stage(first_stage_config)
             if vae is not None:
@@ -106,6 +107,39 @@ class CogVideoXWorkFlow(nn.Module):
     @property
     def device(self):
         return next(self.model.parameters()).device
+
+    # ---- latents back to video (cogvideo_pl.py:162-172, 410-418); log_images itself needs the sampler and is not built ----
+    def _decoder(self):
+        """the VAE decoder, built on the first call from the ``first_stage_config`` directory the encoder came from"""
+        dec = getattr(self, "vae_decoder", None)
+        if dec is not None:
+            return dec
+        import os
+        from .vae import CogVideoXVaeDecoder
+        node = self._first_stage_config
+        params = dict((node.get("params") or {}) if isinstance(node, dict) else {})
+        root = params.get("pretrained_model_name_or_path") or params.get("path")
+        path = os.path.join(root, params.get("subfolder") or "") if root else None
+        if path is None or not os.path.exists(path):
+            raise RuntimeError("decoding needs the VAE decoder's weights (the in-tree twin's keys under `decoder.`: decoder.conv_in.conv.weight, "
+                               f"decoder.up.N.block.M...), but first_stage_config names no local checkpoint ({path})")
+        dec = CogVideoXVaeDecoder.from_pretrained(**params)          # RuntimeError when the file holds no `decoder.` keys
+        self.vae_decoder = dec.to(self.device)
+        return self.vae_decoder
+
+    @torch.no_grad()
+    def decode_first_stage(self, z):
+        """z [B, C, F, H, W] scaled latents -> ``vae.decode(z / scaling_factor)`` (an object with ``.sample``), cogvideo_pl.py:162-172"""
+        dec = self._decoder()
+        return dec.decode(1.0 / dec.config.scaling_factor * z)
+
+    @torch.no_grad()
+    def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
+        """latents [B, F, C, H, W] -> frames [B, 3, T, H, W] bf16 (cogvideo_pl.py:410-418 without moving the DiT off the device)"""
+        dec = self._decoder()
+        latents = latents.permute(0, 2, 1, 3, 4)
+        latents = 1 / dec.config.scaling_factor * latents
+        return dec.decode(latents.to(dec.dtype)).sample
 
     def inject_adapter(self, adapter_config):
         self.model.requires_grad_(False)
