@@ -259,6 +259,32 @@ int vt_unpatchify(const void* tok, void* img, int B, int F, int C, int H, int W,
 /* scheduler.add_noise (cogvideo_pl.py:864): noisy = sqrt_ab[b]*x0 + sqrt_1mab[b]*noise  (fp32 in, bf16 out) */
 int vt_add_noise(const float* x0, const float* noise, const float* sqrt_ab, const float* sqrt_1mab, void* noisy,
                  long long per_sample, int B, void* stream);
+/* Sampler (csrc/sampler.hip; CogVideoXWorkFlow.sample, cogvideo_pl.py:476-772).
+ *
+ * Noise convention (vt355.workflow.sample without a torch generator; a statement of record):
+ *   element  e = index inside one sample's logical array of n elements (row-major over the sample's shape); sample b of B
+ *   key      seed + b (mod 2^64): sample b under `seed` is sample 0 under `seed + b`
+ *   counter  (stream << 40) + e / 4, as (lo, hi, 0, 0); stream 0 = the initial latents, stream i + 1 = the noise of denoising step i.
+ *            n <= 2^42 (e / 4 stays below 2^40) and 0 <= stream < 2^24, else VT_ERR_BAD_SHAPE
+ *   normal   words (w0, w1, w2, w3) of Philox4x32-10(key, counter) give elements 4 (e / 4) + {0, 1, 2, 3} by Box-Muller on the pairs
+ *            (w0, w1) and (w2, w3): u1 = ((w >> 8) + 1) 2^-24 in (0, 1], u2 = (w' >> 8) 2^-24 in [0, 1), both exact in fp32,
+ *            rad = sqrt(-2 ln u1), z_even = rad cos(2 pi u2), z_odd = rad sin(2 pi u2) with the precise logf / sincosf
+ *            (tests/sampler_ref.py restates it in fp64 on oracle/philox.py)
+ * vt_philox_normal: out[b * n + e] for b < B, e < n, fp32 (4-byte aligned) or bf16 (out_bf16 != 0, 2-byte aligned, one rounding of the
+ *   fp32 value).  Not torch's generator: it neither reads nor advances one.  Replaces: diffusers randn_tensor (cogvideo_pl.py:651-661).
+ * vt_dpm_step: guidance combine + CogVideoXDPMScheduler.step (cogvideo_pl.py:725-746) over B samples of `per` elements, all in fp32:
+ *     v  = guided ? v[b] + g (v[B + b] - v[b]) : v[b]        v bf16 [2B, per] (uncond rows, then cond rows) or [B, per]
+ *     x0 = sqrt_ab x - sqrt_1mab v                            x bf16 [B, per];  x0_out fp32 [B, per]
+ *     d  = second_order ? m3 x0 - m4 x0_old : x0              x0_old fp32 [B, per], NOT read when second_order == 0 (may be NULL)
+ *     x' = m1 x - m2 d + m_noise eps                          x_out bf16 [B, per]
+ *   eps = noise[b, e] (fp32 [B, per]) or, noise == NULL, the value vt_philox_normal(seed, stream) gives that element, bit for bit;
+ *   m_noise == 0: noise is neither read nor drawn.  The coefficients are host scalars (vt355.scheduler computes them in fp64).
+ *   Any per >= 1: bf16 pointers 2-byte, fp32 pointers 4-byte aligned (else VT_ERR_BAD_ALIGN); the 8- / 16-byte path is taken only when
+ *   per % 4 == 0 and every pointer read or written allows it.  x_out may be x. */
+int vt_philox_normal(void* out, int out_bf16, long long n, int B, unsigned long long seed, int stream_id, void* stream);
+int vt_dpm_step(const void* v, const void* x, const float* x0_old, const float* noise, void* x_out, float* x0_out,
+                long long per, int B, int guided, float g, float sqrt_ab, float sqrt_1mab, float m1, float m2, float m3,
+                float m4, float m_noise, int second_order, unsigned long long seed, int stream_id, void* stream);
 /* cogvideo_pl.py:872-886: x0_hat = sqrt_ab*noisy - sqrt_1mab*v ; loss = mean_b mean_i w_b (x0_hat-x0)^2 ;
  * optionally d loss / d v * grad_scale (bf16).  partials_ws: >= 512 floats. */
 int vt_diffusion_loss(const void* vpred, const void* noisy, const float* x0, const float* sqrt_ab,

@@ -69,6 +69,9 @@ PROTOTYPES = {
     "vt_patchify": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "vt_unpatchify": [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "vt_add_noise": [_fp, _fp, _fp, _fp, _vp, _ll, _i, _vp],
+    # sampler (csrc/sampler.hip): Philox normals under the header's noise convention; guidance combine + one DPM-Solver++ step
+    "vt_philox_normal": [_vp, _i, _ll, _i, C.c_ulonglong, _i, _vp],
+    "vt_dpm_step": [_vp, _vp, _fp, _fp, _vp, _fp, _ll, _i, _i] + [_f] * 8 + [_i, C.c_ulonglong, _i, _vp],
     "vt_diffusion_loss": [_vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _ll, _i, _f, _vp],
     "vt_diffusion_loss_bwd": [_vp, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _ll, _i, _vp],
     "vt_adamw": [_fp, _fp, _fp, _fp, _vp, _ll, _f, _f, _f, _f, _f, _i, _f, _vp, _vp],

@@ -700,6 +700,49 @@ def add_noise(x0, noise, sa, sb, noisy):
                                       x0.numel() // B, B, _stream()), "vt_add_noise")
 
 
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def philox_normal(out, seed: int, stream_id: int):
+    """out [B, ...] fp32 or bf16, contiguous: standard normals under the header's noise convention (sample b: key seed + b)"""
+    if out.dtype not in (torch.float32, BF16):
+        raise ValueError(f"philox_normal: out must be fp32 or bf16, got {out.dtype}")
+    _req(out, out.dtype, "out")
+    if not out.is_contiguous() or out.dim() < 1 or out.numel() == 0:
+        raise ValueError(f"philox_normal: out must be a contiguous, non-empty [B, ...] tensor, got {tuple(out.shape)}")
+    B = out.shape[0]
+    check(load_library().vt_philox_normal(out.data_ptr(), int(out.dtype == BF16), out.numel() // B, B, int(seed) & _U64, int(stream_id),
+                                          _stream()), "vt_philox_normal")
+    return out
+
+
+def dpm_step(v, x, x0_old, noise, x_out, x0_out, g: Optional[float], sa: float, sb: float, m1: float, m2: float, m3: float, m4: float,
+             m_noise: float, second_order: bool, seed: int = 0, stream_id: int = 0):
+    """guidance combine + one CogVideoXDPMScheduler.step (vt_dpm_step).  x [B, ...] bf16; v [2B, ...] (uncond, cond) with a guidance
+    scale g, or [B, ...] with g None; x0_old fp32 | None (first order); noise fp32 | None (drawn in the kernel from seed / stream_id)."""
+    _req(v, BF16, "v"); _req(x, BF16, "x"); _req(x_out, BF16, "x_out"); _req(x0_out, torch.float32, "x0_out")
+    B, n = x.shape[0], x.numel()
+    guided = g is not None
+    for name, t in (("v", v), ("x", x), ("x0_old", x0_old), ("noise", noise), ("x_out", x_out), ("x0_out", x0_out)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"dpm_step: {name} must be contiguous")
+    if v.numel() != (2 * n if guided else n):
+        raise ValueError(f"dpm_step: v holds {v.numel()} elements for {n} latent elements (guidance {'on' if guided else 'off'})")
+    _numel(x_out, n, "x_out", "dpm_step"); _numel(x0_out, n, "x0_out", "dpm_step")
+    if second_order:
+        if x0_old is None:
+            raise ValueError("dpm_step: a second-order step needs x0_old")
+        _req(x0_old, torch.float32, "x0_old"); _numel(x0_old, n, "x0_old", "dpm_step")
+    if noise is not None:
+        _req(noise, torch.float32, "noise"); _numel(noise, n, "noise", "dpm_step")
+    scal = [float(g) if guided else 0.0, sa, sb, m1, m2, m3 if second_order else 0.0, m4 if second_order else 0.0, m_noise]
+    if not all(math.isfinite(s) for s in scal):
+        raise ValueError(f"dpm_step: non-finite coefficient among (g, sa, sb, m1, m2, m3, m4, m_noise) = {scal}")
+    check(load_library().vt_dpm_step(v.data_ptr(), x.data_ptr(), _p(x0_old) if second_order else None, _p(noise), x_out.data_ptr(),
+                                     x0_out.data_ptr(), n // B, B, int(guided), *scal, int(bool(second_order)), int(seed) & _U64,
+                                     int(stream_id), _stream()), "vt_dpm_step")
+
+
 def diffusion_loss(vpred, noisy, x0, sa, sb, w, loss, partials, dvpred, grad_scale: float = 1.0):
     _req(vpred, BF16, "vpred"); _req(noisy, BF16, "noisy"); _req(x0, torch.float32, "x0")
     B = x0.shape[0]

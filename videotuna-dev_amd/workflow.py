@@ -1,7 +1,8 @@
 """``CogVideoXWorkFlow`` -- the training workflow of videotuna/models/cogvideo_hf/cogvideo_pl.py:90-149, 774-887 on the
 vt355 engine: same constructor keys (so configs/004_cogvideox/*.yaml load unchanged through
 ``vt355.config.instantiate_from_config``), same ``training_step(batch, batch_idx) -> loss``,
-``configure_optimizers()``, ``inject_adapter()``, ``on_save_checkpoint()`` (LoRA-only filter), ``lora_args``.
+``configure_optimizers()``, ``inject_adapter()``, ``on_save_checkpoint()`` (LoRA-only filter), ``lora_args``; and the sampling side
+(cogvideo_pl.py:476-772, 890-899): ``sample(...)`` and, when the VAE directory holds a decoder, ``log_images(batch)``.
 
 Scope: the frozen VAE and T5 encoders are NOT part of this hot path.  A batch is either
   * pre-encoded: {"latents": [B,C,F,H,W] (VAE sample * scaling_factor), "prompt_embeds": [B,226,4096]}  or
@@ -9,6 +10,8 @@ Scope: the frozen VAE and T5 encoders are NOT part of thi
 """
 from __future__ import annotations
 
+import math
+import os
 from typing import Any, Dict, Optional
 
 import torch
@@ -108,7 +111,40 @@ class CogVideoXWorkFlow(nn.Module):
     def device(self):
         return next(self.model.parameters()).device
 
-    # ---- latents back to video (cogvideo_pl.py:162-172, 410-418); log_images itself needs the sampler and is not built ----
+    # ---- latents back to video (cogvideo_pl.py:162-172, 410-418) ----
+    def _decoder_checkpoint(self):
+        """the local file (or directory) ``first_stage_config`` names, or None"""
+        node = getattr(self, "_first_stage_config", None)
+        params = dict((node.get("params") or {}) if isinstance(node, dict) else {})
+        root = params.get("pretrained_model_name_or_path") or params.get("path")
+        path = os.path.join(root, params.get("subfolder") or "") if root else None
+        return path if path is not None and os.path.exists(path) else None
+
+    def _decodable(self) -> bool:
+        """does ``first_stage_config`` name a local checkpoint with the decoder's weights?  Reads the file's key list only: the decoder
+        itself is still built on the first decode."""
+        if getattr(self, "vae_decoder", None) is not None:
+            return True
+        path = self._decoder_checkpoint()
+        if path is None:
+            return False
+        if os.path.isdir(path):
+            files = [os.path.join(path, fn) for fn in ("model.safetensors", "diffusion_pytorch_model.safetensors")]
+            path = next((f for f in files if os.path.exists(f)), None)
+            if path is None:
+                return False
+        cache = self.__dict__.setdefault("_decodable_cache", {})
+        if path not in cache:
+            from safetensors import safe_open
+            from .vae import CogVideoXVaeDecoder
+            try:
+                with safe_open(path, "pt") as f:
+                    keys = list(f.keys())
+            except Exception:                                    # not a safetensors file: nothing this decoder can load
+                keys = []
+            cache[path] = any(k.startswith(tuple(p + "up." for p in CogVideoXVaeDecoder._PREFIXES + ("",))) for k in keys)
+        return cache[path]
+
     def _decoder(self):
         """the VAE decoder, built on the first call from the ``first_stage_config`` directory the encoder came from"""
         dec = getattr(self, "vae_decoder", None)
@@ -233,6 +269,164 @@ class CogVideoXWorkFlow(nn.Module):
         sa, sb, w = self.scheduler.coefficients(timesteps)
         return _LossFn.apply(out, noisy, x0, sa, sb, w)
 
+    # ---- sampling (cogvideo_pl.py:476-772) ----
+    _CALLBACK_TENSORS = ("latents", "prompt_embeds", "negative_prompt_embeds", "noise_pred", "old_pred_original_sample",
+                         "guidance_scale")
+
+    def _encode_prompts(self, prompt, negative_prompt, do_cfg, num_videos_per_prompt, prompt_embeds, negative_prompt_embeds):
+        """(prompt_embeds, negative_prompt_embeds | None) as bf16 device tensors [B * num_videos_per_prompt, L, D] (encode_prompt,
+        cogvideo_pl.py:288-367): given embeddings pass through, prompts go through ``cond_stage``"""
+        def encode(texts, what):
+            if self.cond_stage is None:
+                raise RuntimeError(f"sample: {what} needs the T5 text encoder, which this workflow was built without (no local weights); "
+                                   f"pass prompt_embeds / negative_prompt_embeds instead")
+            return self.cond_stage(list(texts))
+
+        if prompt_embeds is None:
+            if prompt is None:
+                raise ValueError("sample: give `prompt` or `prompt_embeds`")
+            prompt = [prompt] if isinstance(prompt, str) else list(prompt)
+            prompt_embeds = encode(prompt, "a text prompt")
+        B = prompt_embeds.shape[0]
+        if do_cfg and negative_prompt_embeds is None:
+            negative_prompt = "" if negative_prompt is None else negative_prompt
+            neg = B * [negative_prompt] if isinstance(negative_prompt, str) else list(negative_prompt)
+            if len(neg) != B:
+                raise ValueError(f"sample: {len(neg)} negative prompts for {B} prompts")
+            negative_prompt_embeds = encode(neg, "the negative prompt (guidance_scale > 1)")
+
+        def place(e):
+            e = e.to(device=self.device, dtype=torch.bfloat16)
+            return e.repeat_interleave(num_videos_per_prompt, dim=0) if num_videos_per_prompt != 1 else e
+
+        return place(prompt_embeds), (place(negative_prompt_embeds) if do_cfg else None)
+
+    def sample(self, prompt=None, negative_prompt=None, height: int = 480, width: int = 720, num_frames: int = 49,
+               num_inference_steps: int = 50, timesteps=None, guidance_scale: float = 6, use_dynamic_cfg: bool = False,
+               num_videos_per_prompt: int = 1, eta: float = 0.0, generator=None, latents=None, prompt_embeds=None,
+               negative_prompt_embeds=None, output_type: str = "pil", sample_precision=None, callback_on_step_end=None,
+               callback_on_step_end_tensor_inputs=("latents",), max_sequence_length: int = 226, progress_bar: bool = False,
+               seed: Optional[int] = None, **unused):
+        """The reference's sampling loop on the device: one DiT forward (both guidance halves in one batch) and one fused
+        guidance + DPM-Solver++ kernel per step.  Noise: with ``generator`` torch.randn(generator=...) feeds the kernel; otherwise the
+        initial latents and every step's noise are Philox(seed) under the header's noise convention, no torch generator is touched,
+        and ``self.last_sample_seed`` holds the seed (8 bytes of os.urandom when ``seed`` is None).  Returns ``video[None].cpu()``:
+        [1, B, 3, T, H, W] frames, or [1, B, F, C, H/8, W/8] latents for output_type="latent"."""
+        if timesteps is not None:
+            raise ValueError("sample: custom `timesteps` are not supported: CogVideoXDPMScheduler.set_timesteps takes none "
+                             "(diffusers retrieve_timesteps raises the same way)")
+        if sample_precision not in (None, "bfloat16"):
+            raise ValueError(f"sample_precision = {sample_precision!r}: this engine samples in bfloat16 only")
+        bad = [k for k in callback_on_step_end_tensor_inputs if k not in self._CALLBACK_TENSORS]
+        if bad:
+            raise ValueError(f"callback_on_step_end_tensor_inputs {bad}: expected names among {self._CALLBACK_TENSORS}")
+        was_training = self.model.training
+        self.model.eval()
+        # a workflow without adapters whose optimizer does not exist yet has trainable base weights and no training state, which the
+        # engine refuses to pack; inference needs neither: freeze for the run, then put the flags back and drop that pack
+        thawed = []
+        if getattr(self.model, "_lora_state", None) is None and getattr(self.model, "fullft", None) is None:
+            thawed = [p for p in self.model.parameters() if p.requires_grad]
+            for p in thawed:
+                p.requires_grad_(False)
+        try:
+            with torch.no_grad():
+                return self._sample(prompt, negative_prompt, height, width, num_frames, int(num_inference_steps), float(guidance_scale),
+                                    use_dynamic_cfg, num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds,
+                                    output_type, callback_on_step_end, tuple(callback_on_step_end_tensor_inputs), progress_bar, seed)
+        finally:
+            self.model.train(was_training)
+            for p in thawed:
+                p.requires_grad_(True)
+            if thawed:
+                self.model._packed = None
+
+    def _sample(self, prompt, negative_prompt, height, width, num_frames, num_inference_steps, guidance_scale, use_dynamic_cfg,
+                num_videos_per_prompt, generator, latents, prompt_embeds, negative_prompt_embeds, output_type, callback, callback_inputs,
+                progress_bar, seed):
+        device = self.device
+        do_cfg = guidance_scale > 1.0
+        prompt_embeds, negative_prompt_embeds = self._encode_prompts(prompt, negative_prompt, do_cfg, num_videos_per_prompt,
+                                                                     prompt_embeds, negative_prompt_embeds)
+        B = prompt_embeds.shape[0]
+        if do_cfg:
+            prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)          # cogvideo_pl.py:641
+        sch = self.scheduler
+        sch.set_timesteps(num_inference_steps, device=device)
+        t_dev, t_host = sch.timesteps, sch.timesteps.tolist()
+        cfg = getattr(self.model, "config", None) or self.model.base_model.config
+        shape = (B, (num_frames - 1) // self.vae_scale_factor_temporal + 1, cfg.in_channels,
+                 height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
+        if generator is None:
+            if seed is None:
+                seed = int.from_bytes(os.urandom(8), "little")
+            seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            self.last_sample_seed = seed
+        else:
+            seed = None
+        if latents is not None:
+            if tuple(latents.shape) != shape:
+                raise ValueError(f"sample: latents of shape {tuple(latents.shape)}, expected {shape}")
+            latents = latents.to(device=device, dtype=torch.bfloat16).contiguous()
+        elif generator is not None:
+            latents = torch.randn(shape, generator=generator, device=generator.device, dtype=torch.bfloat16).to(device)
+        else:
+            latents = ops.philox_normal(torch.empty(shape, dtype=torch.bfloat16, device=device), seed, 0)
+        latents = latents * sch.init_noise_sigma if sch.init_noise_sigma != 1.0 else latents
+        rope = None
+        if cfg.use_rotary_positional_embeddings:                                                # cogvideo_pl.py:667-679
+            rope = self._prepare_rotary_positional_embeddings(
+                height=height, width=width, num_frames=shape[1], vae_scale_factor_spatial=self.vae_scale_factor_spatial,
+                patch_size=cfg.patch_size, attention_head_dim=cfg.attention_head_dim, device=device)
+        old = None
+        steps = enumerate(t_host)
+        if progress_bar:
+            from tqdm import tqdm
+            steps = tqdm(steps, desc="Denoising Steps", total=num_inference_steps)
+        for i, t in steps:
+            model_in = sch.scale_model_input(torch.cat([latents] * 2) if do_cfg else latents, t)
+            noise_pred = self.model(hidden_states=model_in, encoder_hidden_states=prompt_embeds, timestep=t_dev[i].expand(model_in.shape[0]),
+                                    image_rotary_emb=rope, return_dict=False)[0]
+            g = guidance_scale
+            if use_dynamic_cfg:
+                # the diffusers pipeline's formula, applied to the scale the step uses (cogvideo_pl.py:711-722 assigns it to a name it
+                # never reads); t is the timestep, so the base of the fifth power is negative for every step but the last few
+                g = 1 + guidance_scale * ((1 - math.cos(math.pi * ((num_inference_steps - t) / num_inference_steps) ** 5.0)) / 2)
+            latents, old = sch.step_guided(noise_pred, g if do_cfg else None, old, t, t_host[i - 1] if i > 0 else None, latents,
+                                           generator=generator, seed=seed, noise_stream=i + 1)
+            if callback is not None:
+                have = {"latents": latents, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds,
+                        "noise_pred": noise_pred, "old_pred_original_sample": old, "guidance_scale": g}
+                outs = callback(self, i, t_dev[i], {k: have[k] for k in callback_inputs})
+                latents = outs.pop("latents", latents)
+                prompt_embeds = outs.pop("prompt_embeds", prompt_embeds)
+                negative_prompt_embeds = outs.pop("negative_prompt_embeds", negative_prompt_embeds)
+        video = latents if output_type == "latent" else self.decode_latents(latents)
+        return video[None, ...].cpu()
+
+    @property
+    def log_images(self):
+        """``log_images(batch, **kwargs)`` (cogvideo_pl.py:890-899), present only when the workflow can turn latents into frames: without
+        a local VAE checkpoint that holds ``decoder.`` weights the attribute does not exist (``hasattr`` is False, as before the sampler)"""
+        if not self._decodable():
+            raise AttributeError("log_images: first_stage_config names no local VAE checkpoint with `decoder.` weights")
+        return self._log_images
+
+    @torch.no_grad()
+    def _log_images(self, batch, **kwargs):
+        """{"gt": batch["video"], "samples": sample(batch["caption"], num_inference_steps=50, sample_precision="bfloat16")}; kwargs may
+        set num_inference_steps, guidance_scale, seed, height, width, num_frames; a batch without captions is sampled from its
+        ``prompt_embeds`` (and ``negative_prompt_embeds``): the route when no T5 is on the machine"""
+        allowed = ("num_inference_steps", "guidance_scale", "seed", "height", "width", "num_frames")
+        args = {"num_inference_steps": 50}
+        args.update({k: v for k, v in kwargs.items() if k in allowed})
+        if "caption" in batch:
+            samples = self.sample([c for c in batch["caption"]], sample_precision="bfloat16", **args)
+        else:
+            samples = self.sample(prompt_embeds=batch["prompt_embeds"], negative_prompt_embeds=batch.get("negative_prompt_embeds"),
+                                  sample_precision="bfloat16", **args)
+        return {"gt": batch.get("video"), "samples": samples}
+
 
 class CogVideoXI2V(CogVideoXWorkFlow):
     """Image-to-video finetune workflow (videotuna/models/cogvideo_hf/cogvideo_i2v.py:39-181): the first-frame image
@@ -247,6 +441,14 @@ class CogVideoXI2V(CogVideoXWorkFlow):
                          adapter_config, logdir, first_stage=first_stage, cond_stage=cond_stage)
         self.noised_image_input = noised_image_input
         self.noised_image_dropout = noised_image_dropout
+
+    def sample(self, *args, **kwargs):
+        raise NotImplementedError("CogVideoXI2V.sample is not built: the image-to-video loop concatenates the image latents to the "
+                                  "model input at every step (cogvideo_i2v.py), which the text-to-video sampler does not do")
+
+    @property
+    def log_images(self):
+        raise AttributeError("log_images: CogVideoXI2V.sample is not built")
 
     def get_batch_input(self, batch):
         if "latents" in batch:
