@@ -47,6 +47,8 @@ const char* vt_error_string(int code);
 #define VT_EPI_DGELU 3       /* C = (A W^T) * gelu_tanh'(U)                        (backward through net.0 act) */
 
 /* C[M,N] = A[M,K] * W[N,K]^T, bf16 operands, fp32 accumulate.  K % 64 == 0, N % 4 == 0.
+ * A, W and an fp32 C 16-byte aligned; a bf16 C and C2 / R / U 8-byte aligned with leading dimensions that are multiples of 4 (the
+ * 256x256 kernel moves them 16 bytes at a time where they are 16-byte aligned with leading dimensions that are multiples of 8).
  * Replaces: every torch.nn.Linear of diffusers CogVideoXBlock / CogVideoXPatchEmbed / TimestepEmbedding /
  * CogVideoXLayerNormZero.linear / proj_out, called by the reference via
  * videotuna/models/cogvideo_hf/cogvideo_pl.py:865-871; rows m belong to sample b = m / S and are text
@@ -62,9 +64,24 @@ int vt_gemm_set_tile(int mode);
 /* which kernel vt_gemm_bf16 runs for an (M, N, K) problem under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128
  * producer/consumer, 4 = the producer/consumer kernel's 128-row instantiation; < 0 on a bad shape */
 int vt_gemm_bf16_kernel(int M, int N, int K);
+/* vt_gemm_bf16 with the tiling named by the caller: tile 0 = by shape (exactly vt_gemm_bf16), 1 / 2 / 3 = that kernel, as under
+ * vt_gemm_set_tile.  A non-zero global mode of vt_gemm_set_tile wins over the argument.  Same validation as vt_gemm_bf16;
+ * VT_ERR_BAD_SHAPE for a tile outside 0..3.  The kernels are bit-identical, so the argument only moves time. */
+int vt_gemm_bf16_tile(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+                      int M, int N, int K, const void* bias, int epilogue, int out_fp32,
+                      const void* R, int ldr, int r_mod,
+                      const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St,
+                      void* C2, int ldc2, const void* U, int ldu, int tile, void* stream);
+/* the tile argument a CogVideoX block passes for its ff.net.2 forward and ff.net.0.proj input-gradient products (N = 1920 / 1984 with
+ * a long K, which vt_gemm_bf16's shape rule leaves on the producer / consumer kernel): 2 where the 256x256 kernel was measured ahead
+ * (csrc/gemm_bf16.hip has the rule and the rows), 0 = no opinion for every other shape; < 0 on a bad shape */
+int vt_gemm_bf16_block_tile(int M, int N, int K);
 /* K-loop of the 256x256 kernel: 0 = by shape (default), 1 = always the two-phase loop, 2 = always the eight-phase loop (operand
  * loads in flight across barriers); bit-identical results, tests and A/B timing only */
 int vt_gemm_set_big_loop(int mode);
+/* epilogue path of the last 256x256-kernel launch: 1 = 16-byte accesses, 0 = the 8-byte path (an operand of the epilogue was not
+ * 16-byte aligned, or N % 8 != 0), -1 = no launch yet (tests) */
+int vt_gemm_big_last_wide(void);
 /* convolution tile choice: 0 = per shape (default), 1 = always the 128 x 128 kernels, 2 = the 320-wide loader / multiplier kernels whenever
  * Cout % 320 == 0 (tests and A/B timing; csrc/convnd.hip) */
 int vt_conv_set_tile(int mode);

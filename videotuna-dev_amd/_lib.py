@@ -28,7 +28,11 @@ PROTOTYPES = {
                      _vp, _i, _vp, _i, _vp],
     "vt_gemm_set_tile": [_i],
     "vt_gemm_set_big_loop": [_i],
+    "vt_gemm_big_last_wide": [],
     "vt_gemm_bf16_kernel": [_i, _i, _i],
+    "vt_gemm_bf16_tile": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _fp, _fp, _i, _i, _i,
+                          _vp, _i, _vp, _i, _i, _vp],
+    "vt_gemm_bf16_block_tile": [_i, _i, _i],
     "vt_conv_set_tile": [_i],
     "vt_transpose_bf16": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp],
     "vt_transpose_multi_bf16": [_vp, _i, _ll, _vp],

@@ -142,6 +142,9 @@ static int launch(const GemmParams& p, hipStream_t st) {
 }
 
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+// the bf16 matrices of the epilogue (C, C2, R, U) are accessed 8 bytes at a time by every kernel; the 256x256 kernel widens to 16 bytes
+// where it finds them 16-byte aligned (gemm_big_bf16.hip, big_wide)
+static bool al8(const void* p) { return (((uintptr_t)p) & 7) == 0; }
 
 // 256x256-tile kernel (gemm_big_bf16.hip) for the token-sized problems; 0 = choose by shape, 1 = always 128x128, 2 = always 256x256
 int vt_gemm_big_dispatch(const GemmParams& p, int epilogue, int out_fp32, hipStream_t st);
@@ -203,14 +206,35 @@ extern "C" int vt_gemm_bf16_kernel(int M, int N, int K) {
     return tile == 3 && vt_gemm_pc_bm(M) == 128 ? 4 : tile;
 }
 
-extern "C" int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+// The measured rule for the two CogVideoX block products that pick_tile leaves on the producer / consumer kernel (ff.net.2 forward and
+// the input gradient of ff.net.0.proj: N = 1920, or 1984 with the LoRA K-extension columns, K = 7680 / 7744), for callers that know
+// their shape and pass the answer to vt_gemm_bf16_tile.  2 = the 256x256 kernel, 0 = no opinion (pick_tile decides).
+// profiles/gemm_big8_kbench.txt, M = 71104, us per launch, 256x256 default loop / producer-consumer / 128x128:
+//   N=1920 K=7680 bias   1522.5 / 1804.1 / 2363.3      N=1920 K=7680 gated  1590.1 / 1916.2 / 2438.1
+//   N=1920 K=1984 bias    452.9 /  528.0 /  568.3      N=1984 K=1920 bias    451.0 /  602.2 /  606.2      N=1984 K=5760 bias 1172.2 / 1436.3 / 1652.9
+// The rule is pick_tile's own for K < 4096 without the K bound: the last column tile at least 15/16 used and the tiles filling whole passes
+// of the chip (>= 90 % of the last one or a single pass of >= 160 tiles, or >= 85 % of all passes beyond one); only the two N that were
+// measured answer 2.  pick_tile itself keeps K >= 4096 on the producer / consumer kernel: its answers are pinned by the dispatch tests.
+extern "C" int vt_gemm_bf16_block_tile(int M, int N, int K) {
+    if (M <= 0 || N <= 0 || K <= 0) return VT_ERR_BAD_SHAPE;
+    if ((N != 1920 && N != 1984) || (K % BK) != 0 || K < 512 || M < 1024) return 0;
+    const long long nbn = (N + 255) / 256, t256 = (long long)((M + 255) / 256) * nbn;
+    const long long passes = (t256 + 255) / 256;
+    const bool full = t256 <= 256 ? t256 >= 160 : 10 * t256 >= 9 * passes * 256;
+    const bool most = t256 > 256 && 100 * t256 >= 85 * passes * 256;
+    return ((full || most) && 16LL * N >= 15 * 256 * nbn) ? 2 : 0;
+}
+
+// tile: 0 = pick_tile, 1 / 2 / 3 = that kernel as under vt_gemm_set_tile; a global mode set by vt_gemm_set_tile wins over it
+extern "C" int vt_gemm_bf16_tile(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
                             int M, int N, int K, const void* bias, int epilogue, int out_fp32,
                             const void* R, int ldr, int r_mod,
                             const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St,
-                            void* C2, int ldc2, const void* U, int ldu, void* stream) {
+                            void* C2, int ldc2, const void* U, int ldu, int tile_req, void* stream) {
+    if (tile_req < 0 || tile_req > 3) return VT_ERR_BAD_SHAPE;
     if (M <= 0 || N <= 0 || K <= 0 || (K % BK) != 0 || (N % 4) != 0) return VT_ERR_BAD_SHAPE;
     if ((lda % 8) || (ldw % 8) || (ldc % 4) || lda < K || ldw < K || ldc < N) return VT_ERR_BAD_SHAPE;
-    if (!al16(A) || !al16(W) || !al16(C)) return VT_ERR_BAD_ALIGN;
+    if (!al16(A) || !al16(W) || !(out_fp32 ? al16(C) : al8(C))) return VT_ERR_BAD_ALIGN;
     GemmParams p;
     p.A = (const bf16_t*)A; p.W = (const bf16_t*)W; p.C = C; p.bias = (const bf16_t*)bias;
     p.R = (const bf16_t*)R; p.gate_txt = gate_txt; p.gate_vid = gate_vid;
@@ -218,12 +242,12 @@ extern "C" int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldc2 = ldc2; p.ldu = ldu;
     p.S = S > 0 ? S : 1; p.St = St; p.gate_bstride = gate_bstride; p.r_mod = r_mod; p.splits = 1;
     hipStream_t st = (hipStream_t)stream;
-    const int tile = pick_tile(M, N, K);
+    const int tile = (g_gemm_tile == 0 && tile_req != 0) ? tile_req : pick_tile(M, N, K);
     const bool big = tile == 2;
     if (tile == 3) {                                     // producer / consumer kernel (256x128 tile)
-        if (epilogue == EPI_BIAS_GELU && (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al16(C2))) return VT_ERR_BAD_SHAPE;
-        if (epilogue == EPI_GATED_RES && (out_fp32 || R == nullptr || (ldr % 4) || !al16(R))) return VT_ERR_BAD_SHAPE;
-        if (epilogue == EPI_DGELU && (out_fp32 || U == nullptr || (ldu % 4) || !al16(U))) return VT_ERR_BAD_SHAPE;
+        if (epilogue == EPI_BIAS_GELU && (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al8(C2))) return VT_ERR_BAD_SHAPE;
+        if (epilogue == EPI_GATED_RES && (out_fp32 || R == nullptr || (ldr % 4) || !al8(R))) return VT_ERR_BAD_SHAPE;
+        if (epilogue == EPI_DGELU && (out_fp32 || U == nullptr || (ldu % 4) || !al8(U))) return VT_ERR_BAD_SHAPE;
         return vt_gemm_pc_dispatch(p, epilogue, out_fp32, st);
     }
     switch (epilogue) {
@@ -231,21 +255,30 @@ extern "C" int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void
             if (big) return vt_gemm_big_dispatch(p, epilogue, out_fp32, st);
             return out_fp32 ? launch<EPI_BIAS, true>(p, st) : launch<EPI_BIAS, false>(p, st);
         case EPI_BIAS_GELU:
-            if (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al16(C2)) return VT_ERR_BAD_SHAPE;
+            if (out_fp32 || C2 == nullptr || (ldc2 % 4) || !al8(C2)) return VT_ERR_BAD_SHAPE;
             if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
             return launch<EPI_BIAS_GELU, false>(p, st);
         case EPI_GATED_RES:
-            if (out_fp32 || R == nullptr || (ldr % 4) || !al16(R)) return VT_ERR_BAD_SHAPE;
-            if (C2 != nullptr && ((ldc2 % 4) || !al16(C2))) return VT_ERR_BAD_SHAPE;
+            if (out_fp32 || R == nullptr || (ldr % 4) || !al8(R)) return VT_ERR_BAD_SHAPE;
+            if (C2 != nullptr && ((ldc2 % 4) || !al8(C2))) return VT_ERR_BAD_SHAPE;
             if (gate_vid != nullptr && (gate_txt == nullptr || (gate_bstride % 4) || !al16(gate_vid) || !al16(gate_txt)))
                 return VT_ERR_BAD_SHAPE;
             if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
             return launch<EPI_GATED_RES, false>(p, st);
         case EPI_DGELU:
-            if (out_fp32 || U == nullptr || (ldu % 4) || !al16(U)) return VT_ERR_BAD_SHAPE;
+            if (out_fp32 || U == nullptr || (ldu % 4) || !al8(U)) return VT_ERR_BAD_SHAPE;
             if (big) return vt_gemm_big_dispatch(p, epilogue, 0, st);
             return launch<EPI_DGELU, false>(p, st);
         default:
             return VT_ERR_UNSUPPORTED;
     }
+}
+
+extern "C" int vt_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc,
+                            int M, int N, int K, const void* bias, int epilogue, int out_fp32,
+                            const void* R, int ldr, int r_mod,
+                            const float* gate_txt, const float* gate_vid, int gate_bstride, int S, int St,
+                            void* C2, int ldc2, const void* U, int ldu, void* stream) {
+    return vt_gemm_bf16_tile(A, lda, W, ldw, C, ldc, M, N, K, bias, epilogue, out_fp32, R, ldr, r_mod, gate_txt, gate_vid, gate_bstride, S, St,
+                             C2, ldc2, U, ldu, 0, stream);
 }

@@ -67,6 +67,17 @@ __device__ __forceinline__ u32x2 gemm_epilogue_aux_load(const GemmParams& p, int
     }
     return (u32x2){0u, 0u};
 }
+// the same for 8 consecutive columns in one 16-byte load (the caller has checked the alignment of the pointer and the leading dimension)
+template <int EPI>
+__device__ __forceinline__ u32x4 gemm_epilogue_aux_load8(const GemmParams& p, int m, int n) {
+    if (EPI == EPI_GATED_RES) {
+        const int rr = p.r_mod > 0 ? (m % p.r_mod) : m;
+        return *(const u32x4*)(p.R + (size_t)rr * p.ldr + n);
+    } else if (EPI == EPI_DGELU) {
+        return *(const u32x4*)(p.U + (size_t)m * p.ldu + n);
+    }
+    return (u32x4){0u, 0u, 0u, 0u};
+}
 
 // EPI_GATED_RES gates of one output tile, hoisted out of the per-row work: a tile of `rows` <= S rows touches at most the
 // samples b0 = row0 / S and b0 + 1, so their (text, video) gate vectors for this thread's 4 columns are loaded once per
@@ -100,10 +111,12 @@ __device__ __forceinline__ GateCtx gate_ctx_load(const GemmParams& p, int row0, 
 
 // v = accumulators of (row m, columns n..n+3), bias4 = bias of those columns (zeros if none).  Caller guarantees
 // m < M and n < N (N % 4 == 0).
-// The arithmetic of the epilogue: o = epilogue(v + bias4) of (row m, columns n..n+3), the second output (C2) written here.
+// The arithmetic of the epilogue: o = epilogue(v + bias4) of (row m, columns n..n+3), the second output (C2) written here -- or, with
+// c2v given, handed back as its four packed bf16 for a caller that stores wider (it stores them under the same condition: always for
+// EPI_BIAS_GELU, where p.C2 is set for EPI_GATED_RES).
 template <int EPI>
 __device__ __forceinline__ f32x4 gemm_epilogue_apply(const GemmParams& p, int m, int n, f32x4 v, const float* bias4, u32x2 aux,
-                                                     const GateCtx* gc) {
+                                                     const GateCtx* gc, u32x2* c2v = nullptr) {
                 float o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) o[j] = v[j] + bias4[j];
@@ -111,7 +124,8 @@ __device__ __forceinline__ f32x4 gemm_epilogue_apply(const GemmParams& p, int m,
                     u32x2 u2;
                     u2[0] = pack2(o[0], o[1]);
                     u2[1] = pack2(o[2], o[3]);
-                    *(u32x2*)(p.C2 + (size_t)m * p.ldc2 + n) = u2;
+                    if (c2v != nullptr) *c2v = u2;
+                    else *(u32x2*)(p.C2 + (size_t)m * p.ldc2 + n) = u2;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = gelu_tanh_f(o[j]);
                 } else if (EPI == EPI_GATED_RES) {
@@ -119,7 +133,8 @@ __device__ __forceinline__ f32x4 gemm_epilogue_apply(const GemmParams& p, int m,
                         u32x2 u2;
                         u2[0] = pack2(o[0], o[1]);
                         u2[1] = pack2(o[2], o[3]);
-                        *(u32x2*)(p.C2 + (size_t)m * p.ldc2 + n) = u2;
+                        if (c2v != nullptr) *c2v = u2;
+                        else *(u32x2*)(p.C2 + (size_t)m * p.ldc2 + n) = u2;
                     }
                     const u32x2 r2 = aux;
                     float r[4] = {__uint_as_float(r2[0] << 16), __uint_as_float(r2[0] & 0xffff0000u),

@@ -466,8 +466,9 @@ def block_forward(model, i: int, h, mod, dims, rope, save: bool, scratch, drop=N
         _lora_down(st, i, "ff2", gact, dff, drop)
     h2 = E(M, d)
     fo = E(M, d) if (keep_ff or (save and dora is not None and ff2)) else None
+    k2 = dff + ef if ff2 else dff
     ops.gemm(gact, Lw.w2, h2, Lw.b2, epilogue=EPI_GATED_RES, residual=h1, gate_txt=m2.gate_txt, gate_vid=m2.gate_vid,
-             gate_bstride=m2.bs, S=S, St=St, pre_act_out=fo, K=dff + ef if ff2 else None)
+             gate_bstride=m2.bs, S=S, St=St, pre_act_out=fo, K=k2, tile=ops.gemm_block_tile(M, d, k2))
     if save:
         a.x1, a.qkv, a.qkh, a.o, a.lse, a.h1, a.u = x1, qkv, qkh, o, lse, h1, u
         a.x2, a.g, a.ao, a.fo = (x2, gact, ao, fo) if ft is not None else (x2 if ff1 else None, gact if ff2 else None, ao, fo)
@@ -619,7 +620,7 @@ def run_backward(model, ctx, dout: torch.Tensor):
                 _lora_dx_dgelu(st, i, du, tgf[:, d:], a.u, dff, drop)
         else:
             ops.gemm(tg, Lw.w2_t, du, None, epilogue=EPI_DGELU, pre_act_in=a.u)
-        ops.gemm(du, Lw.w1_t, dx2, None)                                  # ff.net.0.proj adapted: [M, d+ext]: dx2 | dT1
+        ops.gemm(du, Lw.w1_t, dx2, None, tile=ops.gemm_block_tile(M, Lw.w1_t.shape[0], dff))   # ff.net.0.proj adapted: [M, d+ext]: dx2 | dT1
         if ff1:
             _lora_db(st, tn, du, a.x2[:, d:], st.view(st.grad, i, "B", 4), dff, Lw.c_1 if dora else None)  # dB1
             if dora:

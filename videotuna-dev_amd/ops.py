@@ -135,8 +135,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[tor
          epilogue: int = EPI_BIAS, residual: Optional[torch.Tensor] = None, r_mod: int = 0,
          gate_txt: Optional[torch.Tensor] = None, gate_vid: Optional[torch.Tensor] = None, gate_bstride: int = 0,
          S: int = 1, St: int = 0, pre_act_out: Optional[torch.Tensor] = None,
-         pre_act_in: Optional[torch.Tensor] = None, K: Optional[int] = None, N: Optional[int] = None) -> torch.Tensor:
-    """out[M,N] = a[M,K] @ w[N,K]^T (+ epilogue).  a, w are 2-d (row-strided views allowed)."""
+         pre_act_in: Optional[torch.Tensor] = None, K: Optional[int] = None, N: Optional[int] = None, tile: int = 0) -> torch.Tensor:
+    """out[M,N] = a[M,K] @ w[N,K]^T (+ epilogue).  a, w are 2-d (row-strided views allowed).  tile: 0 = the library chooses by shape,
+    1 / 2 / 3 = that kernel as under gemm_set_tile (same bits, a caller that knows its shape; a global gemm_set_tile mode wins)."""
     _req(a, BF16, "a", 2); _req(w, BF16, "w", 2)
     M = a.shape[0]
     K = a.shape[1] if K is None else K
@@ -146,12 +147,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias: Optional[tor
         _req(out, BF16, "out", 2)
     lib = load_library()
     with _timed("gemm", 2.0 * M * N * K if (_PROFILE["on"] and M >= 4096) else 0.0) if (_PROFILE["on"] and M >= 4096) else _NOTIME:
-        check(lib.vt_gemm_bf16(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
-                               M, N, K, _p(bias), epilogue, int(out_f32),
-                               _p(residual), 0 if residual is None else residual.stride(0), r_mod,
-                               _p(gate_txt), _p(gate_vid), gate_bstride, S, St,
-                               _p(pre_act_out), 0 if pre_act_out is None else pre_act_out.stride(0),
-                               _p(pre_act_in), 0 if pre_act_in is None else pre_act_in.stride(0), _stream()),
+        check(lib.vt_gemm_bf16_tile(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
+                                    M, N, K, _p(bias), epilogue, int(out_f32),
+                                    _p(residual), 0 if residual is None else residual.stride(0), r_mod,
+                                    _p(gate_txt), _p(gate_vid), gate_bstride, S, St,
+                                    _p(pre_act_out), 0 if pre_act_out is None else pre_act_out.stride(0),
+                                    _p(pre_act_in), 0 if pre_act_in is None else pre_act_in.stride(0), tile, _stream()),
               "vt_gemm_bf16")
     return out
 
@@ -538,6 +539,11 @@ def gemm_set_big_loop(mode: int = 0):
     check(load_library().vt_gemm_set_big_loop(mode), "vt_gemm_set_big_loop")
 
 
+def gemm_big_last_wide() -> int:
+    """epilogue path of the last 256x256-kernel launch: 1 = 16-byte accesses, 0 = the 8-byte path, -1 = none yet (tests)"""
+    return load_library().vt_gemm_big_last_wide()
+
+
 def gemm_kernel(M: int, N: int, K: int) -> int:
     """the kernel vt_gemm_bf16 runs for this shape under the current tile mode: 1 = 128x128, 2 = 256x256, 3 = 256x128 producer / consumer,
     4 = the producer / consumer kernel's 128-row instantiation"""
@@ -545,6 +551,15 @@ def gemm_kernel(M: int, N: int, K: int) -> int:
     if k < 0:
         check(k, "vt_gemm_bf16_kernel")
     return k
+
+
+def gemm_block_tile(M: int, N: int, K: int) -> int:
+    """the `tile` a CogVideoX block passes to gemm() for its ff.net.2 forward and ff.net.0.proj input-gradient products: 2 where the 256x256
+    kernel was measured ahead of the shape rule's choice, 0 = no opinion (vt_gemm_bf16_block_tile, csrc/gemm_bf16.hip)"""
+    t = load_library().vt_gemm_bf16_block_tile(M, N, K)
+    if t < 0:
+        check(t, "vt_gemm_bf16_block_tile")
+    return t
 
 
 def attn_bwd_set_chain(chain_len: int = 0, slots: int = 0):
