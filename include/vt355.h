@@ -14,8 +14,8 @@
  *     no allocation, no host reads of device data -> safe under hipGraph capture;
  *   - return 0 on success, a negative VT_ERR_* otherwise; no C++ exception crosses the ABI;
  *   - compute entry points keep no state between calls and are safe from autograd's backward thread (one process per
- *     GPU, as PL's DDPStrategy runs the reference).  Four process-global TUNING knobs exist for tests and A/B timing only --
- *     vt_gemm_set_tile, vt_gemm_set_big_loop, vt_conv_set_tile, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
+ *     GPU, as PL's DDPStrategy runs the reference).  Five process-global TUNING knobs exist for tests and A/B timing only --
+ *     vt_gemm_set_tile, vt_gemm_set_big_loop, vt_conv_set_tile, vt_conv3d_set_kernel, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
  *     they select between kernels that give the same results, the product path never calls them.
  *   - deviation from SURVEY 8(b)'s sketch of this ABI (vt_tensor descriptors, vt_<op>_params structs,
  *     vt_workspace_bytes_<op>, vt_last_error): arguments are flat pointers + leading dimensions (one ctypes call, no struct
@@ -171,6 +171,21 @@ int vt_causal_conv3d_cl(const void* x, long long ldx, const void* wk, const void
  * permuted to [Cout,3,3,Cin]; y bf16 [N,T,H/2,W/2,Cout]. */
 int vt_downsample_conv2d_cl(const void* x, long long ldx, const void* wk, const void* bias, void* y, long long ldy,
                             int N, int T, int H, int W, int Cin, int Cout, void* stream);
+/* vt_downsample_conv2d_cl with a residual (bf16 [N,T,H/2,W/2,Cout], position stride ldr) added to the result: the EPI_GATED_RES
+ * instantiations of the stride-2 kernels, which no layer of the VAE uses (tests) */
+int vt_downsample_conv2d_res_cl(const void* x, long long ldx, const void* wk, const void* bias, const void* res, long long ldr,
+                                void* y, long long ldy, int N, int T, int H, int W, int Cin, int Cout, void* stream);
+/* Kernel choice of vt_causal_conv3d_cl / vt_downsample_conv2d_cl, process-global (tests and A/B timing; csrc/conv3d.hip).
+ * mode: 0 = by shape (default), 1 = always the 128-row kernel, 2 = the 256-row producer / consumer kernel wherever its span check allows;
+ * the environment variable VT_CONV_KERNEL, read once, is its initial value.  slots: cap of the persistent grid, 0 = the device's own
+ * (CUs rounded down to a multiple of 8), else a multiple of 8 from 8 up to that value.  Anything else: VT_ERR_BAD_SHAPE, nothing changes. */
+int vt_conv3d_set_kernel(int mode, int slots);
+/* host-only query, no launch: what the launch for this geometry would be under the current setting.  kt = 3, stride = 1: vt_causal_conv3d_cl;
+ * kt = 1, stride = 2: vt_downsample_conv2d_cl.  kernel: 1 = 128-row tiles (one per workgroup), 2 = producer / consumer (256-row tiles,
+ * persistent); grid: workgroups; tiles: output tiles of that kernel; tiles_per_wg: the most tiles one workgroup walks.  Each output
+ * pointer may be NULL.  Computed by the helper the launch itself follows. */
+int vt_conv3d_plan(long long ldx, int N, int T, int H, int W, int Cin, int Cout, int kt, int stride,
+                   int* kernel, int* grid, int* tiles, int* tiles_per_wg);
 /* The encoder's first convolution (RGB): x bf16 [N,T,H,W,8] (8 channels per position, unused ones zero), wk bf16 [Cout, 32*8] =
  * the Conv3d weight as (tap, channel) with taps 27..31 and channels >= Cin zero; 8 taps per K-tile instead of one. */
 int vt_causal_conv3d_in8_cl(const void* x, const void* wk, const void* bias, void* y, long long ldy,

@@ -52,6 +52,9 @@ PROTOTYPES = {
     "vt_causal_conv3d_cl": [_vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp],
     "vt_causal_conv3d_in8_cl": [_vp, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _vp],
     "vt_downsample_conv2d_cl": [_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp],
+    "vt_downsample_conv2d_res_cl": [_vp, _ll, _vp, _vp, _vp, _ll, _vp, _ll, _i, _i, _i, _i, _i, _i, _vp],
+    "vt_conv3d_set_kernel": [_i, _i],
+    "vt_conv3d_plan": [_ll] + [_i] * 8 + [C.POINTER(C.c_int)] * 4,
     "vt_temporal_pool_cl": [_vp, _ll, _vp, _ll, _i, _i, _ll, _i, _i, _vp],
     "vt_spatialnorm_silu_cl": [_vp, _ll, _vp, _vp, _vp, _vp, _ll] + [_i] * 9 + [_f, _i, _fp, _ll, _vp],
     "vt_upsample_conv2d_cl": [_vp, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _i, _i, _i, _i, _vp],

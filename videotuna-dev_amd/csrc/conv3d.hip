@@ -390,52 +390,119 @@ __global__ __launch_bounds__(512, 1) void conv3d_pc_kernel(Conv3dParams cp) {
     }
 }
 
+// ---- kernel choice (host).  g_c3_mode: 0 = by shape, 1 = always the 128-row kernel, 2 = the producer / consumer kernel wherever its span
+// check allows; it starts as VT_CONV_KERNEL (read once).  g_c3_slots: cap of the persistent grid, 0 = the device's own (CUs rounded down to
+// a multiple of 8).  vt_conv3d_set_kernel sets both (tests, A/B timing); the product path never calls it.
+static int g_c3_mode = -1, g_c3_slots = 0;
+static int c3_mode() {
+    if (g_c3_mode < 0) {
+        const char* e = getenv("VT_CONV_KERNEL");
+        g_c3_mode = e ? atoi(e) : 0;
+        if (g_c3_mode < 0) g_c3_mode = 0;
+    }
+    return g_c3_mode;
+}
+static int c3_device_slots() {
+    static int slots = 0;
+    if (slots == 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+        slots = cus >= 8 ? cus / 8 * 8 : 8;
+    }
+    return slots;
+}
+extern "C" int vt_conv3d_set_kernel(int mode, int slots) {
+    if (mode < 0 || mode > 2 || slots < 0 || (slots % 8) || slots > c3_device_slots()) return VT_ERR_BAD_SHAPE;
+    g_c3_mode = mode;
+    g_c3_slots = slots;
+    return VT_OK;
+}
+
+// What conv_launch does with a geometry: the plan vt_conv3d_plan reports and conv_launch follows.
+struct Conv3dPlan {
+    int kernel;            // 1 = conv3d_cl_kernel (128-row tiles, one per workgroup), 2 = conv3d_pc_kernel (256-row tiles, persistent)
+    int grid;              // workgroups
+    int tiles;             // output tiles of that kernel
+    int tiles_per_wg;      // most tiles one workgroup walks
+    int Ho, Wo;
+    long long rows_in, rows_out;
+};
 template <int KT, int STRIDE>
-static int conv_launch(const void* x, long long ldx, const void* wk, const void* bias, const void* res, long long ldr, void* y, long long ldy,
-                       int N, int T, int H, int W, int Cin, int Cout, hipStream_t st) {
+static int conv_plan(long long ldx, int N, int T, int H, int W, int Cin, int Cout, Conv3dPlan* pl) {
     if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % CV_BK) || (Cout % 4)) return VT_ERR_BAD_SHAPE;
     if (STRIDE == 2 && ((H % 2) || (W % 2))) return VT_ERR_BAD_SHAPE;
-    if ((ldx % 8) || (ldy % 4) || ldx < Cin || ldy < Cout || (res != nullptr && ((ldr % 4) || ldr < Cout))) return VT_ERR_BAD_SHAPE;
-    if ((((uintptr_t)x) | ((uintptr_t)wk) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) return VT_ERR_BAD_ALIGN;
+    if ((ldx % 8) || ldx < Cin) return VT_ERR_BAD_SHAPE;
     const int Ho = H / STRIDE, Wo = W / STRIDE;
     const long long rows_in = (long long)N * T * H * W, rows_out = (long long)N * T * Ho * Wo;
     // 31-bit byte offsets from the start of the first frame a tile touches: at most KT + 2 frames (a tile may end one sample and
     // begin the next) plus the lines it covers
     const long long span = ((long long)(KT + 2) * H * W + ((long long)CV_BM / Wo + 4) * STRIDE * W + 256) * ldx * 2;
     if (rows_out >= 0x7fffffffLL || span >= 0x7fffffffLL || (long long)KT * 9 * Cin * 2 * CV_BN >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-    Conv3dParams cp;
-    GemmParams& p = cp.g;
-    p.A = (const bf16_t*)x; p.W = (const bf16_t*)wk; p.C = y; p.bias = (const bf16_t*)bias;
-    p.R = (const bf16_t*)res; p.gate_txt = nullptr; p.gate_vid = nullptr; p.C2 = nullptr; p.U = nullptr;
-    p.M = (int)rows_out; p.N = Cout; p.K = KT * 9 * Cin; p.lda = (int)ldx; p.ldw = KT * 9 * Cin; p.ldc = (int)ldy; p.ldr = (int)ldr;
-    p.ldc2 = 0; p.ldu = 0; p.S = 1; p.St = 0; p.gate_bstride = 0; p.r_mod = 0; p.splits = 1;
-    cp.T = T; cp.H = H; cp.W = W; cp.Cin = Cin; cp.Ho = Ho; cp.Wo = Wo; cp.ldx = ldx; cp.x_rows = rows_in; cp.To = T; cp.tup = 0;
-    // kernel: the producer / consumer one (256-row tiles, persistent) where it was measured faster; VT_CONV_KERNEL=1|2 forces the
-    // 128-row / the producer-consumer kernel
-    static int kmode = -1, slots = 0;
-    if (kmode < 0) {
-        const char* e = getenv("VT_CONV_KERNEL");
-        kmode = e ? atoi(e) : 0;
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-        slots = cus >= 8 ? cus / 8 * 8 : 8;
-    }
+    // kernel: the producer / consumer one (256-row tiles, persistent) where it was measured faster; VT_CONV_KERNEL=1|2 and
+    // vt_conv3d_set_kernel force the 128-row / the producer-consumer kernel
+    const int kmode = c3_mode(), slots = g_c3_slots ? g_c3_slots : c3_device_slots();
     const int nbn = (Cout + CV_BN - 1) / CV_BN;
     const long long tiles_pc = ((rows_out + CP_BM - 1) / CP_BM) * nbn;
     const long long span_pc = ((long long)(KT + 2) * H * W + ((long long)CP_BM / Wo + 4) * STRIDE * W + 256) * ldx * 2;
     // measured (tools/kbench.py conv, VT_CONV_KERNEL=1 / 2): 128 -> 128 at 480x720 822 / 804 TFLOP/s, 256 -> 256 at 240x360 1024 / 1087,
     // at 120x180 1055 / 1048, 512 -> 512 at 60x90 1117 / 1065: the 256-row kernel pays only with two column tiles and many rounds
     const bool pc = span_pc < 0x7fffffffLL && (kmode == 2 || (kmode == 0 && nbn >= 2 && tiles_pc >= 16LL * slots));
+    pl->Ho = Ho; pl->Wo = Wo; pl->rows_in = rows_in; pl->rows_out = rows_out;
     if (pc) {
-        const int grid = tiles_pc < slots ? (int)((tiles_pc + 7) / 8 * 8) : slots;
-        if (res != nullptr) hipLaunchKernelGGL((conv3d_pc_kernel<KT, STRIDE, EPI_GATED_RES>), dim3(grid), dim3(512), 0, st, cp);
-        else hipLaunchKernelGGL((conv3d_pc_kernel<KT, STRIDE, EPI_BIAS>), dim3(grid), dim3(512), 0, st, cp);
+        pl->kernel = 2;
+        pl->grid = tiles_pc < slots ? (int)((tiles_pc + 7) / 8 * 8) : slots;
+        pl->tiles = (int)tiles_pc;
+        pl->tiles_per_wg = (int)((tiles_pc + pl->grid - 1) / pl->grid);
+    } else {
+        pl->kernel = 1;
+        pl->tiles = (int)((rows_out + CV_BM - 1) / CV_BM) * nbn;
+        pl->grid = pl->tiles;
+        pl->tiles_per_wg = 1;
+    }
+    return VT_OK;
+}
+
+template <int KT, int STRIDE>
+static int conv_launch(const void* x, long long ldx, const void* wk, const void* bias, const void* res, long long ldr, void* y, long long ldy,
+                       int N, int T, int H, int W, int Cin, int Cout, hipStream_t st) {
+    Conv3dPlan pl;
+    const int rc = conv_plan<KT, STRIDE>(ldx, N, T, H, W, Cin, Cout, &pl);
+    if (rc != VT_OK) return rc;
+    if ((ldy % 4) || ldy < Cout || (res != nullptr && ((ldr % 4) || ldr < Cout))) return VT_ERR_BAD_SHAPE;
+    if ((((uintptr_t)x) | ((uintptr_t)wk) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) return VT_ERR_BAD_ALIGN;
+    Conv3dParams cp;
+    GemmParams& p = cp.g;
+    p.A = (const bf16_t*)x; p.W = (const bf16_t*)wk; p.C = y; p.bias = (const bf16_t*)bias;
+    p.R = (const bf16_t*)res; p.gate_txt = nullptr; p.gate_vid = nullptr; p.C2 = nullptr; p.U = nullptr;
+    p.M = (int)pl.rows_out; p.N = Cout; p.K = KT * 9 * Cin; p.lda = (int)ldx; p.ldw = KT * 9 * Cin; p.ldc = (int)ldy; p.ldr = (int)ldr;
+    p.ldc2 = 0; p.ldu = 0; p.S = 1; p.St = 0; p.gate_bstride = 0; p.r_mod = 0; p.splits = 1;
+    cp.T = T; cp.H = H; cp.W = W; cp.Cin = Cin; cp.Ho = pl.Ho; cp.Wo = pl.Wo; cp.ldx = ldx; cp.x_rows = pl.rows_in; cp.To = T; cp.tup = 0;
+    if (pl.kernel == 2) {
+        if (res != nullptr) hipLaunchKernelGGL((conv3d_pc_kernel<KT, STRIDE, EPI_GATED_RES>), dim3(pl.grid), dim3(512), 0, st, cp);
+        else hipLaunchKernelGGL((conv3d_pc_kernel<KT, STRIDE, EPI_BIAS>), dim3(pl.grid), dim3(512), 0, st, cp);
         return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
     }
-    const int nbm = (p.M + CV_BM - 1) / CV_BM;
-    if (res != nullptr) hipLaunchKernelGGL((conv3d_cl_kernel<KT, STRIDE, EPI_GATED_RES>), dim3(nbm * nbn), dim3(256), 0, st, cp);
-    else hipLaunchKernelGGL((conv3d_cl_kernel<KT, STRIDE, EPI_BIAS>), dim3(nbm * nbn), dim3(256), 0, st, cp);
+    if (res != nullptr) hipLaunchKernelGGL((conv3d_cl_kernel<KT, STRIDE, EPI_GATED_RES>), dim3(pl.grid), dim3(256), 0, st, cp);
+    else hipLaunchKernelGGL((conv3d_cl_kernel<KT, STRIDE, EPI_BIAS>), dim3(pl.grid), dim3(256), 0, st, cp);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
+}
+
+// Host-only query, no launch: the kernel (1 = 128-row, 2 = producer / consumer), grid, number of output tiles and the most tiles one
+// workgroup walks that vt_causal_conv3d_cl (kt = 3, stride = 1) / vt_downsample_conv2d_cl (kt = 1, stride = 2) would take for this
+// geometry under the current vt_conv3d_set_kernel setting.  Each output pointer may be NULL.
+extern "C" int vt_conv3d_plan(long long ldx, int N, int T, int H, int W, int Cin, int Cout, int kt, int stride,
+                              int* kernel, int* grid, int* tiles, int* tiles_per_wg) {
+    Conv3dPlan pl;
+    int rc;
+    if (kt == 3 && stride == 1) rc = conv_plan<3, 1>(ldx, N, T, H, W, Cin, Cout, &pl);
+    else if (kt == 1 && stride == 2) rc = conv_plan<1, 2>(ldx, N, T, H, W, Cin, Cout, &pl);
+    else return VT_ERR_BAD_SHAPE;
+    if (rc != VT_OK) return rc;
+    if (kernel) *kernel = pl.kernel;
+    if (grid) *grid = pl.grid;
+    if (tiles) *tiles = pl.tiles;
+    if (tiles_per_wg) *tiles_per_wg = pl.tiles_per_wg;
+    return VT_OK;
 }
 
 // x: bf16 [N, T, H, W, Cin] channels-last (position stride ldx >= Cin, a multiple of 8); wk: bf16 [Cout, 27 * Cin], tap-major
@@ -453,6 +520,12 @@ extern "C" int vt_causal_conv3d_cl(const void* x, long long ldx, const void* wk,
 extern "C" int vt_downsample_conv2d_cl(const void* x, long long ldx, const void* wk, const void* bias, void* y, long long ldy,
                                        int N, int T, int H, int W, int Cin, int Cout, void* stream) {
     return conv_launch<1, 2>(x, ldx, wk, bias, nullptr, 0, y, ldy, N, T, H, W, Cin, Cout, (hipStream_t)stream);
+}
+// The same with a residual (bf16 [N, T, H/2, W/2, Cout], position stride ldr) added to the result: conv3d_*_kernel<1, 2, EPI_GATED_RES>,
+// which the entry point above never reaches (tests; the VAE has no such layer)
+extern "C" int vt_downsample_conv2d_res_cl(const void* x, long long ldx, const void* wk, const void* bias, const void* res, long long ldr,
+                                           void* y, long long ldy, int N, int T, int H, int W, int Cin, int Cout, void* stream) {
+    return conv_launch<1, 2>(x, ldx, wk, bias, res, ldr, y, ldy, N, T, H, W, Cin, Cout, (hipStream_t)stream);
 }
 
 // The encoder's first convolution (RGB input): x bf16 [N,T,H,W,8] (8 channels per position, the unused ones zero), wk bf16

@@ -354,17 +354,43 @@ def causal_conv3d_in8(x, wk, bias, y):
     return y
 
 
-def downsample_conv2d(x, wk, bias, y):
-    """per frame: zero line / column at the bottom / right, 3x3 conv, stride 2.  x bf16 [N,T,H,W,Cin], y bf16 [N,T,H/2,W/2,Cout]"""
+def downsample_conv2d(x, wk, bias, y, residual=None):
+    """per frame: zero line / column at the bottom / right, 3x3 conv, stride 2.  x bf16 [N,T,H,W,Cin], y bf16 [N,T,H/2,W/2,Cout];
+    residual (optional, like y; no layer of the VAE has one -- the kernels' residual epilogue, for tests) is added to the result"""
     _req(x, BF16, "x", 5); _req(y, BF16, "y", 5); _req(wk, BF16, "wk", 2)
     N, T, H, W, Cin = x.shape
     Cout = y.shape[4]
     if tuple(y.shape[:4]) != (N, T, H // 2, W // 2) or tuple(wk.shape) != (Cout, 9 * Cin) or not wk.is_contiguous():
         raise ValueError(f"shape mismatch: x {tuple(x.shape)} wk {tuple(wk.shape)} y {tuple(y.shape)}")
     _cl_check(x, "x"); _cl_check(y, "y")
+    if residual is not None:
+        _req(residual, BF16, "residual", 5); _cl_check(residual, "residual")
+        if tuple(residual.shape) != tuple(y.shape):
+            raise ValueError("residual must have the shape of y")
+        check(load_library().vt_downsample_conv2d_res_cl(x.data_ptr(), x.stride(3), wk.data_ptr(), _p(bias), residual.data_ptr(),
+                                                         residual.stride(3), y.data_ptr(), y.stride(3), N, T, H, W, Cin, Cout, _stream()),
+              "vt_downsample_conv2d_res_cl")
+        return y
     check(load_library().vt_downsample_conv2d_cl(x.data_ptr(), x.stride(3), wk.data_ptr(), _p(bias), y.data_ptr(), y.stride(3),
                                                  N, T, H, W, Cin, Cout, _stream()), "vt_downsample_conv2d_cl")
     return y
+
+
+def conv3d_set_kernel(mode: int = 0, slots: int = 0):
+    """kernel of causal_conv3d / downsample_conv2d: 0 = by shape, 1 = always the 128-row kernel, 2 = the 256-row producer / consumer kernel
+    wherever its span check allows; slots: cap of its persistent grid, 0 = the device's own, else a multiple of 8 (tests, A/B timing)"""
+    check(load_library().vt_conv3d_set_kernel(mode, slots), "vt_conv3d_set_kernel")
+
+
+def conv3d_plan(N: int, T: int, H: int, W: int, Cin: int, Cout: int, kt: int = 3, stride: int = 1, ldx: int = 0):
+    """(kernel, grid, tiles, tiles_per_wg) of the launch causal_conv3d (kt 3, stride 1) / downsample_conv2d (kt 1, stride 2) would make for
+    this geometry under the current conv3d_set_kernel setting; no launch.  kernel: 1 = 128-row tiles, 2 = producer / consumer (256-row
+    tiles, persistent).  ldx: position stride of x, 0 = Cin"""
+    import ctypes as C
+    k, grid, tiles, per = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load_library().vt_conv3d_plan(ldx or Cin, N, T, H, W, Cin, Cout, kt, stride, C.byref(k), C.byref(grid), C.byref(tiles), C.byref(per)),
+          "vt_conv3d_plan")
+    return k.value, grid.value, tiles.value, per.value
 
 
 def temporal_pool_frames(T: int, keep_first: bool) -> int:
