@@ -15,7 +15,7 @@
  *   - return 0 on success, a negative VT_ERR_* otherwise; no C++ exception crosses the ABI;
  *   - compute entry points keep no state between calls and are safe from autograd's backward thread (one process per
  *     GPU, as PL's DDPStrategy runs the reference).  Five process-global TUNING knobs exist for tests and A/B timing only --
- *     vt_gemm_set_tile, vt_gemm_set_big_loop, vt_conv_set_tile, vt_conv3d_set_kernel, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
+ *     vt_gemm_set_tile, vt_gemm_set_big_loop, vt_conv_set_tile, vt_conv_set_slots, vt_conv3d_set_kernel, vt_attn_bwd_set_chain (and the VT_* environment variables read once at first use);
  *     they select between kernels that give the same results, the product path never calls them.
  *   - deviation from SURVEY 8(b)'s sketch of this ABI (vt_tensor descriptors, vt_<op>_params structs,
  *     vt_workspace_bytes_<op>, vt_last_error): arguments are flat pointers + leading dimensions (one ctypes call, no struct
@@ -85,6 +85,10 @@ int vt_gemm_big_last_wide(void);
 /* convolution tile choice: 0 = per shape (default), 1 = always the 128 x 128 kernels, 2 = the 320-wide loader / multiplier kernels whenever
  * Cout % 320 == 0 (tests and A/B timing; csrc/convnd.hip) */
 int vt_conv_set_tile(int mode);
+/* cap of the persistent grid of the 128 x 320 forward convolution kernel, process-global (tests; csrc/convnd.hip): 0 = the device's CU count
+ * (default), else 1 .. that count, so that a few thousand positions make workgroups walk several tiles.  The shape rule of vt_conv_cl keeps
+ * counting with the device's CUs.  Anything else: VT_ERR_BAD_SHAPE, nothing changes. */
+int vt_conv_set_slots(int slots);
 
 /* Weight-gradient GEMM: C[P,Q] (+)= alpha * sum_m A[m,P] * B[m,Q]  (A = dY [M,lda], B = X [M,ldb] bf16, C fp32).
  * P % 128 == 0, Q % 128 == 0.  Replaces: autograd's dW = dY^T X of every nn.Linear (full fine-tuning, config 3). */
@@ -485,6 +489,11 @@ int vt_dora_dm(const float* sum_g, const float* sum_gy, const void* bias, const 
 int vt_conv_cl(const void* x, long long ldx, const void* wk, const void* bias, const float* sbias, int sbias_ld,
                const void* res, long long ldr, void* y, long long ldy,
                int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw, int stride, void* stream);
+/* host-only query, no launch: what vt_conv_cl's launch for this geometry would be under the current vt_conv_set_tile / vt_conv_set_slots
+ * setting.  kernel: 1 = 128 x 128 tiles (one per workgroup), 2 = 128 x 320 tiles, persistent; grid: workgroups; tiles: output tiles of that
+ * kernel; tiles_per_wg: the most tiles one workgroup walks.  Each output pointer may be NULL.  Computed by the helper the launch follows. */
+int vt_conv_plan(long long ldx, long long ldy, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw,
+                 int stride, int* kernel, int* grid, int* tiles, int* tiles_per_wg);
 /* Weight gradient of the same convolution: dw[co, tap, ci] (+)= sum_m dy[m, co] * x[shift(m, tap), ci]; dw fp32 [Cout, taps*Cin],
  * overwritten or (accumulate != 0) added to.  One tap, no padding: the weight gradient of an nn.Linear of any (multiple-of-8) size.
  * Replaces: autograd's conv / linear weight gradients under loss.backward(). */
@@ -496,6 +505,13 @@ int vt_conv_dw_cl(const void* dy, long long lddy, const void* x, long long ldx, 
 int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x, long long ldx, float* dw, float* dbias,
                        int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw, int stride,
                        int accumulate, void* stream);
+/* host-only query, no launch: what vt_conv_dw_bias_cl's launch for this geometry would be under the current vt_conv_set_tile setting.
+ * kernel: 1 = 128 x 128 tiles (grid tiles x splits), 2 = 320-row tiles (grid tiles * splits); splits position ranges of m_chunk rows each
+ * (the last may be shorter; more than one: fp32 atomics onto a zeroed or accumulated dw); dbias_fused: 1 = the kernel adds the bias
+ * gradient itself, 0 = vt_group_colsum does; row_step > 0: a Linear over more rows than one descriptor spans, run in row chunks of that
+ * many, the other values describing the first chunk.  Each output pointer may be NULL.  Computed by the helper the launch follows. */
+int vt_conv_dw_plan(long long lddy, long long ldx, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw,
+                    int stride, int* kernel, int* tiles, int* splits, int* m_chunk, int* dbias_fused, long long* row_step);
 /* dst[b][c][r] = src[b][r][c] for nb bf16 matrices of rows x cols (multiples of 8), matrix b at src + b*src_boff / dst + b*dst_boff elements
  * (either offset may be negative): W^T of a Linear (torch: w.t().contiguous()) and, per tap, the flipped / channel-swapped weight of a
  * convolution's input-gradient convolution (replaces pack_conv_weight_dx's flip + permute + contiguous; lvdm/modules/networks/

@@ -34,6 +34,9 @@ PROTOTYPES = {
                           _vp, _i, _vp, _i, _i, _vp],
     "vt_gemm_bf16_block_tile": [_i, _i, _i],
     "vt_conv_set_tile": [_i],
+    "vt_conv_set_slots": [_i],
+    "vt_conv_plan": [_ll, _ll] + [_i] * 13 + [C.POINTER(C.c_int)] * 4,
+    "vt_conv_dw_plan": [_ll, _ll] + [_i] * 13 + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_longlong)],
     "vt_transpose_bf16": [_vp, _ll, _ll, _vp, _ll, _ll, _i, _i, _i, _vp],
     "vt_transpose_multi_bf16": [_vp, _i, _ll, _vp],
     "vt_gemm_nt_bf16": [_vp, _i, _vp, _i, _fp, _i, _i, _i, _i, _f, _i, _vp],

@@ -37,9 +37,25 @@ struct ConvNdParams {
 #define CN_OOB 0x80000000u
 // 0 = pick per shape, 1 = always the 128 x 128 kernels, 2 = the 320-wide kernels whenever the shape allows (tests, A/B timing)
 static int g_conv_tile = 0;
+// cap of convnd320_kernel's persistent grid: 0 = the device's CU count, else 1 .. that count (tests: with a small cap a few thousand positions
+// make workgroups walk several tiles).  The shape rule itself keeps counting with the device's CUs; the product path never sets it.
+static int g_conv_slots = 0;
+static int cn_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    }
+    return cus;
+}
 extern "C" int vt_conv_set_tile(int mode) {
     if (mode < 0 || mode > 2) return VT_ERR_BAD_SHAPE;
     g_conv_tile = mode;
+    return VT_OK;
+}
+extern "C" int vt_conv_set_slots(int slots) {
+    if (slots < 0 || slots > cn_cus()) return VT_ERR_BAD_SHAPE;
+    g_conv_slots = slots;
     return VT_OK;
 }
 __device__ __forceinline__ int dw3_key(int row) { return (row & 7) ^ (((row >> 3) & 1) << 2); }
@@ -386,6 +402,60 @@ extern "C" int vt_conv_desc_extents(long long ldx, long long lddy, int N, int T,
     return VT_OK;
 }
 
+// What vt_conv_cl does with a geometry: the plan vt_conv_plan reports and vt_conv_cl follows.
+struct ConvNdPlan {
+    int kernel;            // 1 = convnd_cl_kernel (128 x 128 tiles, one per workgroup), 2 = convnd320_kernel (128 x 320 tiles, persistent)
+    int grid;              // workgroups
+    int tiles;             // output tiles of that kernel
+    int tiles_per_wg;      // the most tiles one workgroup walks
+    int Ho, Wo;
+    long long rows_out, x_bytes;
+};
+static int cn_plan(long long ldx, long long ldy, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw,
+                   int stride, ConvNdPlan* pl) {
+    if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % CN_BK) || (Cout % 4)) return VT_ERR_BAD_SHAPE;
+    if (KT < 1 || KH < 1 || KW < 1 || stride < 1 || pt < 0 || ph < 0 || pw < 0 || 2 * pt != KT - 1) return VT_ERR_BAD_SHAPE;   // no temporal stride / shrink
+    const int Ho = (H + 2 * ph - KH) / stride + 1, Wo = (W + 2 * pw - KW) / stride + 1;
+    if (Ho <= 0 || Wo <= 0) return VT_ERR_BAD_SHAPE;
+    if ((ldx % 8) || (ldy % 4) || ldx < Cin || ldy < Cout) return VT_ERR_BAD_SHAPE;
+    const long long rows_in = (long long)N * T * H * W, rows_out = (long long)N * T * Ho * Wo;
+    const long long xb = cn_extent_bytes(rows_in, ldx, Cin);    // ends with the last row's Cin columns (x may be a column slice of a wider buffer)
+    if (xb >= 0x7fffffffLL || rows_out >= 0x7fffffffLL || (long long)KT * KH * KW * Cin * 2 * CN_BN >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+    pl->Ho = Ho; pl->Wo = Wo; pl->rows_out = rows_out; pl->x_bytes = xb;
+    const int nbm = (int)((rows_out + CN_BM - 1) / CN_BM), nbn = (Cout + CN_BN - 1) / CN_BN;
+    static int cn3_env = -1;                 // VT355_CONV320=0: always the 128 x 128 kernel (A/B)
+    if (cn3_env < 0) { const char* e = getenv("VT355_CONV320"); cn3_env = e ? atoi(e) : 1; }
+    // Cout = 320 (and 960): 2.5 (7.5) tiles of 128 -- there the 128 x 320 kernel wins 15 .. 25 % (profiles/r03_conv_kbench.txt); at 640 / 1280 the
+    // 128 x 128 kernel has no ragged tile, runs two workgroups per CU and is 4 .. 25 % faster
+    if (cn3_env && g_conv_tile != 1 && (Cout % 320) == 0 && ((Cout % 128) != 0 || g_conv_tile == 2)) {
+        const int cus3 = cn_cus();
+        // one workgroup per CU and pass (140 KiB of LDS): only when whole passes are >= 80 % full
+        const long long t3 = (long long)nbm * (Cout / 320), passes = (t3 + cus3 - 1) / cus3;
+        if (g_conv_tile == 2 || (t3 >= cus3 && (double)t3 >= 0.8 * (double)(passes * cus3))) {
+            const int cap = g_conv_slots ? g_conv_slots : cus3;
+            pl->kernel = 2; pl->tiles = (int)t3; pl->grid = (int)(t3 < cap ? t3 : cap);
+            pl->tiles_per_wg = (int)((t3 + pl->grid - 1) / pl->grid);
+            return VT_OK;
+        }
+    }
+    pl->kernel = 1; pl->tiles = pl->grid = nbm * nbn; pl->tiles_per_wg = 1;
+    return VT_OK;
+}
+
+// host-only query (tests): kernel, grid, tiles and the most tiles per workgroup of the launch vt_conv_cl would make for this geometry under the
+// current vt_conv_set_tile / vt_conv_set_slots setting.  Each output pointer may be NULL.
+extern "C" int vt_conv_plan(long long ldx, long long ldy, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw,
+                            int stride, int* kernel, int* grid, int* tiles, int* tiles_per_wg) {
+    ConvNdPlan pl;
+    const int rc = cn_plan(ldx, ldy, N, T, H, W, Cin, Cout, KT, KH, KW, pt, ph, pw, stride, &pl);
+    if (rc != VT_OK) return rc;
+    if (kernel) *kernel = pl.kernel;
+    if (grid) *grid = pl.grid;
+    if (tiles) *tiles = pl.tiles;
+    if (tiles_per_wg) *tiles_per_wg = pl.tiles_per_wg;
+    return VT_OK;
+}
+
 // x: bf16 [N,T,H,W,Cin] (position stride ldx), wk: bf16 [Cout, KT*KH*KW*Cin] tap-major (dt,dh,dw,ci); y: bf16
 // [N,T,Ho,Wo,Cout] with Ho = (H + 2 ph - KH) / stride + 1 (same for W); bias bf16 [Cout] | null; sbias fp32 [N, sbias_ld] | null;
 // res bf16 like y | null.  Cin % 64 == 0, Cout % 4 == 0, the whole x must span < 2 GiB.
@@ -393,41 +463,21 @@ extern "C" int vt_conv_cl(const void* x, long long ldx, const void* wk, const vo
                           const void* res, long long ldr, void* y, long long ldy,
                           int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw, int stride,
                           void* stream) {
-    if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin % CN_BK) || (Cout % 4)) return VT_ERR_BAD_SHAPE;
-    if (KT < 1 || KH < 1 || KW < 1 || stride < 1 || pt < 0 || ph < 0 || pw < 0 || 2 * pt != KT - 1) return VT_ERR_BAD_SHAPE;   // no temporal stride / shrink
-    const int Ho = (H + 2 * ph - KH) / stride + 1, Wo = (W + 2 * pw - KW) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return VT_ERR_BAD_SHAPE;
-    if ((ldx % 8) || (ldy % 4) || ldx < Cin || ldy < Cout || (res != nullptr && ((ldr % 4) || ldr < Cout))) return VT_ERR_BAD_SHAPE;
+    ConvNdPlan pl;
+    const int rc = cn_plan(ldx, ldy, N, T, H, W, Cin, Cout, KT, KH, KW, pt, ph, pw, stride, &pl);
+    if (rc != VT_OK) return rc;
+    if (res != nullptr && ((ldr % 4) || ldr < Cout)) return VT_ERR_BAD_SHAPE;
     if (sbias != nullptr && ((sbias_ld % 4) || sbias_ld < Cout)) return VT_ERR_BAD_SHAPE;
     if ((((uintptr_t)x) | ((uintptr_t)wk) | ((uintptr_t)y) | ((uintptr_t)res) | ((uintptr_t)sbias)) & 15) return VT_ERR_BAD_ALIGN;
-    const long long rows_in = (long long)N * T * H * W, rows_out = (long long)N * T * Ho * Wo;
-    const long long xb = cn_extent_bytes(rows_in, ldx, Cin);    // ends with the last row's Cin columns (x may be a column slice of a wider buffer)
-    if (xb >= 0x7fffffffLL || rows_out >= 0x7fffffffLL || (long long)KT * KH * KW * Cin * 2 * CN_BN >= 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+    const int Ho = pl.Ho, Wo = pl.Wo;
     ConvNdParams p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)wk; p.y = (bf16_t*)y; p.bias = (const bf16_t*)bias; p.sbias = sbias;
-    p.res = (const bf16_t*)res; p.ldx = ldx; p.ldy = ldy; p.ldr = ldr; p.x_bytes = xb; p.sbias_ld = sbias_ld;
+    p.res = (const bf16_t*)res; p.ldx = ldx; p.ldy = ldy; p.ldr = ldr; p.x_bytes = pl.x_bytes; p.sbias_ld = sbias_ld;
     p.rows_per_sample = T * Ho * Wo;
-    p.M = (int)rows_out; p.Cout = Cout; p.Cin = Cin; p.T = T; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
+    p.M = (int)pl.rows_out; p.Cout = Cout; p.Cin = Cin; p.T = T; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
     p.KT = KT; p.KH = KH; p.KW = KW; p.pt = pt; p.ph = ph; p.pw = pw; p.stride = stride;
-    const int nbm = (p.M + CN_BM - 1) / CN_BM, nbn = (Cout + CN_BN - 1) / CN_BN;
-    static int cn3_env = -1;                 // VT355_CONV320=0: always the 128 x 128 kernel (A/B)
-    if (cn3_env < 0) { const char* e = getenv("VT355_CONV320"); cn3_env = e ? atoi(e) : 1; }
-    // Cout = 320 (and 960): 2.5 (7.5) tiles of 128 -- there the 128 x 320 kernel wins 15 .. 25 % (profiles/r03_conv_kbench.txt); at 640 / 1280 the
-    // 128 x 128 kernel has no ragged tile, runs two workgroups per CU and is 4 .. 25 % faster
-    if (cn3_env && g_conv_tile != 1 && (Cout % 320) == 0 && ((Cout % 128) != 0 || g_conv_tile == 2) && (ldy % 4) == 0) {
-        static int cus3 = 0;
-        if (cus3 == 0) {
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus3, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus3 <= 0) cus3 = 256;
-        }
-        // one workgroup per CU and pass (140 KiB of LDS): only when whole passes are >= 80 % full
-        const long long t3 = (long long)nbm * (Cout / 320), passes = (t3 + cus3 - 1) / cus3;
-        if (g_conv_tile == 2 || (t3 >= cus3 && (double)t3 >= 0.8 * (double)(passes * cus3))) {
-            hipLaunchKernelGGL(convnd320_kernel, dim3((unsigned)(t3 < cus3 ? t3 : cus3)), dim3(768), 0, (hipStream_t)stream, p);
-            return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-        }
-    }
-    hipLaunchKernelGGL(convnd_cl_kernel, dim3(nbm * nbn), dim3(256), 0, (hipStream_t)stream, p);
+    if (pl.kernel == 2) hipLaunchKernelGGL(convnd320_kernel, dim3((unsigned)pl.grid), dim3(768), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(convnd_cl_kernel, dim3((unsigned)pl.grid), dim3(256), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }
 
@@ -792,14 +842,21 @@ extern "C" int vt_conv_dw_cl(const void* dy, long long lddy, const void* x, long
                              int accumulate, void* stream) {
     return vt_conv_dw_bias_cl(dy, lddy, x, ldx, dw, nullptr, N, T, H, W, Cin, Cout, KT, KH, KW, pt, ph, pw, stride, accumulate, stream);
 }
-extern "C" int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x, long long ldx, float* dw, float* dbias,
-                                  int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw, int stride,
-                                  int accumulate, void* stream) {
+// What vt_conv_dw_bias_cl does with a geometry: the plan vt_conv_dw_plan reports and vt_conv_dw_bias_cl follows.
+struct ConvDwPlan {
+    int kernel;            // 1 = conv_dw_kernel (128 x 128 tiles, grid tiles x splits), 2 = conv_dw320_kernel (320 x 128 tiles, grid tiles * splits)
+    int tiles, splits, m_chunk;
+    int dbias_fused;       // 1: the kernel adds the bias gradient itself, 0: vt_group_colsum does
+    long long row_step;    // > 0: a Linear over more rows than one descriptor spans, run in row chunks of this many; the rest describes the first
+    int Ho, Wo;
+    long long rows_out, x_bytes, dy_bytes;
+};
+static int cn_dw_plan(long long lddy, long long ldx, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw,
+                      int stride, ConvDwPlan* pl) {
     if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return VT_ERR_BAD_SHAPE;
     if (KT < 1 || KH < 1 || KW < 1 || stride < 1 || pt < 0 || ph < 0 || pw < 0 || 2 * pt != KT - 1) return VT_ERR_BAD_SHAPE;
     const int Ho = (H + 2 * ph - KH) / stride + 1, Wo = (W + 2 * pw - KW) / stride + 1;
     if (Ho <= 0 || Wo <= 0 || (ldx % 8) || (lddy % 8) || ldx < Cin || lddy < Cout || (Cin % 8)) return VT_ERR_BAD_SHAPE;    // a 16-byte chunk must stay inside one tap
-    if ((((uintptr_t)x) | ((uintptr_t)dy)) & 15 || (((uintptr_t)dw) & 3)) return VT_ERR_BAD_ALIGN;
     const long long rows_in = (long long)N * T * H * W, rows_out = (long long)N * T * Ho * Wo;
     // The descriptors end with the LOGICAL end of the last row (its Cin / Cout columns, rounded up to a 16-byte chunk), not at
     // rows * ld: when dy or x is a column slice of a wider buffer (the gradient of one half of a skip concatenation), rows * ld counted
@@ -813,24 +870,14 @@ extern "C" int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x,
         const long long ldmax = lddy > ldx ? lddy : ldx;
         const long long step = (0x7fffff00LL / (ldmax * 2) - 1) / 256 * 256;
         if (step < 256) return VT_ERR_BAD_SHAPE;
-        for (long long r0 = 0; r0 < rows_in; r0 += step) {
-            const long long n = rows_in - r0 < step ? rows_in - r0 : step;
-            const int rc = vt_conv_dw_bias_cl((const bf16_t*)dy + r0 * lddy, lddy, (const bf16_t*)x + r0 * ldx, ldx, dw, dbias, 1, 1, 1, (int)n, Cin, Cout,
-                                              1, 1, 1, 0, 0, 0, 1, (accumulate || r0 > 0) ? 1 : 0, stream);
-            if (rc != VT_OK) return rc;
-        }
+        const int rc = cn_dw_plan(lddy, ldx, 1, 1, 1, (int)(rows_in < step ? rows_in : step), Cin, Cout, 1, 1, 1, 0, 0, 0, 1, pl);
+        if (rc != VT_OK || pl->row_step) return VT_ERR_BAD_SHAPE;
+        pl->row_step = step;
         return VT_OK;
     }
-    ConvDwParams p;
-    p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.dw = dw; p.dbias = dbias; p.lddy = lddy; p.ldx = ldx; p.dy_bytes = yb; p.x_bytes = xb;
-    p.M = (int)rows_out; p.Cout = Cout; p.Cin = Cin; p.T = T; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
-    p.KT = KT; p.KH = KH; p.KW = KW; p.pt = pt; p.ph = ph; p.pw = pw; p.stride = stride; p.accumulate = accumulate;
+    pl->row_step = 0; pl->Ho = Ho; pl->Wo = Wo; pl->rows_out = rows_out; pl->x_bytes = xb; pl->dy_bytes = yb;
     const int taps = KT * KH * KW;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
+    const int cus = cn_cus();
     static int dw3_env = -1;                 // VT355_CONV_DW320=0: always the 128 x 128 kernel (A/B)
     if (dw3_env < 0) { const char* e = getenv("VT355_CONV_DW320"); dw3_env = e ? atoi(e) : 1; }
     if (dw3_env && g_conv_tile != 1 && (Cout % DW3_P) == 0 && (rows_out >= 2048 || g_conv_tile == 2)) {
@@ -847,20 +894,8 @@ extern "C" int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x,
         }
         int chunk3 = (int)((rows_out + best_s - 1) / best_s);
         chunk3 = (chunk3 + 31) / 32 * 32;
-        const int splits3 = (int)((rows_out + chunk3 - 1) / chunk3);
-        p.m_chunk = chunk3; p.splits = splits3;
-        cn_magic(Ho * Wo, &p.mg_hwo, &p.sh_hwo); cn_magic(Wo, &p.mg_wo, &p.sh_wo); cn_magic(T, &p.mg_t, &p.sh_t);
-        hipStream_t st3 = (hipStream_t)stream;
-        if (splits3 > 1 && !accumulate) {
-            if (hipMemsetAsync(dw, 0, (size_t)Cout * taps * Cin * 4, st3) != hipSuccess) return VT_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL(conv_dw320_kernel, dim3((unsigned)(t3 * splits3)), dim3(768), 0, st3, p);
-        return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
-    }
-    if (dbias != nullptr) {
-        if ((((uintptr_t)dbias) & 3) || lddy > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
-        const int rc = vt_group_colsum(dy, (int)lddy, nullptr, 0, nullptr, nullptr, dbias, nullptr, rows_out, Cout, 1, 0, 0, 0, 0, stream);
-        if (rc != VT_OK) return rc;
+        pl->kernel = 2; pl->tiles = (int)t3; pl->m_chunk = chunk3; pl->splits = (int)((rows_out + chunk3 - 1) / chunk3); pl->dbias_fused = 1;
+        return VT_OK;
     }
     const int tiles = ((Cout + 127) / 128) * ((taps * Cin + 127) / 128);
     long long want = (2LL * cus + (long long)tiles - 1) / (long long)tiles;                       // ~2 workgroups per CU
@@ -869,13 +904,62 @@ extern "C" int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x,
     if (splits < 1) splits = 1;
     int chunk = (int)((rows_out + splits - 1) / splits);
     chunk = (chunk + 63) / 64 * 64;
-    splits = (int)((rows_out + chunk - 1) / chunk);
-    p.m_chunk = chunk; p.splits = splits;
+    pl->kernel = 1; pl->tiles = tiles; pl->m_chunk = chunk; pl->splits = (int)((rows_out + chunk - 1) / chunk); pl->dbias_fused = 0;
+    return VT_OK;
+}
+
+// host-only query (tests): kernel, tiles, position splits and rows per split of the launch vt_conv_dw_bias_cl would make for this geometry under
+// the current vt_conv_set_tile setting, whether the kernel folds the bias gradient in (1) or vt_group_colsum computes it (0), and row_step > 0
+// when the call is run in row chunks of that many (the other values then describe the first chunk).  Each output pointer may be NULL.
+extern "C" int vt_conv_dw_plan(long long lddy, long long ldx, int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph,
+                               int pw, int stride, int* kernel, int* tiles, int* splits, int* m_chunk, int* dbias_fused, long long* row_step) {
+    ConvDwPlan pl;
+    const int rc = cn_dw_plan(lddy, ldx, N, T, H, W, Cin, Cout, KT, KH, KW, pt, ph, pw, stride, &pl);
+    if (rc != VT_OK) return rc;
+    if (kernel) *kernel = pl.kernel;
+    if (tiles) *tiles = pl.tiles;
+    if (splits) *splits = pl.splits;
+    if (m_chunk) *m_chunk = pl.m_chunk;
+    if (dbias_fused) *dbias_fused = pl.dbias_fused;
+    if (row_step) *row_step = pl.row_step;
+    return VT_OK;
+}
+
+extern "C" int vt_conv_dw_bias_cl(const void* dy, long long lddy, const void* x, long long ldx, float* dw, float* dbias,
+                                  int N, int T, int H, int W, int Cin, int Cout, int KT, int KH, int KW, int pt, int ph, int pw, int stride,
+                                  int accumulate, void* stream) {
+    ConvDwPlan pl;
+    const int prc = cn_dw_plan(lddy, ldx, N, T, H, W, Cin, Cout, KT, KH, KW, pt, ph, pw, stride, &pl);
+    if (prc != VT_OK) return prc;
+    if ((((uintptr_t)x) | ((uintptr_t)dy)) & 15 || (((uintptr_t)dw) & 3)) return VT_ERR_BAD_ALIGN;
+    if (pl.row_step) {
+        const long long rows_in = (long long)N * T * H * W, step = pl.row_step;
+        for (long long r0 = 0; r0 < rows_in; r0 += step) {
+            const long long n = rows_in - r0 < step ? rows_in - r0 : step;
+            const int rc = vt_conv_dw_bias_cl((const bf16_t*)dy + r0 * lddy, lddy, (const bf16_t*)x + r0 * ldx, ldx, dw, dbias, 1, 1, 1, (int)n, Cin, Cout,
+                                              1, 1, 1, 0, 0, 0, 1, (accumulate || r0 > 0) ? 1 : 0, stream);
+            if (rc != VT_OK) return rc;
+        }
+        return VT_OK;
+    }
+    const int Ho = pl.Ho, Wo = pl.Wo;
+    ConvDwParams p;
+    p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.dw = dw; p.dbias = dbias; p.lddy = lddy; p.ldx = ldx; p.dy_bytes = pl.dy_bytes; p.x_bytes = pl.x_bytes;
+    p.M = (int)pl.rows_out; p.Cout = Cout; p.Cin = Cin; p.T = T; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo;
+    p.KT = KT; p.KH = KH; p.KW = KW; p.pt = pt; p.ph = ph; p.pw = pw; p.stride = stride; p.accumulate = accumulate;
+    p.m_chunk = pl.m_chunk; p.splits = pl.splits;
     cn_magic(Ho * Wo, &p.mg_hwo, &p.sh_hwo); cn_magic(Wo, &p.mg_wo, &p.sh_wo); cn_magic(T, &p.mg_t, &p.sh_t);
+    const int taps = KT * KH * KW;
     hipStream_t st = (hipStream_t)stream;
-    if (splits > 1 && !accumulate) {
+    if (!pl.dbias_fused && dbias != nullptr) {
+        if ((((uintptr_t)dbias) & 3) || lddy > 0x7fffffffLL) return VT_ERR_BAD_SHAPE;
+        const int rc = vt_group_colsum(dy, (int)lddy, nullptr, 0, nullptr, nullptr, dbias, nullptr, pl.rows_out, Cout, 1, 0, 0, 0, 0, stream);
+        if (rc != VT_OK) return rc;
+    }
+    if (pl.splits > 1 && !accumulate) {
         if (hipMemsetAsync(dw, 0, (size_t)Cout * taps * Cin * 4, st) != hipSuccess) return VT_ERR_LAUNCH;
     }
-    hipLaunchKernelGGL(conv_dw_kernel, dim3(tiles, splits), dim3(256), 0, st, p);
+    if (pl.kernel == 2) hipLaunchKernelGGL(conv_dw320_kernel, dim3((unsigned)((long long)pl.tiles * pl.splits)), dim3(768), 0, st, p);
+    else hipLaunchKernelGGL(conv_dw_kernel, dim3(pl.tiles, pl.splits), dim3(256), 0, st, p);
     return hipGetLastError() == hipSuccess ? VT_OK : VT_ERR_LAUNCH;
 }

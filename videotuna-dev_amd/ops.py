@@ -550,9 +550,34 @@ def attn_bwd_chain_errors_clear():
         ws[64:256].zero_()
 
 
-def conv_set_tile(mode: int = 0):
-    """0 = per shape, 1 = always the 128 x 128 convolution kernels, 2 = the 320-wide kernels whenever Cout % 320 == 0 (tests, A/B timing)"""
-    check(load_library().vt_conv_set_tile(mode), "vt_conv_set_tile")
+def conv_set_tile(mode: int = 0, slots: int = 0):
+    """0 = per shape, 1 = always the 128 x 128 convolution kernels, 2 = the 320-wide kernels whenever Cout % 320 == 0; slots: cap of the
+    128 x 320 forward kernel's persistent grid, 0 = the device's CU count, else 1 .. that count (tests, A/B timing)"""
+    lib = load_library()
+    check(lib.vt_conv_set_slots(slots), "vt_conv_set_slots")
+    check(lib.vt_conv_set_tile(mode), "vt_conv_set_tile")
+
+
+def conv_plan(N: int, T: int, H: int, W: int, Cin: int, Cout: int, kernel=(1, 3, 3), padding=(0, 1, 1), stride: int = 1, ldx: int = 0, ldy: int = 0):
+    """(kernel, grid, tiles, tiles_per_wg) of the launch conv_cl would make for this geometry under the current conv_set_tile setting; no
+    launch.  kernel: 1 = 128 x 128 tiles (one per workgroup), 2 = 128 x 320 tiles, persistent.  ldx / ldy: position strides, 0 = Cin / Cout"""
+    import ctypes as C
+    k, grid, tiles, per = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    check(load_library().vt_conv_plan(ldx or Cin, ldy or Cout, N, T, H, W, Cin, Cout, *kernel, *padding, stride, C.byref(k), C.byref(grid),
+                                      C.byref(tiles), C.byref(per)), "vt_conv_plan")
+    return k.value, grid.value, tiles.value, per.value
+
+
+def conv_dw_plan(N: int, T: int, H: int, W: int, Cin: int, Cout: int, kernel=(1, 3, 3), padding=(0, 1, 1), stride: int = 1, ldx: int = 0, lddy: int = 0):
+    """(kernel, tiles, splits, m_chunk, dbias_fused, row_step) of the launch conv_dw_cl / linear_dw (N = T = H = 1, W = rows, one tap) would
+    make under the current conv_set_tile setting; no launch.  kernel: 1 = 128 x 128 tiles, 2 = 320-row tiles; splits x m_chunk cover the
+    output positions; dbias_fused: 1 = the kernel adds the bias gradient, 0 = the column-sum kernel does; row_step > 0: the call runs in row
+    chunks of that many and the other values describe the first"""
+    import ctypes as C
+    k, tiles, splits, chunk, fused, step = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_longlong(0)
+    check(load_library().vt_conv_dw_plan(lddy or Cout, ldx or Cin, N, T, H, W, Cin, Cout, *kernel, *padding, stride, C.byref(k), C.byref(tiles),
+                                         C.byref(splits), C.byref(chunk), C.byref(fused), C.byref(step)), "vt_conv_dw_plan")
+    return k.value, tiles.value, splits.value, chunk.value, fused.value, step.value
 
 
 def gemm_set_tile(mode: int = 0):
